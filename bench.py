@@ -6,10 +6,19 @@ move, random-init residual policy/value net (32 filters, 3 residual blocks), sel
 (Dirichlet alpha 0.3, fraction 0.25, 6 sampled opening moves).  Synthetic data: games start from the
 empty board, weights are seeded random-init.  Leaves are evaluated in the REFERENCE's precision (the reference's net is
 float32, model.py:252-282): `dtype: "f32x3"` = every fp32 operand as an fp16 hi + lo pair, three MFMAs per product, fp32
-accumulation.  The opt-in fp16-storage mode (`--net-precision f16`) is timed in a short second run and reported as the
-secondary block `f16_storage_mode` of the same line -- it is NOT the headline.
+accumulation.  With `--full`, the opt-in fp16-storage mode (`--net-precision f16`) is timed in a short second run and
+reported as the secondary block `f16_storage_mode` of the same line -- it is NOT the headline.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, pre-rolls, warms up, times the K steps and prints the line.  `--full` adds what the headline does
+not need, after the timed region: the short run of the other fused-net precision (`--precise-compare`) and the
+CPU baseline (`--cpu-seconds`, `--no-cpu-baseline`).  `--dump-outputs DIR`, after the measurement, writes the packed
+training records the timed path delivers for a fixed set of games -- the `--slots` games it starts with (ids 0 ..
+slots-1), played to the end by an engine built like the timed one -- as DIR/<name>.npy, float32 / float64, sorted by
+game id.  A step is a budget of shader cycles, so WHICH games the last timed step finishes differs from run to run; a
+game's records depend only on its id (RNG keyed by seed, game id and ply) and the fixed weights, so these arrays are
+the same in every run and two builds can be compared array for array.
 
 A "step" = ONE launch of the persistent self-play kernel (c4_selfplay_split_kernel: tree waves + network waves): `--quanta-per-step`
 (256) time quanta of `--time-budget` (80,000) shader cycles for every one of the 4096 games per GPU,
@@ -107,9 +116,20 @@ def parse_args(argv=None):
                     help="launcher / rendezvous / reduction plumbing only (no GPU, gloo): what the CPU test of --gpus N runs; "
                          "the line it prints is flagged dry_run and carries no measurement")
     ap.add_argument("--precise-compare", type=int, default=1,
-                    help="1: at N=1 also time a short run of the OTHER fused-net precision (f16 storage next to the f32x3 headline, "
-                         "or the reverse) and report its throughput as a secondary block")
-    return ap.parse_args(argv)
+                    help="with --full, 1: at N=1 also time a short run of the OTHER fused-net precision (f16 storage next to the "
+                         "f32x3 headline, or the reverse) and report its throughput as a secondary block")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (other precision, CPU baseline) after the timed region; "
+                         "a plain run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the measurement, write the packed training records of the timed path's opening games (ids 0 .. "
+                         "slots-1, played to the end) to DIR/<name>.npy (rank 0)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 def cpu_baseline(state_dict, sims, seconds, n_games):
@@ -178,7 +198,7 @@ def launch_ranks(args, argv):
     return proc.wait()
 
 
-def make_selfplay(args, sd, rank, local_rank, precision):
+def make_selfplay(args, sd, rank, local_rank, precision, games_target=-1, record_capacity_games=0):
     import torch
     from connect4_amd.config import MCTSConfig
     from connect4_amd.net import InferenceNet
@@ -191,7 +211,7 @@ def make_selfplay(args, sd, rank, local_rank, precision):
         tdt = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[args.net_dtype]
         net = InferenceNet(sd, device="cuda:%d" % local_rank, dtype=tdt)
     sp = SelfPlay(net, args.slots, MCTSConfig.self_play(args.sims), seed=rank, device=local_rank,
-                  games_target=-1, record_capacity_games=0, planes_dtype=tdt,
+                  games_target=games_target, record_capacity_games=record_capacity_games, planes_dtype=tdt,
                   use_graph=not args.no_graph, steps_per_graph=args.steps_per_graph, max_inner_iters=args.max_inner,
                   eval_cache_log2_entries=args.eval_cache, level_budget=args.level_budget, time_budget_cycles=args.time_budget, pipeline=args.pipeline,
                   fused_loop=bool(args.fused_loop), steps_per_launch=args.quanta_per_step)
@@ -257,6 +277,79 @@ def timed_region(sp, args, barrier):
     d["games_finished_total"] = s1["games_finished"]
     d["dropped_games_total"] = s1["dropped_games"]
     return elapsed, gpu_ms, d
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_S = 600.0
+
+
+def opening_games(args, sd, rank, local_rank):
+    """The games the timed engine starts with (ids 0 .. slots-1, played during its pre-roll), played again to the end by
+    an engine built like it -- same kernel, net, settings and seed -- and returned as PackedGames on the host, sorted
+    by id.  A game's moves, values and policies depend only on its id (the RNG is keyed by seed, game id and ply), so
+    these records are the same in every run; which games the last timed step finishes is not, since a step is a budget
+    of shader cycles."""
+    sp, net = make_selfplay(args, sd, rank, local_rank, args.net_precision, games_target=args.slots,
+                            record_capacity_games=args.slots)
+    try:
+        if args.pmc_mode:
+            sp._fused_loop, sp._use_graph = False, False
+        t0 = time.perf_counter()
+        st = sp.stats()
+        while st["active_slots"] > 0:
+            if time.perf_counter() - t0 > DUMP_MAX_S:
+                raise RuntimeError("--dump-outputs: the opening games did not finish in %.0f s: %r" % (DUMP_MAX_S, st))
+            sp.run_steps(args.quanta_per_step)
+            st = sp.stats()
+        if st["dropped_games"]:
+            raise RuntimeError("--dump-outputs: %d finished games were dropped" % st["dropped_games"])
+        packed = sp.engine.export_games(args.slots).cpu().sorted_by_id()
+    finally:
+        sp.close()
+        if hasattr(net, "close"):
+            net.close()
+    if packed.n_games != args.slots:
+        raise RuntimeError("--dump-outputs: %d of %d opening games exported" % (packed.n_games, args.slots))
+    return packed
+
+
+def write_outputs(p, out_dir):
+    """PackedGames (host tensors) -> DIR/<name>.npy in float32 / float64 (bitboards < 2^49 and ids are exact in float64).
+    Above DUMP_MAX_BYTES a fixed seeded sample of the games is written instead (`sampled_games` says which)."""
+    import numpy as np
+    per_pos = ("boards", "moves", "values", "policy", "targets", "game_index")
+    n_games, n_pos = p.n_games, p.n_positions
+    arrays = {
+        "boards": p.boards.numpy().astype(np.float64),           # [positions, 2] bitboards before the move
+        "moves": p.moves.numpy().astype(np.float32),
+        "values": p.values.numpy().astype(np.float32),           # chosen child's value (NaN where the reference has None)
+        "policy": p.policy.numpy().astype(np.float32),           # [positions, 7] visit policy
+        "targets": p.targets.numpy().astype(np.float32),         # game result value per position
+        "game_index": p.game_index.numpy().astype(np.float64),
+        "lengths": p.lengths.numpy().astype(np.float32),
+        "results": p.results.numpy().astype(np.float32),
+        "ids": p.ids.numpy().astype(np.float64),
+    }
+    if sum(a.nbytes for a in arrays.values()) + 16 > DUMP_MAX_BYTES:
+        # games in a fixed seeded order while they fit: per position and per game (+ its sampled_games entry) bytes
+        pos_b = sum(arrays[k][:1].nbytes for k in per_pos)
+        game_b = sum(arrays[k][:1].nbytes for k in ("lengths", "results", "ids")) + 8
+        cost = arrays["lengths"].astype(np.int64) * pos_b + game_b
+        order = np.random.RandomState(0).permutation(n_games)
+        fits = np.cumsum(cost[order]) <= DUMP_MAX_BYTES - 16
+        games = np.sort(order[fits])
+        pos = np.isin(arrays["game_index"].astype(np.int64), games)
+        for k in per_pos:
+            arrays[k] = arrays[k][pos]
+        for k in ("lengths", "results", "ids"):
+            arrays[k] = arrays[k][games]
+        arrays["game_index"] = np.searchsorted(games, arrays["game_index"].astype(np.int64)).astype(np.float64)
+        arrays["sampled_games"] = games.astype(np.float64)
+    arrays["game_counts"] = np.array([n_games, n_pos], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def run_rank(args):
@@ -443,7 +536,9 @@ def run_rank(args):
     sp.close()
     if hasattr(net, "close"):
         net.close()
-    if rank == 0 and world == 1:
+    if rank == 0 and args.dump_outputs:
+        write_outputs(opening_games(args, sd, rank, local_rank), args.dump_outputs)
+    if rank == 0 and world == 1 and args.full:
         if args.precise_compare and fused_timed and args.filters == 32:
             if args.net_precision == "f16":
                 out["reference_precision_mode"] = precise_compare(args, sd, out, "f32x3")
@@ -584,6 +679,8 @@ def main(argv=None):
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: become the launcher.  Nothing in this process has touched the GPU
         # (no torch import, no HIP call), and the ranks are children -- this process is never replaced.
+        if args.dump_outputs:
+            argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]   # the ranks run in ROOT
         return launch_ranks(args, argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:

@@ -21,6 +21,8 @@ What is written (all data: inputs + expected outputs, no reference source text):
   train_step.npz      ModelWrapper.train (model.py:200-240) on a seeded net and a small seeded dataset:
                       initial weights, the dataset, torch seed, final weights / BN statistics / momentum
                       (`python gen_golden.py train` regenerates only this file)
+  reference_result.json  the members of oinkoink.utils.Result (name -> value) that the reference's callers
+                      compare this package's results with (`python gen_golden.py result` regenerates only this file)
 """
 import json
 import os
@@ -363,10 +365,19 @@ def dump_train_step():
     np.savez_compressed(os.path.join(OUT, "train_step.npz"), **blobs)
 
 
+def dump_result_enum():
+    with open(os.path.join(OUT, "reference_result.json"), "w") as f:
+        json.dump({m.name: m.value for m in Result}, f, indent=1)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "train":
         dump_train_step()
         print("train_step.npz written to", OUT)
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "result":
+        dump_result_enum()
+        print("reference_result.json written to", OUT)
         return
     torch.manual_seed(0)
     torch.set_num_threads(1)  # deterministic accumulation order for the recorded net outputs
@@ -378,6 +389,7 @@ def main():
     dump_search_net(model)
     dump_selfplay(model)
     dump_train_step()
+    dump_result_enum()
     print("golden fixtures written to", OUT)
 
 

