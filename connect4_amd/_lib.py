@@ -110,6 +110,10 @@ SIGNATURES = {
     "c4_board_planes": (C.c_int, [C.c_int, _u64p, _u64p, C.c_int32, _f32p]),
     "c4_board_fliplr": (C.c_int, [C.c_int, _u64p, _u64p, C.c_int32, _u64p, _u64p]),
     "c4_board_centre_value": (C.c_int, [C.c_int, _u64p, _u64p, C.c_int32, _f64p]),
+    "c4_grid_search": (C.c_int, [C.c_int, _u64p, _u64p, C.c_int32, C.c_int32, _f64p, _f64p, _i32p]),
+    "c4_grid_frontier": (C.c_int, [C.c_int, _u64p, _u64p, C.c_int32, C.c_int32, _u64p, _u64p, C.c_int64, _i64p]),
+    "c4_grid_finish": (C.c_int, [C.c_int, _u64p, _u64p, C.c_int32, C.c_int32, _f64p, C.c_int64, _f64p, _f64p, _i32p]),
+    "c4_grid_last_error": (C.c_char_p, []),
     "c4_debug_stamps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "c4_debug_fused_net_stamps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "c4_debug_latency_stamps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),

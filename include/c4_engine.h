@@ -289,6 +289,29 @@ int c4_board_fliplr(int device, const uint64_t *color0, const uint64_t *color1, 
 /* evaluators.py:28-33 evaluate_centre (float64) */
 int c4_board_centre_value(int device, const uint64_t *color0, const uint64_t *color1, int32_t n, double *out);
 
+/* -- fixed-depth negamax, the reference's GridSearch (c4_grid.hip) ---------------------------- */
+/* grid_search.py:10-71 + tree.py:68-72,119-131: exhaustive negamax `plies` deep (1..42) below each of n
+ * undecided positions, evaluate_centre (evaluators.py:28-33) at the depth-0 leaves.  Per position:
+ * child_values float64 [n][7] = the root children's absolute_value (tree.py:27-38: a finished child gives
+ * its result without the age term; NaN for an illegal column), root_value float64 [n] = the root's
+ * search_value, move int32 [n] = Tree.best_move (ties to the higher column).  A finished or malformed
+ * position, or plies out of range: C4_EINVAL.  Messages of all c4_grid_* calls: c4_grid_last_error().
+ * Test aids (environment, read per call): C4_GRID_LEVEL_CAP (most nodes of one expanded level, >= 7;
+ * default 2^21) and C4_GRID_FILL_NODES (level size at which the depth-first tail starts; default half the
+ * device's resident lanes) change how the work is split, never the answers. */
+int c4_grid_search(int device, const uint64_t *color0, const uint64_t *color1, int32_t n, int32_t plies,
+                   double *child_values, double *root_value, int32_t *move);
+/* grid_search.py:51-54 with any other scalar evaluator, step 1: the undecided positions `plies` deep, in
+ * the order the reference calls its evaluator on them (repeats included), into leaf0/leaf1 [cap];
+ * *n_leaves = their number (C4_ECAPACITY if it exceeds cap: call again with a larger buffer). */
+int c4_grid_frontier(int device, const uint64_t *color0, const uint64_t *color1, int32_t n, int32_t plies,
+                     uint64_t *leaf0, uint64_t *leaf1, int64_t cap, int64_t *n_leaves);
+/* step 2: leaf_values float64 [n_leaves], the evaluator's value of each c4_grid_frontier leaf in its
+ * order (C4_EINVAL if n_leaves is not the frontier's size); outputs as c4_grid_search. */
+int c4_grid_finish(int device, const uint64_t *color0, const uint64_t *color1, int32_t n, int32_t plies,
+                   const double *leaf_values, int64_t n_leaves, double *child_values, double *root_value, int32_t *move);
+const char *c4_grid_last_error(void);
+
 /* -- fused leaf-batch network (c4_net.hip) -------------------------------------------------- */
 /* Eval-mode forward of the reference's Net (oinkoink/neural/pytorch/model.py:120-134) as ONE
  * gfx950 MFMA kernel reading the leaves' bitboards; stands in for ModelWrapper._call_list
