@@ -1,8 +1,10 @@
 """The PRODUCTION random streams (C4_RNG_PHILOX): Marsaglia-Tsang Gamma(alpha) draws on Philox4x32-10 for the
 root's Dirichlet noise (mcts.py:171-181) and the inverse-CDF sample of the opening moves proportional to value^2
-(mcts.py:81-82, tree.py:75-82).  Parity tests inject tapes, so nothing else exercises these; here their
-distributions are tested through read-outs that run the very device functions the kernels call
-(c4_debug_root_noise / c4_debug_sample_move).  All bounds are >= 5 sigma for the sample sizes used."""
+(mcts.py:81-82, tree.py:75-82), through read-outs that run the very device functions the kernels call
+(c4_debug_root_noise / c4_debug_sample_move).  Exactly: the device's draws against the host model oracle/philox_ref.py
+on 100 k (seed, game id, ply) keys -- uniforms bit for bit, Gamma draws within a stated tolerance -- which is what lets
+tests/test_gpu_production_replay.py replay Philox-mode games move for move on the oracle.  Statistically: their
+distributions, with bounds >= 5 sigma for the sample sizes used."""
 import numpy as np
 import pytest
 
@@ -10,6 +12,71 @@ pytestmark = pytest.mark.gpu
 
 N = 120_000
 ALPHA = 0.3
+# Device Gamma draw vs the host model: stated before the first measurement.  The draws can only differ through ocml's
+# log / cos / pow against the host libm (about an ulp each) and the cancellation in 1 + c*x; a different accept/reject
+# branch would show as an error of order 1, not 1e-12.
+GAMMA_REL_TOL = 1e-12
+MODEL_SEEDS = [0x2545F491, (1 << 32) + 7, 0x9E3779B97F4A7C15, (1 << 64) - 1]     # three with the high word set
+MODEL_ALPHAS = [0.03, 0.3, 1.0, 2.5]
+
+
+def _model_keys(n, seed):
+    """n (game id, ply) keys: every ply 0..41, game ids up to 2^40 with the 2^32 boundary on both sides."""
+    rng = np.random.RandomState(seed)
+    gid = rng.randint(0, 1 << 40, size=n).astype(np.int64)
+    gid[:8] = [0, 1, (1 << 32) - 1, 1 << 32, (1 << 32) + 1, (1 << 33) + 5, (1 << 40) - 1, 4095]
+    gid[8:n // 4] = rng.randint(0, 1 << 16, size=n // 4 - 8)            # small ids too, as a generation has them
+    ply = (np.arange(n) % 42).astype(np.int32)
+    return gid, ply
+
+
+def test_device_uniforms_are_the_host_models_bit_for_bit():
+    """uniform_out of c4_debug_sample_move (rng_uniform2(seed, gid, ply, 32, 0).u0, the opening-move draw) against
+    philox_ref.uniform2 on 4 x 25 k keys."""
+    from connect4_amd.engine import debug_sample_move
+    from oracle import philox_ref as R
+    n, total, differ = 25_000, 0, 0
+    V = np.tile(np.linspace(0.2, 0.8, 7), (n, 1))
+    for k, seed in enumerate(MODEL_SEEDS):
+        gid, ply = _model_keys(n, 100 + k)
+        dev, _ = debug_sample_move(seed, gid, ply, V, np.full(n, 7, dtype=np.int32))
+        want, _ = R.uniform2(seed, gid, ply, R.MOVE_STREAM, 0)
+        differ += int(np.count_nonzero(dev.view(np.uint64) != want.view(np.uint64)))
+        total += n
+    print("uniforms: %d device draws against the host model, %d not bit-equal" % (total, differ))
+    assert differ == 0
+
+
+@pytest.mark.parametrize("alpha", MODEL_ALPHAS)
+def test_device_gamma_draws_are_the_host_models(alpha):
+    """gamma_raw of c4_debug_root_noise (rng_gamma for the 7 columns) against philox_ref.gamma on 4 x 25 k keys x 7
+    streams: relative error <= GAMMA_REL_TOL.  Prints the worst error and the number of draws that are not bit-equal; a draw
+    beyond the tolerance is reported with the Marsaglia-Tsang round and branch the model took."""
+    from connect4_amd.engine import debug_root_noise
+    from oracle import philox_ref as R
+    n = 25_000
+    worst, differ, total, bad = 0.0, 0, 0, []
+    for k, seed in enumerate(MODEL_SEEDS):
+        gid, ply = _model_keys(n, 200 + k)
+        dev, _ = debug_root_noise(seed, alpha, gid, ply, np.full(n, 0x7f, dtype=np.int32))
+        want, rnd = R.gamma_with_round(seed, gid[:, None], ply[:, None].astype(np.int64), np.arange(7)[None, :], alpha)
+        assert np.all(np.isfinite(dev)) and np.all(dev >= 0)
+        err = np.abs(dev - want)
+        rel = np.where(want > 0, err / np.where(want > 0, want, 1.0), np.where(err > 0, np.inf, 0.0))
+        worst = max(worst, float(rel.max()))
+        differ += int(np.count_nonzero(dev.view(np.uint64) != want.view(np.uint64)))
+        total += dev.size
+        for i, c in zip(*np.nonzero(rel > GAMMA_REL_TOL)):
+            bad.append(dict(seed=seed, gid=int(gid[i]), ply=int(ply[i]), col=int(c), device=float(dev[i, c]), model=float(want[i, c]),
+                            model_round=int(rnd[i, c])))
+    for b in bad[:10]:     # which round the device's value belongs to, and the branch the model takes in that round
+        cand = R.gamma_round_values_scalar(b["seed"], b["gid"], b["ply"], b["col"], alpha)
+        r = min(cand, key=lambda t: abs(cand[t][0] - b["device"]))
+        b.update(device_round=r, model_branch_in_that_round=cand[r][1])
+    print("gamma(%g): %d device draws against the host model, worst relative error %.3g, %d not bit-equal"
+          % (alpha, total, worst, differ))
+    assert not bad, bad[:10]
+    assert worst <= GAMMA_REL_TOL
 
 
 def _keys(n, seed=0):
