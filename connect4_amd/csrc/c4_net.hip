@@ -150,6 +150,21 @@ int c4_net_create(int device, const c4_net_desc *desc, c4_net **out)
                  "(the hi/lo planes of %d filters do not fit a wave's private LDS)", FW);
         return C4_EINVAL;
     }
+    // the folded conv weights are stored in fp16 (the hi parts in C4_NET_F32X3): one beyond +-65504 would become inf and,
+    // times an out-of-board zero tap, NaN in every answer.  NaN weights pass (the kernels contain a net that answers NaN).
+    {
+        const int R0 = desc->n_residuals;
+        const struct { const char *name; const float *w; size_t n; } fp16_stored[3] = {
+            {"stem_w", desc->stem_w, (size_t)FW * 27}, {"conv_w", desc->conv_w, (size_t)2 * R0 * FW * FW * 9},
+            {"head_w", desc->head_w, (size_t)3 * FW}};
+        for (const auto &t : fp16_stored)
+            for (size_t i = 0; i < t.n; ++i)
+                if (std::fabs(t.w[i]) > 65504.0f) {
+                    snprintf(n_err, 512, "c4_net_create: folded weight %s[%zu] = %g lies beyond fp16's range (+-65504)", t.name, i,
+                             (double)t.w[i]);
+                    return C4_EINVAL;
+                }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) {
         snprintf(n_err, 512, "no usable HIP device %d: the fused net has no CPU fallback", device);

@@ -14,6 +14,45 @@ from . import _lib as L
 from .net import PolicyValueNet, _fold_bn
 
 
+def fold_for_fused(state_dict, dtype=np.float32) -> dict:
+    """What FusedNet hands to c4_net_create, as a pure function of a state dict: the arrays of c4_net_desc (layouts in
+    include/c4_engine.h) -- eval-mode BatchNorm folded into the convolutions, the head 1x1 convs stacked value first, the
+    value head's activation-free Linear stack collapsed into one affine map (identity for n_fc_layers = 0) -- and its
+    scalars vout_b, w1, w2.  The fold runs in float64; dtype=np.float64 returns it before the float32 rounding."""
+    import torch
+    sd = {k: v.detach().cpu() for k, v in state_dict.items()}
+    cfg = PolicyValueNet.config_from_state_dict(sd)
+
+    def bn(prefix):
+        return (sd[prefix + ".weight"], sd[prefix + ".bias"], sd[prefix + ".running_mean"], sd[prefix + ".running_var"])
+
+    arr = lambda t: np.ascontiguousarray(t.double().numpy().astype(dtype))  # noqa: E731
+    stem_w, stem_b = _fold_bn(sd["body.0.0.weight"], None, *bn("body.0.1"))
+    cw, cb = [], []
+    for i in range(cfg.n_residuals):
+        p = "body.1.%d." % i
+        for j in (1, 2):
+            w, b = _fold_bn(sd[p + "conv%d.weight" % j], None, *bn(p + "batch_norm%d" % j))
+            cw.append(w)
+            cb.append(b)
+    vw, vb = _fold_bn(sd["value_head.conv1.weight"], sd["value_head.conv1.bias"], *bn("value_head.batch_norm"))
+    pw, pb = _fold_bn(sd["policy_head.conv1.weight"], sd["policy_head.conv1.bias"], *bn("policy_head.batch_norm"))
+    W = torch.eye(42, dtype=torch.float64)
+    bias = torch.zeros(42, dtype=torch.float64)
+    for i in range(cfg.n_fc_layers):
+        Wi = sd["value_head.fcN.%d.weight" % i].double()
+        W, bias = Wi @ W, Wi @ bias + sd["value_head.fcN.%d.bias" % i].double()
+    return dict(
+        stem_w=arr(stem_w), stem_b=arr(stem_b),
+        conv_w=arr(torch.stack(cw)) if cw else np.zeros(1, dtype),
+        conv_b=arr(torch.stack(cb)) if cb else np.zeros(1, dtype),
+        head_w=arr(torch.cat([vw, pw], 0).reshape(3, cfg.filters)), head_b=arr(torch.cat([vb, pb], 0)),
+        vfc_w=arr(W), vfc_b=arr(bias), vout_w=arr(sd["value_head.fc1.weight"].reshape(42)),
+        pfc_w=arr(sd["policy_head.fc1.weight"]), pfc_b=arr(sd["policy_head.fc1.bias"]),
+        vout_b=float(sd["value_head.fc1.bias"].reshape(-1)[0]),
+        w1=float(sd["value_head.w1"]), w2=float(sd["value_head.w2"]))
+
+
 class FusedNet:
     from_bitboards = True
 
@@ -29,7 +68,6 @@ class FusedNet:
         """precision: "f32x3" = reference precision (the default at 32 filters): every fp32 operand split into fp16 hi +
         scaled lo parts, three MFMAs per k-step, fp32 accumulation; "f16" = fp16 storage / fp32 accumulation (one MFMA
         per k-step), opt-in: faster, answers within 2e-2 of the reference's instead of 5e-5."""
-        import torch
         sd = {k: v.detach().cpu() for k, v in state_dict.items()}
         cfg = PolicyValueNet.config_from_state_dict(sd)
         if precision is None:
@@ -40,40 +78,12 @@ class FusedNet:
         self.config = cfg
         self.device = device
 
-        def bn(prefix):
-            return (sd[prefix + ".weight"], sd[prefix + ".bias"], sd[prefix + ".running_mean"], sd[prefix + ".running_var"])
-
-        f32 = lambda t: np.ascontiguousarray(t.to(torch.float32).numpy())  # noqa: E731
-        stem_w, stem_b = _fold_bn(sd["body.0.0.weight"], None, *bn("body.0.1"))
-        cw, cb = [], []
-        for i in range(cfg.n_residuals):
-            p = "body.1.%d." % i
-            for j in (1, 2):
-                w, b = _fold_bn(sd[p + "conv%d.weight" % j], None, *bn(p + "batch_norm%d" % j))
-                cw.append(w)
-                cb.append(b)
-        vw, vb = _fold_bn(sd["value_head.conv1.weight"], sd["value_head.conv1.bias"], *bn("value_head.batch_norm"))
-        pw, pb = _fold_bn(sd["policy_head.conv1.weight"], sd["policy_head.conv1.bias"], *bn("policy_head.batch_norm"))
-        W = torch.eye(42, dtype=torch.float64)
-        bias = torch.zeros(42, dtype=torch.float64)
-        for i in range(cfg.n_fc_layers):
-            Wi = sd["value_head.fcN.%d.weight" % i].double()
-            W, bias = Wi @ W, Wi @ bias + sd["value_head.fcN.%d.bias" % i].double()
-        self._arrays = dict(
-            stem_w=f32(stem_w), stem_b=f32(stem_b),
-            conv_w=f32(torch.stack(cw)) if cw else np.zeros(1, np.float32),
-            conv_b=f32(torch.stack(cb)) if cb else np.zeros(1, np.float32),
-            head_w=f32(torch.cat([vw, pw], 0).reshape(3, cfg.filters)), head_b=f32(torch.cat([vb, pb], 0)),
-            vfc_w=f32(W), vfc_b=f32(bias), vout_w=f32(sd["value_head.fc1.weight"].reshape(42)),
-            pfc_w=f32(sd["policy_head.fc1.weight"]), pfc_b=f32(sd["policy_head.fc1.bias"]))
+        self._arrays = fold_for_fused(sd)
         d = L.NetDesc()
         d.channels, d.filters, d.n_residuals = cfg.channels, cfg.filters, cfg.n_residuals
         d.precision = self.PRECISIONS[precision]
         for k, a in self._arrays.items():
-            setattr(d, k, a.ctypes.data_as(C.POINTER(C.c_float)))
-        d.vout_b = float(sd["value_head.fc1.bias"].reshape(-1)[0])
-        d.w1 = float(sd["value_head.w1"])
-        d.w2 = float(sd["value_head.w2"])
+            setattr(d, k, a.ctypes.data_as(C.POINTER(C.c_float)) if isinstance(a, np.ndarray) else a)
         self._lib = L.load()
         self._h = C.c_void_p()
         rc = self._lib.c4_net_create(device, C.byref(d), C.byref(self._h))
@@ -121,8 +131,9 @@ def make_selfplay_net(state_dict, device: int = 0, precision: Optional[str] = No
     """The fastest evaluator this build has for a checkpoint at the requested precision: the fused MFMA forwards for 32
     filters (the reference's default, config.py:8-12; reference precision "f32x3" unless "f16" is asked for) and for
     64 filters (its example_config, data/example_config.py:8-16; fp16 storage only, so precision=None or "f16"), up to
-    16 / 7 residual blocks (their biases live in LDS) and any number of value-head Linear layers; anything else -- and
-    64 filters with precision="f32x3" -- runs through the PyTorch-ROCm plan (connect4_amd.net.InferenceNet, fp32).
+    16 / 7 residual blocks (their biases live in LDS) and any number of value-head Linear layers; anything else -- 64
+    filters with precision="f32x3", and a net with a folded conv weight beyond fp16's range (c4_net_create refuses it
+    with C4_EINVAL) -- runs through the PyTorch-ROCm plan (connect4_amd.net.InferenceNet, fp32).
     All plug into SelfPlay / generate_games / DeviceNetEvaluator unchanged."""
     import torch
     cfg = PolicyValueNet.config_from_state_dict(state_dict)
@@ -130,6 +141,10 @@ def make_selfplay_net(state_dict, device: int = 0, precision: Optional[str] = No
         precision = FusedNet.default_precision(cfg.filters)
     fits = (cfg.filters == 32 and cfg.n_residuals <= 16) or (cfg.filters == 64 and cfg.n_residuals <= 7 and precision == "f16")
     if cfg.channels == 3 and fits:
-        return FusedNet(state_dict, device=device, precision=precision)
+        try:
+            return FusedNet(state_dict, device=device, precision=precision)
+        except L.EngineError as e:
+            if e.code != L.EINVAL:
+                raise
     from .net import InferenceNet
     return InferenceNet(state_dict, device="cuda:%d" % device, dtype=torch.float32)
