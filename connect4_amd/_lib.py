@@ -19,6 +19,8 @@ EVAL_EXTERNAL_F32, EVAL_EXTERNAL_F64, EVAL_CENTRE = 0, 1, 2
 RNG_PHILOX, RNG_TAPE = 0, 1
 PLANES_F32, PLANES_F16, PLANES_BF16 = 0, 1, 2
 SLOT_ACTIVE, SLOT_PARKED, SLOT_MOVE_DONE = 0, 1, 2
+PRIOR_NONE, PRIOR_F32, PRIOR_F64 = 0, 1, 2
+PV_VALUE, PV_VISITS = 0, 1
 
 
 class EngineError(RuntimeError):
@@ -54,6 +56,23 @@ class RootResult(C.Structure):
                 ("child_status", C.c_int32 * 7), ("root_prior", C.c_double * 7),
                 ("values_policy", C.c_double * 7), ("color0", C.c_uint64), ("color1", C.c_uint64),
                 ("expansions", C.c_int64), ("simulations", C.c_int64)]
+
+
+class TreeNode(C.Structure):
+    """c4_tree_node: one row of an exported tree (TREE_NODE_DTYPE is the same layout for NumPy)."""
+    _fields_ = [("parent", C.c_int32), ("first_child", C.c_int32), ("visits", C.c_int32), ("move", C.c_int8),
+                ("depth", C.c_int8), ("n_children", C.c_int8), ("status", C.c_int8), ("value_sum", C.c_double),
+                ("color0", C.c_uint64), ("color1", C.c_uint64), ("prior", C.c_double * 7), ("prior_kind", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def tree_node_dtype():
+    import numpy as np
+    dt = np.dtype([("parent", "<i4"), ("first_child", "<i4"), ("visits", "<i4"), ("move", "i1"), ("depth", "i1"),
+                   ("n_children", "i1"), ("status", "i1"), ("value_sum", "<f8"), ("color0", "<u8"), ("color1", "<u8"),
+                   ("prior", "<f8", (7,)), ("prior_kind", "<i4"), ("reserved", "<i4")])
+    assert dt.itemsize == C.sizeof(TreeNode)
+    return dt
 
 
 class GameRecord(C.Structure):
@@ -95,6 +114,10 @@ SIGNATURES = {
     "c4_read_leaves": (C.c_int, [C.c_void_p, _u64p, _u64p, _i32p]),
     "c4_get_stats": (C.c_int, [C.c_void_p, _P(Stats)]),
     "c4_read_roots": (C.c_int, [C.c_void_p, _P(RootResult)]),
+    "c4_tree_sizes": (C.c_int, [C.c_void_p, _i32p, C.c_int32, C.c_int32, C.c_int32, _i64p]),
+    "c4_export_trees": (C.c_int, [C.c_void_p, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
+    "c4_export_trees_dev": (C.c_int, [C.c_void_p, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
+    "c4_principal_variations": (C.c_int, [C.c_void_p, _i32p, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _P(C.c_uint32), _f64p]),
     "c4_drain_games": (C.c_int, [C.c_void_p, _P(GameRecord), C.c_int32, _i32p]),
     "c4_finished_games": (C.c_int, [C.c_void_p, _i64p, _i64p]),
     "c4_export_games_dev": (C.c_int, [C.c_void_p, _P(ExportBuffers), C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -3273,3 +3273,308 @@ int c4_board_centre_value(int device, const uint64_t *c0, const uint64_t *c1, in
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// whole-tree export (the reference's Tree: tree.py:18-64, mcts.py:29-66) and principal variations
+// ------------------------------------------------------------------------------------------
+// Reads the node pools between launches; the search kernels above are not involved.  One wave64 walks
+// one tree breadth-first: each of its eight 8-lane groups takes one queued node per round, lane k of
+// a group reads child k's record (the two 16-byte loads per lane of the descent: a group touches
+// exactly the sibling block's two 128-byte lines), one ballot + prefix count over the wave places the
+// surviving children behind the queue's tail -- by parent, within a parent by ascending column, which is
+// the order of the reference's node.children (tree.py:125-129).  The queue holds {record index, depth};
+// boards are rebuilt from the parent's exported board and the child's info_bit, as the descent does.
+// A count pass sizes every table exactly; the write pass is the same walk with the stores switched on.
+//
+// Reference shape: the engine creates child records when a node's evaluation is applied, the reference
+// when the node is reached a second time (mcts.py:113-116) -- a non-terminal node has children iff
+// visits >= 2.  The records of a once-visited node still carry that node's normalised prior.
+namespace {
+
+constexpr uint32_t TREE_IDX_BITS = 24;   // queue entry: record index (< 2^22) | depth << 24
+
+// does slot g hold a tree that belongs to its root board?  (parked: none; a root waiting for its
+// evaluation: node 0 and the pool still hold the previous move's tree or nothing)
+__device__ __forceinline__ bool tree_readable(const Dev &d, int g)
+{
+    return d.state[g] != SLOT_PARKED && d.need_root[g] == 0 && d.pending[g] != 0 && d.n_alloc[g] >= 2;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(64) void k_tree_walk(Dev d, const int32_t *__restrict__ slots, int n, uint32_t min_visits, int max_depth,
+                                                  const int64_t *__restrict__ q_off, uint32_t *__restrict__ queue,
+                                                  int64_t *__restrict__ counts, const int64_t *__restrict__ out_off,
+                                                  c4_tree_node *__restrict__ out_all)
+{
+    const int t = blockIdx.x;
+    if (t >= n) return;
+    const int g = slots[t];
+    const int lane = threadIdx.x & (GROUP - 1), grp = threadIdx.x / GROUP;
+    const Pool pool{d.pool + (size_t)g * d.cap * (BLOCK_BYTES / 8)};
+    uint32_t *q = queue + q_off[t];
+    const uint32_t qcap = (uint32_t)(q_off[t + 1] - q_off[t]);   // records the slot has allocated: no table is longer
+    c4_tree_node *out = WRITE ? out_all + out_off[t] : nullptr;
+    const uint32_t ocap = WRITE ? (uint32_t)(out_off[t + 1] - out_off[t]) : 0;
+
+    uint32_t head = 0, tail = 0;   // wave-uniform
+    if (tree_readable(d, g) && qcap >= GROUP && pool.n(0) >= min_visits) {
+        tail = 1;
+        if (threadIdx.x == 0) {
+            q[0] = 0;
+            if (WRITE && ocap > 0) {
+                const Rec r = *pool.rec(0);
+                c4_tree_node &o = out[0];
+                o.parent = -1; o.visits = (int32_t)r.n; o.move = -1; o.depth = 0; o.status = -1;
+                o.value_sum = r.w; o.color0 = d.root_c0[g]; o.color1 = d.root_c1[g];
+            }
+        }
+        group_fence();
+    }
+    while (head < tail) {
+        const uint32_t row = head + (uint32_t)grp;
+        const bool pv = row < tail && (!WRITE || row < ocap);
+        const uint32_t ent = pv ? q[row] : 0;
+        const uint32_t pi = ent & ((1u << TREE_IDX_BITS) - 1), depth = ent >> TREE_IDX_BITS;
+        Rec pr = Rec{};
+        if (pv && pi < qcap) pr = *pool.rec(pi);
+        const uint32_t cb = info_base(pr.info);
+        const bool has_block = info_status(pr.info) == ST_EVALUATED && cb + GROUP <= qcap;   // evaluated: its child records exist
+        const uint32_t nc = has_block ? info_nchild(pr.info) : 0;
+        const bool isc = (uint32_t)lane < nc;
+        Rec cr = Rec{};
+        if (isc) cr = *pool.rec(cb + lane);
+        const bool keep = isc && pr.n >= 2 && cr.n >= min_visits && (max_depth < 0 || (int)depth + 1 <= max_depth);
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
+        const uint32_t crow = tail + (uint32_t)__popcll(bal & ((1ull << threadIdx.x) - 1));
+        const uint32_t gkept = (uint32_t)__popcll((bal >> (grp * GROUP)) & 0xffull);
+        const uint32_t gfirst = tail + (uint32_t)__popcll(bal & ((1ull << (grp * GROUP)) - 1));
+        if (keep && crow < qcap) q[crow] = (cb + (uint32_t)lane) | ((depth + 1) << TREE_IDX_BITS);
+        if (WRITE) {
+            uint64_t b0 = 0, b1 = 0;
+            if (pv) { b0 = out[row].color0; b1 = out[row].color1; }
+            if (keep && crow < ocap) {   // the child's own row: structure, counts, board
+                const uint64_t stone = 1ull << info_bit(cr.info);
+                uint64_t c0 = b0, c1 = b1;
+                if (popc64(b0 | b1) & 1) c1 ^= stone; else c0 ^= stone;
+                const uint32_t cst = info_status(cr.info);
+                c4_tree_node &o = out[crow];
+                o.parent = (int32_t)row; o.visits = (int32_t)cr.n; o.move = (int8_t)info_move(cr.info); o.depth = (int8_t)(depth + 1);
+                o.status = cst >= ST_XWIN ? (int8_t)(cst - ST_XWIN) : (int8_t)-1;
+                o.value_sum = cr.w; o.color0 = c0; o.color1 = c1;
+            }
+            // this node's position_value.prior, gathered from the p of its child records (zeros at illegal columns)
+            const int mask = legal_mask(b0 | b1);
+            const double pk = gshfl(cr.p, __popc(mask & ((1 << lane) - 1)) & (GROUP - 1));
+            if (pv) {
+                c4_tree_node &o = out[row];
+                if (lane < WIDTH) o.prior[lane] = (has_block && ((mask >> lane) & 1)) ? pk : 0.0;
+                if (lane == 0) {
+                    o.n_children = (int8_t)gkept;
+                    o.first_child = gkept ? (int32_t)gfirst : -1;
+                    o.prior_kind = has_block ? (info_pf64(pr.info) ? C4_PRIOR_F64 : C4_PRIOR_F32) : C4_PRIOR_NONE;
+                    o.reserved = 0;
+                }
+            }
+        }
+        head = head + SLOTS_PER_BLOCK < tail ? head + SLOTS_PER_BLOCK : tail;   // the rows this round took (at most eight of those queued)
+        tail += (uint32_t)__popcll(bal);
+        if (tail > qcap) tail = qcap;
+        group_fence();   // the queue entries and boards written above are read by other lanes of this wave next round
+    }
+    if (!WRITE && threadIdx.x == 0) counts[t] = (int64_t)tail;
+}
+
+// Principal variation of one slot per 8-lane group: from the root take the child the reference's Tree.best_move takes for the side to
+// move at that node (rule 0: largest data.value(side), tree.py:38-44,69-73) or Tree.most_visited (rule 1: largest visit count,
+// tree.py:84-91), ties to the higher column (tree.py:11-15), until a node without children in reference shape.
+__global__ __launch_bounds__(BLOCK) void k_tree_pv(Dev d, const int32_t *__restrict__ slots, int n, int rule, int max_len,
+                                                   int32_t *__restrict__ moves, int32_t *__restrict__ lengths,
+                                                   uint32_t *__restrict__ visits, double *__restrict__ values)
+{
+    const int lane = threadIdx.x & (GROUP - 1);
+    const int t = blockIdx.x * SLOTS_PER_BLOCK + threadIdx.x / GROUP;
+    if (t >= n) return;   // (whole groups leave together)
+    const int g = slots[t];
+    const Pool pool{d.pool + (size_t)g * d.cap * (BLOCK_BYTES / 8)};
+    const uint32_t limit = (d.n_alloc[g] < d.cap ? d.n_alloc[g] : d.cap) * GROUP;   // records the slot has allocated
+    int len = 0;
+    if (tree_readable(d, g)) {
+        uint32_t cur = 0;
+        int age = popc64(d.root_c0[g] | d.root_c1[g]);
+        while (len < max_len) {
+            const Rec pr = *pool.rec(cur);
+            const uint32_t cb = info_base(pr.info);
+            if (info_status(pr.info) != ST_EVALUATED || pr.n < 2 || info_nchild(pr.info) == 0 || cb + GROUP > limit) break;
+            const bool isc = (uint32_t)lane < info_nchild(pr.info);
+            Rec cr = Rec{};
+            if (isc) cr = *pool.rec(cb + lane);
+            const uint32_t cst = info_status(cr.info);
+            // tree.py:27-36 absolute_value: the exact result of a finished position, else value_sum / visit_count, else None
+            double absv = __longlong_as_double(0x7ff8000000000000LL);
+            if (cst >= ST_XWIN) absv = 0.5 * (double)(cst - ST_XWIN);
+            else if (cr.n > 0) absv = cr.w / (double)cr.n;
+            // tree.py:38-44 value(side): unknown = 0.0 ("assume lost"); utils.py:33-34 value_to_side
+            const double sv = (cst >= ST_XWIN || cr.n > 0) ? ((age & 1) ? 1.0 - absv : absv) : 0.0;
+            const double score = rule == C4_PV_VISITS ? (double)cr.n : sv;
+            const int kb = group_argmax(isc ? score : -1.0, isc ? lane : -1);
+            const uint32_t bi = gshfl(cr.info, kb), bn = gshfl(cr.n, kb);
+            const double bv = gshfl(absv, kb);
+            if (lane == 0) {
+                const size_t o = (size_t)t * max_len + len;
+                moves[o] = (int32_t)info_move(bi);
+                visits[o] = bn;
+                values[o] = bv;
+            }
+            cur = cb + (uint32_t)kb;
+            age += 1;
+            len += 1;
+        }
+    }
+    if (lane == 0) lengths[t] = len;
+}
+
+// slots[n] (NULL: 0..n-1) checked and copied: every index inside the engine, none twice
+int tree_slots(c4_engine *e, const char *who, const int32_t *slots, int32_t n, std::vector<int32_t> &out)
+{
+    if (n < 0 || n > e->d.G) { set_err(e->err, "%s: n = %d outside 0..%d slots", who, n, e->d.G); return C4_EINVAL; }
+    std::vector<char> seen((size_t)e->d.G, 0);
+    out.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int32_t s = slots ? slots[i] : i;
+        if (s < 0 || s >= e->d.G) { set_err(e->err, "%s: slots[%d] = %d outside 0..%d", who, i, s, e->d.G - 1); return C4_EINVAL; }
+        if (seen[(size_t)s]) { set_err(e->err, "%s: slot %d is named twice", who, s); return C4_EINVAL; }
+        seen[(size_t)s] = 1;
+        out[(size_t)i] = s;
+    }
+    return C4_OK;
+}
+
+#define TREE_HIP(e, r)                                                                                              \
+    do {                                                                                                            \
+        if ((r) != hipSuccess) { set_err((e)->err, "tree export: HIP failure: %s (line %d)", hipGetErrorString(r), __LINE__); return C4_EDEVICE; } \
+    } while (0)
+
+// count pass, and with `want_nodes` the write pass into nodes (host, or device when nodes_on_device) + offsets[n + 1]
+int tree_export(c4_engine *e, const char *who, const int32_t *slots, int32_t n, int32_t min_visits, int32_t max_depth,
+                int64_t *counts, bool want_nodes, c4_tree_node *nodes, bool nodes_on_device, int64_t capacity, int64_t *offsets)
+{
+    if (min_visits < 0) { set_err(e->err, "%s: min_visits < 0", who); return C4_EINVAL; }
+    std::vector<int32_t> sl;
+    int rc = tree_slots(e, who, slots, n, sl);
+    if (rc) return rc;
+    if (want_nodes) offsets[0] = 0;
+    if (n == 0) return C4_OK;
+    hipError_t r = hipSetDevice(e->device);
+    TREE_HIP(e, r);
+    r = hipDeviceSynchronize();
+    TREE_HIP(e, r);
+    std::vector<uint32_t> nalloc((size_t)e->d.G);
+    r = hipMemcpy(nalloc.data(), e->d.n_alloc, nalloc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    TREE_HIP(e, r);
+    std::vector<int64_t> qoff((size_t)n + 1, 0), cnt((size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+        const uint32_t blocks = std::min(nalloc[(size_t)sl[(size_t)i]], e->d.cap);   // (a pool never holds more than its capacity)
+        qoff[(size_t)i + 1] = qoff[(size_t)i] + (int64_t)blocks * GROUP;
+    }
+    Scratch sc;
+    int32_t *sl_dev = sc.up(sl.data(), (size_t)n, r);
+    int64_t *qoff_dev = sc.up(qoff.data(), (size_t)n + 1, r);
+    uint32_t *queue_dev = sc.up((const uint32_t *)nullptr, (size_t)qoff[(size_t)n], r);
+    int64_t *cnt_dev = sc.up((const int64_t *)nullptr, (size_t)n, r);
+    TREE_HIP(e, r);
+    hipLaunchKernelGGL((k_tree_walk<false>), dim3(n), dim3(64), 0, e->stream, e->d, sl_dev, n, (uint32_t)min_visits, (int)max_depth,
+                       qoff_dev, queue_dev, cnt_dev, (const int64_t *)nullptr, (c4_tree_node *)nullptr);
+    r = hipGetLastError();
+    if (r == hipSuccess) r = hipDeviceSynchronize();
+    if (r == hipSuccess) r = hipMemcpy(cnt.data(), cnt_dev, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost);
+    TREE_HIP(e, r);
+    if (counts) std::copy(cnt.begin(), cnt.end(), counts);
+    if (!want_nodes) return C4_OK;
+    std::vector<int64_t> ooff((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) ooff[(size_t)i + 1] = ooff[(size_t)i] + cnt[(size_t)i];
+    const int64_t total = ooff[(size_t)n];
+    if (total > capacity) {
+        set_err(e->err, "%s: the %d trees hold %lld nodes, the buffer %lld (c4_tree_sizes tells)", who, n, (long long)total, (long long)capacity);
+        return C4_EINVAL;
+    }
+    std::copy(ooff.begin(), ooff.end(), offsets);
+    if (total == 0) return C4_OK;
+    int64_t *ooff_dev = sc.up(ooff.data(), (size_t)n + 1, r);
+    c4_tree_node *out_dev = nodes_on_device ? nodes : sc.up((const c4_tree_node *)nullptr, (size_t)total, r);
+    TREE_HIP(e, r);
+    hipLaunchKernelGGL((k_tree_walk<true>), dim3(n), dim3(64), 0, e->stream, e->d, sl_dev, n, (uint32_t)min_visits, (int)max_depth,
+                       qoff_dev, queue_dev, cnt_dev, ooff_dev, out_dev);
+    r = hipGetLastError();
+    if (r == hipSuccess) r = hipDeviceSynchronize();
+    if (r == hipSuccess && !nodes_on_device) r = hipMemcpy(nodes, out_dev, (size_t)total * sizeof(c4_tree_node), hipMemcpyDeviceToHost);
+    TREE_HIP(e, r);
+    return C4_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int c4_tree_sizes(c4_engine *e, const int32_t *slots, int32_t n, int32_t min_visits, int32_t max_depth, int64_t *n_nodes)
+{
+    if (!e) { set_err(g_err, "c4_tree_sizes: null engine"); return C4_EINVAL; }
+    if (!n_nodes) { set_err(e->err, "c4_tree_sizes: null n_nodes"); return C4_EINVAL; }
+    return tree_export(e, "c4_tree_sizes", slots, n, min_visits, max_depth, n_nodes, false, nullptr, false, 0, nullptr);
+}
+
+int c4_export_trees(c4_engine *e, const int32_t *slots, int32_t n, int32_t min_visits, int32_t max_depth, c4_tree_node *nodes,
+                    int64_t capacity, int64_t *offsets)
+{
+    if (!e) { set_err(g_err, "c4_export_trees: null engine"); return C4_EINVAL; }
+    if (!offsets || capacity < 0 || (!nodes && capacity > 0)) { set_err(e->err, "c4_export_trees: null buffer or negative capacity"); return C4_EINVAL; }
+    return tree_export(e, "c4_export_trees", slots, n, min_visits, max_depth, nullptr, true, nodes, false, capacity, offsets);
+}
+
+int c4_export_trees_dev(c4_engine *e, const int32_t *slots, int32_t n, int32_t min_visits, int32_t max_depth, c4_tree_node *nodes_dev,
+                        int64_t capacity, int64_t *offsets)
+{
+    if (!e) { set_err(g_err, "c4_export_trees_dev: null engine"); return C4_EINVAL; }
+    if (!offsets || capacity < 0 || (!nodes_dev && capacity > 0)) { set_err(e->err, "c4_export_trees_dev: null buffer or negative capacity"); return C4_EINVAL; }
+    return tree_export(e, "c4_export_trees_dev", slots, n, min_visits, max_depth, nullptr, true, nodes_dev, true, capacity, offsets);
+}
+
+int c4_principal_variations(c4_engine *e, const int32_t *slots, int32_t n, int32_t rule, int32_t max_len, int32_t *moves,
+                            int32_t *lengths, uint32_t *visits, double *values)
+{
+    if (!e) { set_err(g_err, "c4_principal_variations: null engine"); return C4_EINVAL; }
+    if (!moves || !lengths || !visits || !values) { set_err(e->err, "c4_principal_variations: null output"); return C4_EINVAL; }
+    if (rule != C4_PV_VALUE && rule != C4_PV_VISITS) { set_err(e->err, "c4_principal_variations: rule %d is neither C4_PV_VALUE nor C4_PV_VISITS", rule); return C4_EINVAL; }
+    if (max_len < 1 || max_len > 64) { set_err(e->err, "c4_principal_variations: max_len %d outside 1..64", max_len); return C4_EINVAL; }
+    std::vector<int32_t> sl;
+    int rc = tree_slots(e, "c4_principal_variations", slots, n, sl);
+    if (rc) return rc;
+    if (n == 0) return C4_OK;
+    hipError_t r = hipSetDevice(e->device);
+    TREE_HIP(e, r);
+    r = hipDeviceSynchronize();
+    TREE_HIP(e, r);
+    const size_t cells = (size_t)n * (size_t)max_len;
+    Scratch sc;
+    int32_t *sl_dev = sc.up(sl.data(), (size_t)n, r);
+    int32_t *mv_dev = sc.up((const int32_t *)nullptr, cells, r);
+    int32_t *len_dev = sc.up((const int32_t *)nullptr, (size_t)n, r);
+    uint32_t *vis_dev = sc.up((const uint32_t *)nullptr, cells, r);
+    double *val_dev = sc.up((const double *)nullptr, cells, r);
+    TREE_HIP(e, r);
+    r = hipMemset(mv_dev, 0xff, cells * sizeof(int32_t));                 // beyond a line's length: move -1,
+    if (r == hipSuccess) r = hipMemset(vis_dev, 0, cells * sizeof(uint32_t));   // 0 visits,
+    if (r == hipSuccess) r = hipMemset(val_dev, 0, cells * sizeof(double));     // value 0.0
+    TREE_HIP(e, r);
+    hipLaunchKernelGGL(k_tree_pv, dim3((n + SLOTS_PER_BLOCK - 1) / SLOTS_PER_BLOCK), dim3(BLOCK), 0, e->stream, e->d, sl_dev, n, (int)rule,
+                       (int)max_len, mv_dev, len_dev, vis_dev, val_dev);
+    r = hipGetLastError();
+    if (r == hipSuccess) r = hipDeviceSynchronize();
+    if (r == hipSuccess) r = hipMemcpy(moves, mv_dev, cells * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (r == hipSuccess) r = hipMemcpy(lengths, len_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (r == hipSuccess) r = hipMemcpy(visits, vis_dev, cells * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (r == hipSuccess) r = hipMemcpy(values, val_dev, cells * sizeof(double), hipMemcpyDeviceToHost);
+    TREE_HIP(e, r);
+    return C4_OK;
+}
+
+}  // extern "C"

@@ -141,6 +141,56 @@ class Engine:
         self._check(self._lib.c4_read_roots(self._h, out))
         return out
 
+    # -- whole trees -------------------------------------------------------------------------
+    def _slots(self, slots):
+        if slots is None:
+            return None, self.n_slots
+        a = np.ascontiguousarray(slots, dtype=np.int32)
+        return a, len(a)
+
+    def tree_sizes(self, slots=None, min_visits=0, max_depth=None):
+        """Rows of each slot's tree table under the two filters (int64 [n])."""
+        a, n = self._slots(slots)
+        out = np.zeros(n, dtype=np.int64)
+        self._check(self._lib.c4_tree_sizes(self._h, None if a is None else _ptr(a, C.c_int32), n, int(min_visits),
+                                            -1 if max_depth is None else int(max_depth), _ptr(out, C.c_int64)))
+        return out
+
+    def export_trees(self, slots=None, min_visits=0, max_depth=None, capacity=None):
+        """The whole search trees of `slots` (default: every slot), walked and filtered on the device: one TreeTable
+        (connect4_amd.tree) per slot, all of them views into ONE structured NumPy buffer of c4_tree_node rows.
+        min_visits drops nodes with fewer visits (0 keeps the unvisited children), max_depth nodes further below the
+        root; a dropped node drops its subtree.  A slot without a tree gives an empty table.  `capacity` (rows of
+        the buffer) defaults to what c4_tree_sizes reports."""
+        from .tree import TreeTable
+        a, n = self._slots(slots)
+        if capacity is None:
+            capacity = int(self.tree_sizes(slots, min_visits, max_depth).sum())
+        nodes = np.zeros(int(capacity), dtype=L.tree_node_dtype())
+        off = np.zeros(n + 1, dtype=np.int64)
+        self._check(self._lib.c4_export_trees(self._h, None if a is None else _ptr(a, C.c_int32), n, int(min_visits),
+                                              -1 if max_depth is None else int(max_depth), C.c_void_p(nodes.ctypes.data),
+                                              int(capacity), _ptr(off, C.c_int64)))
+        ids = range(n) if a is None else a.tolist()
+        return [TreeTable(nodes[off[i]:off[i + 1]], int(g)) for i, g in enumerate(ids)]
+
+    def principal_variations(self, slots=None, rule="value", max_len=42):
+        """The line each slot's search expects, walked on the device: per slot (moves int32[k], visits uint32[k],
+        values float64[k]; NaN where the reference's absolute_value is None).  rule "value": Tree.best_move for the
+        side to move at every node; "visits": Tree.most_visited."""
+        if rule not in ("value", "visits"):
+            raise ValueError("rule is 'value' or 'visits'")
+        a, n = self._slots(slots)
+        max_len = int(max_len)
+        moves = np.zeros((n, max(max_len, 1)), dtype=np.int32)
+        visits = np.zeros((n, max(max_len, 1)), dtype=np.uint32)
+        values = np.zeros((n, max(max_len, 1)), dtype=np.float64)
+        lens = np.zeros(n, dtype=np.int32)
+        self._check(self._lib.c4_principal_variations(
+            self._h, None if a is None else _ptr(a, C.c_int32), n, L.PV_VALUE if rule == "value" else L.PV_VISITS, max_len,
+            _ptr(moves, C.c_int32), _ptr(lens, C.c_int32), _ptr(visits, C.c_uint32), _ptr(values, C.c_double)))
+        return [(moves[i, :lens[i]], visits[i, :lens[i]], values[i, :lens[i]]) for i in range(n)]
+
     @property
     def record_capacity(self):
         return int(self.cfg.record_capacity_games or 2 * self.n_slots)

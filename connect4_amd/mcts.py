@@ -74,7 +74,9 @@ class _Searcher:
                 u[i, 0] = np.random.random_sample()
         return nz, u
 
-    def run(self, boards: Sequence[Board], pick=True):
+    def run(self, boards: Sequence[Board], pick=True, full_tree=False):
+        """One search per board.  Returns the root read-outs, and with full_tree the whole trees as well (one
+        export call for the batch, before the engine is reset for the next one)."""
         for b in boards:
             if b.result is not None:
                 raise ValueError("cannot search a finished position")
@@ -99,7 +101,10 @@ class _Searcher:
             eng.set_tapes(*self._tapes(boards, pick))
             eng.reset(c0, c1)
             self._drive_host(eng, np.float32 if f32 else np.float64)
-        return list(eng.read_roots()[:n])
+        roots = list(eng.read_roots()[:n])
+        if full_tree:
+            return roots, eng.export_trees(np.arange(n, dtype=np.int32))
+        return roots
 
     def _drive_device(self, eng):
         import torch
@@ -152,11 +157,12 @@ class _Searcher:
 
 
 class MCTS(BasePlayer):
-    def __init__(self, name: str, config: MCTSConfig, evaluator, device: int = 0):
+    def __init__(self, name: str, config: MCTSConfig, evaluator, device: int = 0, full_tree: bool = False):
         super().__init__(name)
         self.config = config
         self.evaluator = evaluator
         self.device = device
+        self.full_tree = full_tree      # True: make_move's tree is the whole search tree, exported from the device
         self._searcher = None
 
     def _s(self):
@@ -166,10 +172,13 @@ class MCTS(BasePlayer):
 
     def make_moves(self, boards: List[Board]):
         """Batch form: one search per board, all on the GPU at once."""
-        roots = self._s().run(boards)
+        if self.full_tree:
+            roots, tables = self._s().run(boards, full_tree=True)
+        else:
+            roots, tables = self._s().run(boards), None
         out = []
-        for b, r in zip(boards, roots):
-            tree = Tree(r, b)
+        for i, (b, r) in enumerate(zip(boards, roots)):
+            tree = Tree(r, b) if tables is None else Tree(tables[i], b, r)
             value = None if np.isnan(r.value) else float(r.value)
             b.make_move(int(r.move))
             out.append((int(r.move), value, tree))
@@ -179,7 +188,7 @@ class MCTS(BasePlayer):
         return self.make_moves([board])[0]
 
     def __copy__(self):                 # match.py:26-40 copies players per game
-        return MCTS(self.name, self.config, self.evaluator, self.device)
+        return MCTS(self.name, self.config, self.evaluator, self.device, self.full_tree)
 
     def __getstate__(self):             # picklable for Pool.map (match.py:72-76)
         d = dict(self.__dict__)
@@ -190,10 +199,14 @@ class MCTS(BasePlayer):
         return super().__str__() + ", type: Computer"
 
 
-def search(config: MCTSConfig, board: Board, evaluator, device: int = 0) -> Tree:
-    """mcts.py:94-121: run the simulations and return the tree (the board is not modified)."""
+def search(config: MCTSConfig, board: Board, evaluator, device: int = 0, full_tree: bool = False) -> Tree:
+    """mcts.py:94-121: run the simulations and return the tree (the board is not modified).  full_tree: the whole
+    tree, exported from the device; default: the root and its children."""
     s = _Searcher(config, evaluator, device)
     try:
+        if full_tree:
+            roots, tables = s.run([board], pick=False, full_tree=True)
+            return Tree(tables[0], board, roots[0])
         return Tree(s.run([board], pick=False)[0], board)
     finally:
         s.close()

@@ -221,6 +221,63 @@ int c4_drain_games(c4_engine *e, c4_game_record *out, int32_t cap, int32_t *n_ou
 /* Finished games waiting in the ring / finished games lost to a full ring.  Synchronous. */
 int c4_finished_games(c4_engine *e, int64_t *n_ready, int64_t *n_dropped);
 
+/* -- whole search trees --------------------------------------------------------------------- */
+/* One node of an exported tree: what the reference keeps per anytree Node (tree.py:18-64 NodeData, mcts.py:29-66).
+ * A tree is a table of these in breadth-first order -- within a level by parent, within a parent by ascending
+ * column -- so row 0 is the root, a node's children are the rows first_child .. first_child + n_children - 1 and stand
+ * in the order of the reference's node.children (tree.py:125-129).
+ * Shape: the reference creates a node's children when the node is reached a second time (mcts.py:113-116), the engine
+ * when the node's evaluation is applied; the export follows the reference: a non-terminal node has children iff
+ * visits >= 2.  A once-visited node has none, but its prior is known (it comes from its child records). */
+#define C4_PRIOR_NONE 0 /* position_value is None: never evaluated, or the position is finished (mcts.py:125-128) */
+#define C4_PRIOR_F32 1  /* prior[] holds float32 values widened exactly (a net's answer, normalised in float32) */
+#define C4_PRIOR_F64 2  /* prior[] is float64 (table / heuristic evaluator, or the root after the noise, mcts.py:180) */
+typedef struct {
+    int32_t  parent;        /* row of node.parent, -1 for the root */
+    int32_t  first_child;   /* row of the first exported child, -1 when n_children == 0 */
+    int32_t  visits;        /* search_value.visit_count; 0 with value_sum 0.0: search_value is None */
+    int8_t   move;          /* node.name: the column played into this node, -1 for the root */
+    int8_t   depth;         /* plies below the root */
+    int8_t   n_children;    /* exported children (after the filters) */
+    int8_t   status;        /* node.data.board.result: -1 undecided, else C4_RESULT_* */
+    double   value_sum;     /* search_value.value_sum (absolute: o's point of view, as the reference keeps it) */
+    uint64_t color0, color1;   /* node.data.board, rebuilt on the device from the parent's board and the move */
+    double   prior[7];      /* position_value.prior of THIS node by column: normalised over the legal columns, zeros
+                               elsewhere; the root's after the Dirichlet noise; all zero when prior_kind is C4_PRIOR_NONE */
+    int32_t  prior_kind;    /* C4_PRIOR_* */
+    int32_t  reserved;
+} c4_tree_node;
+
+/* When a tree may be read: between launches, in any slot state, for engines driven by c4_step / c4_step_range /
+ * c4_run_centre AND by c4_selfplay_steps (the fused kernels keep node 0 and the pool current -- the backups write the
+ * root record like any other -- and write the slot state back when a launch ends).  A slot that is still searching
+ * gives a consistent snapshot: a leaf waiting for its evaluation has not been backed up, so the counts add up.  A
+ * slot without a tree of its root position -- parked, or its root still waits for the evaluator -- exports 0 nodes.
+ * Filters, applied on the device: nodes with fewer than min_visits visits are dropped (0 keeps the unvisited
+ * children), and nodes deeper than max_depth (< 0: no limit); a dropped node drops its subtree, and n_children /
+ * first_child refer to what was exported.  slots[n]: distinct slot indices, NULL = slots 0..n-1.
+ * A bad or repeated slot, a null buffer or too little capacity: C4_EINVAL, nothing is written beyond `capacity` and
+ * the engine stays usable.  All three calls are synchronous. */
+/* n_nodes[i] = rows of the table of slots[i] under the two filters */
+int c4_tree_sizes(c4_engine *e, const int32_t *slots, int32_t n, int32_t min_visits, int32_t max_depth, int64_t *n_nodes);
+/* nodes[capacity] (host) receives the tables back to back, offsets[n + 1] where each starts (offsets[n] = rows in all) */
+int c4_export_trees(c4_engine *e, const int32_t *slots, int32_t n, int32_t min_visits, int32_t max_depth, c4_tree_node *nodes,
+                    int64_t capacity, int64_t *offsets);
+/* the same into a DEVICE buffer (offsets stays a host array) */
+int c4_export_trees_dev(c4_engine *e, const int32_t *slots, int32_t n, int32_t min_visits, int32_t max_depth, c4_tree_node *nodes_dev,
+                        int64_t capacity, int64_t *offsets);
+
+/* Principal variations, walked on the device: from the root repeatedly the child that Tree.best_move takes for the
+ * side to move AT THAT NODE (C4_PV_VALUE: largest data.value(side) -- unvisited 0.0, a finished position its exact
+ * result; tree.py:38-44,69-73) or that Tree.most_visited takes (C4_PV_VISITS, tree.py:84-91), ties to the higher
+ * column (tree.py:11-15), until a node without children in reference shape or max_len (1..64) moves.
+ * moves / visits / values [n][max_len]: column, visit count and absolute_value (tree.py:27-36; NaN for None) of each
+ * node on the line; beyond lengths[i]: -1, 0, 0.0. */
+#define C4_PV_VALUE 0
+#define C4_PV_VISITS 1
+int c4_principal_variations(c4_engine *e, const int32_t *slots, int32_t n, int32_t rule, int32_t max_len, int32_t *moves,
+                            int32_t *lengths, uint32_t *visits, double *values);
+
 /* Device-side export: pack up to max_games finished games (oldest first, whole games only, at most
  * cap_positions positions) into caller-owned DEVICE buffers and consume them -- no host round trip, so
  * it can be queued behind c4_selfplay_steps on the same stream.  Layout = the compact record of
