@@ -87,6 +87,14 @@ class ExportBuffers(C.Structure):
                                           "game_index_dev", "lengths_dev", "results_dev", "ids_dev")]
 
 
+WINDOW_MAX_SEGMENTS = 64
+
+
+class WindowSegment(C.Structure):
+    """c4_window_segment: one generation of a device-resident training window (device pointers)."""
+    _fields_ = [("boards", C.c_void_p), ("targets", C.c_void_p), ("policy", C.c_void_p), ("n_positions", C.c_int64)]
+
+
 class NetDesc(C.Structure):
     _fields_ = [("channels", C.c_int32), ("filters", C.c_int32), ("n_residuals", C.c_int32), ("precision", C.c_int32)] + \
         [(n, C.POINTER(C.c_float)) for n in ("stem_w", "stem_b", "conv_w", "conv_b", "head_w", "head_b",
@@ -123,6 +131,10 @@ SIGNATURES = {
     "c4_export_games_dev": (C.c_int, [C.c_void_p, _P(ExportBuffers), C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "c4_training_tensors_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "c4_window_gather_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "c4_planes_to_boards_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "c4_window_last_error": (C.c_char_p, []),
     "c4_eval_cache_lookup": (C.c_int, [C.c_void_p, _u64p, _u64p, C.c_int32, _f32p, _f32p, _i32p]),
     "c4_debug_root_noise": (C.c_int, [C.c_int, C.c_uint64, C.c_double, _i64p, _i32p, _i32p, C.c_int32, _f64p, _f64p]),
     "c4_debug_sample_move": (C.c_int, [C.c_int, C.c_uint64, _i64p, _i32p, _f64p, _i32p, _f64p, C.c_int32, _f64p, _i32p]),

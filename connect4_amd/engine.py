@@ -328,6 +328,55 @@ def training_tensors(boards, targets, policy, add_fliplr=True, stream=0):
     return ob, ov, op
 
 
+def _check_window(rc):
+    if rc != L.OK:
+        msg = L.load().c4_window_last_error()
+        raise L.EngineError(rc, msg.decode("utf-8", "replace") if msg else "")
+
+
+def _need_gpu(dev, what):
+    if dev.type != "cuda":
+        raise RuntimeError("%s runs on the GPU; move the tensors to a cuda device first -- there is no CPU fallback" % what)
+
+
+def window_gather(segments_ptr, n_segments, index, boards_out, values_out, priors_out, counter=None, stream=0):
+    """c4_window_gather_dev: rows `index` (int64 device tensor) of the window whose segment table (c4_window_segment
+    [n_segments], device memory) is at `segments_ptr`, into the three float32 device tensors.  `counter`: device int32
+    tensor that receives the number of indices outside the window (their rows are zeros), or None.  One launch on
+    `stream` (default: torch's current stream); nothing is allocated and nothing waited for."""
+    import torch
+    dev = index.device
+    _need_gpu(dev, "window_gather (c4_window_gather_dev)")
+    m = int(index.numel())
+    assert index.dtype == torch.int64 and index.is_contiguous()
+    for t, shape in ((boards_out, (m, 3, 6, 7)), (values_out, (m,)), (priors_out, (m, 7))):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev, (tuple(t.shape), shape)
+    if not stream:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    _check_window(L.load().c4_window_gather_dev(dev.index or 0, C.c_void_p(stream), C.c_void_p(segments_ptr), int(n_segments),
+                                                C.c_void_p(index.data_ptr()), m, C.c_void_p(boards_out.data_ptr()),
+                                                C.c_void_p(values_out.data_ptr()), C.c_void_p(priors_out.data_ptr()),
+                                                C.c_void_p(counter.data_ptr()) if counter is not None else None))
+
+
+def planes_to_boards(planes, stream=0):
+    """c4_planes_to_boards_dev, the inverse of board_planes on device tensors: F32[n,3,6,7] -> (int64 [n,2] bitboards,
+    int32 [1] number of rows that no board encodes), both on the planes' device; no host synchronisation."""
+    import torch
+    assert planes.dtype == torch.float32 and tuple(planes.shape[1:]) == (3, 6, 7)
+    planes = planes.contiguous()
+    dev = planes.device
+    _need_gpu(dev, "planes_to_boards (c4_planes_to_boards_dev)")
+    n = int(planes.shape[0])
+    boards = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if not stream:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    _check_window(L.load().c4_planes_to_boards_dev(dev.index or 0, C.c_void_p(stream), C.c_void_p(planes.data_ptr()), n,
+                                                   C.c_void_p(boards.data_ptr()), C.c_void_p(n_bad.data_ptr())))
+    return boards, n_bad
+
+
 def debug_root_noise(seed, alpha, game_id, ply, legal_mask, device=0):
     gid = np.ascontiguousarray(game_id, dtype=np.int64)
     pl = np.ascontiguousarray(ply, dtype=np.int32)

@@ -34,29 +34,17 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
     net.pth, and then every rank receives rank 0's net / optimiser / scheduler state (broadcast), so the next
     generation's shards are all played by the same net.  `precision`: see make_selfplay_net (None = the reference's)."""
     import torch
-    import torch.distributed as dist
-    multi = dist.is_initialized() and dist.get_world_size() > 1
-    rank = dist.get_rank() if dist.is_initialized() else 0
+    multi, rank = _ranks()
     earlier = existing_window(save_dir, gen) if (save_dir is not None and rank == 0) else []
     t0 = time.perf_counter()
-    net = make_selfplay_net(trainer.net.state_dict(), device=device, precision=precision)   # weights are fixed within a generation
-    try:
-        games = generate_games_sharded_packed(config, net, n_games, seed=seed + 1000 * gen, device=device, n_slots=n_slots)
-    finally:
-        if hasattr(net, "close"):
-            net.close()
-    torch.cuda.synchronize(device)
+    games = _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision)
     t1 = time.perf_counter()
     loss, rows = None, 0
     t2 = t1
     if rank == 0:
         boards, values, priors = games.training_tensors(add_fliplr=True)       # on the device
         if save_dir is not None:
-            folder = os.path.join(save_dir, str(gen))                 # save_dir/<gen>/{data.pth, net.pth} (storage.py:15-16)
-            os.makedirs(folder, exist_ok=True)
-            if write_games_pkl:
-                GameStorage().save(games, folder)
-            torch.save({"boards": boards.cpu(), "values": values.cpu(), "priors": priors.cpu()}, os.path.join(folder, "data.pth"))
+            _write_generation(games, (boards, values, priors), save_dir, gen, write_games_pkl)
             if earlier:   # data.py:66-75: this generation first, then the earlier ones, newest first
                 parts = [torch.load(os.path.join(save_dir, str(g), "data.pth"), weights_only=True) for g in earlier]
                 boards = torch.cat([boards] + [p["boards"].to(boards.device) for p in parts])
@@ -66,10 +54,7 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
         t2 = time.perf_counter()
         rows = int(boards.shape[0])
         loss = trainer.train(boards, values, priors)
-        if save_dir is not None:
-            trainer.save(os.path.join(save_dir, str(gen)))
-        if trainer.device.type == "cuda":
-            torch.cuda.synchronize(trainer.device)
+        _checkpoint(trainer, save_dir, gen)
     if multi:
         loss = trainer.broadcast_state(src=0, extra=loss)
     t3 = time.perf_counter()
@@ -77,3 +62,126 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
         timings.update(selfplay_and_gather_s=t1 - t0, tensors_and_write_s=t2 - t1, train_s=t3 - t2,
                        positions=int(games.n_positions), training_rows=rows)
     return games, loss
+
+
+# -- the steps run_generation and run_generations share ---------------------------------------------------------------
+def _ranks():
+    import torch.distributed as dist
+    multi = dist.is_initialized() and dist.get_world_size() > 1
+    return multi, (dist.get_rank() if dist.is_initialized() else 0)
+
+
+def _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision):
+    """Every rank plays its shard with the trainer's current weights; all ranks receive all games (finished on return)."""
+    import torch
+    net = make_selfplay_net(trainer.net.state_dict(), device=device, precision=precision)   # weights are fixed within a generation
+    try:
+        games = generate_games_sharded_packed(config, net, n_games, seed=seed + 1000 * gen, device=device, n_slots=n_slots)
+    finally:
+        if hasattr(net, "close"):
+            net.close()
+    torch.cuda.synchronize(device)
+    return games
+
+
+def _write_generation(games, tensors, save_dir, gen, write_games_pkl):
+    """save_dir/<gen>/{data.pth, games.pkl} (storage.py:15-16, data.py:47-64) from the device tensors of this generation."""
+    import torch
+    boards, values, priors = tensors
+    folder = os.path.join(save_dir, str(gen))
+    os.makedirs(folder, exist_ok=True)
+    if write_games_pkl:
+        GameStorage().save(games, folder)
+    torch.save({"boards": boards.cpu(), "values": values.cpu(), "priors": priors.cpu()}, os.path.join(folder, "data.pth"))
+
+
+def _checkpoint(trainer, save_dir, gen):
+    import torch
+    if save_dir is not None:
+        trainer.save(os.path.join(save_dir, str(gen)))
+    if trainer.device.type == "cuda":
+        torch.cuda.synchronize(trainer.device)
+
+
+# -- many generations: the window stays on the device -----------------------------------------------------------------
+def latest_generation(save_dir: str):
+    """(next generation, path of the net.pth to resume from or None): the resume rule of TrainingLoop.__init__
+    (oinkoink/neural/training.py:31-47) over the integer-named subdirectories of save_dir.  With MORE THAN ONE of them, the
+    largest g is the last generation; when g/net.pth is missing (the run died between data.pth and the checkpoint) g - 1
+    is, and when that has no net.pth either FileNotFoundError is raised; the next generation is the one after it.
+    Otherwise -- no subdirectory, or exactly one: the reference applies its rule only to more than one and so starts a
+    directory that holds a single generation over, which is reproduced here -- (1, None).  Subdirectories whose names
+    are not integers are ignored (the reference raises on them)."""
+    gens = []
+    if os.path.isdir(save_dir):
+        for f in os.scandir(save_dir):
+            if f.is_dir():
+                try:
+                    gens.append(int(f.name))
+                except ValueError:
+                    pass
+    if len(gens) <= 1:
+        return 1, None
+    g = max(gens)
+    path = os.path.join(save_dir, str(g), "net.pth")
+    if not os.path.exists(path):
+        g -= 1
+        path = os.path.join(save_dir, str(g), "net.pth")
+        if not os.path.exists(path):
+            raise FileNotFoundError("no net.pth in generation %d or %d of %s" % (g + 1, g, save_dir))
+    return g + 1, path
+
+
+def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir: str, n_generations: int,
+                    first_gen: Optional[int] = None, seed: int = 0, device: int = 0, n_slots: Optional[int] = None,
+                    precision: Optional[str] = None, write_games_pkl: bool = False, timings: Optional[list] = None):
+    """n_generations generations of run_generation -- same seeds (seed + 1000 * gen), same files (data.pth, net.pth,
+    optional games.pkl), same broadcast of the trained state -- with the sliding window (data.py:66-75) kept on rank 0's GPU
+    as packed positions (replay.ReplayWindow): each generation's games are appended to it and trained with
+    Trainer.train_window; no earlier data.pth is read back and no materialised window is concatenated (48 B instead
+    of 1,072 B per position, nothing reloaded).  The batches are those of run_generation: row r of the window is row r of
+    the concatenated files.
+
+    first_gen=None resumes save_dir by the reference's rule (latest_generation): the trainer loads that net.pth and the
+    window is rebuilt from the data.pth files (ReplayWindow.from_directory; each file is verified).  An explicit
+    first_gen starts there with the trainer as it is and, like run_generation, with what earlier generations save_dir
+    holds.  `timings`: a list that receives one dict per generation -- run_generation's keys, plus window_rows and
+    window_bytes.  Returns (the window -- None on other ranks --, [last loss of each generation])."""
+    import torch
+    from .replay import ReplayWindow
+    multi, rank = _ranks()
+    os.makedirs(save_dir, exist_ok=True)
+    if first_gen is None:
+        first_gen, net_path = latest_generation(save_dir)
+        if net_path is not None:
+            if rank == 0:
+                trainer.load_state(torch.load(net_path, map_location=trainer.device, weights_only=True))
+            if multi:
+                trainer.broadcast_state(src=0)
+    window = None
+    if rank == 0:       # window_generations(first_gen - 1) covers the earlier generations of first_gen's window
+        window = ReplayWindow.from_directory(save_dir, first_gen - 1, trainer.device) if first_gen > 1 else ReplayWindow(trainer.device)
+    losses = []
+    for gen in range(first_gen, first_gen + n_generations):
+        t0 = time.perf_counter()
+        games = _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision)
+        t1 = time.perf_counter()
+        loss, rows, nbytes = None, 0, 0
+        t2 = t1
+        if rank == 0:
+            _write_generation(games, games.training_tensors(add_fliplr=True), save_dir, gen, write_games_pkl)
+            window.append(gen, tuple(t.to(window.device) for t in (games.boards, games.targets, games.policy)))
+            window.select(gen)
+            torch.cuda.synchronize(device)
+            t2 = time.perf_counter()
+            rows, nbytes = window.rows, window.nbytes
+            loss = trainer.train_window(window)
+            _checkpoint(trainer, save_dir, gen)
+        if multi:
+            loss = trainer.broadcast_state(src=0, extra=loss)
+        t3 = time.perf_counter()
+        losses.append(loss)
+        if timings is not None:
+            timings.append(dict(generation=gen, selfplay_and_gather_s=t1 - t0, tensors_and_write_s=t2 - t1, train_s=t3 - t2,
+                                positions=int(games.n_positions), training_rows=rows, window_rows=rows, window_bytes=nbytes))
+    return window, losses

@@ -48,6 +48,39 @@ def dataloader_permutation(n: int, generator: Optional[torch.Generator] = None) 
     return torch.randperm(n, generator=g)
 
 
+class _TensorBatches:
+    """Batch source of Trainer.train: the materialised dataset on the trainer's device, one tensor index per batch."""
+
+    def __init__(self, boards, values, priors, device):
+        self.rows = int(boards.shape[0])
+        self.boards, self.values, self.priors = boards.to(device), values.to(device), priors.to(device)
+
+    def static_out(self, batch_size):
+        return None             # (the captured indexings allocate their results in the graph's pool)
+
+    def __call__(self, idx, out=None):
+        return self.boards[idx], self.values[idx], self.priors[idx]
+
+
+class _WindowBatches:
+    """Batch source of Trainer.train_window: a ReplayWindow; a batch is one launch of its gather kernel.  The indices are
+    a permutation of range(window.rows), so the kernel's out-of-range counter is not read (no host synchronisation per
+    step); the captured step writes into buffers allocated before the capture."""
+
+    def __init__(self, window):
+        self.window = window
+        self.rows = int(window.rows)
+
+    def static_out(self, batch_size):
+        dev = self.window.device
+        return (torch.empty((batch_size, 3, 6, 7), dtype=torch.float32, device=dev),
+                torch.empty(batch_size, dtype=torch.float32, device=dev),
+                torch.empty((batch_size, 7), dtype=torch.float32, device=dev))
+
+    def __call__(self, idx, out=None):
+        return self.window.gather(idx, out=out, check=False)
+
+
 class Trainer:
     """ModelWrapper's training half (model.py:138-169, 200-250).  `device`: where the net trains; default =
     the reference's rule (cuda:0 when use_gpu and a GPU is there, model.py:143-147) -- a multi-rank caller
@@ -94,16 +127,30 @@ class Trainer:
         Returns the last batch's loss."""
         if self.device.type == "cuda":
             with torch.cuda.device(self.device):    # graph capture / replay and the library's launches go to the current device
-                return self._train(boards, values, priors, generator)
-        return self._train(boards, values, priors, generator)
+                return self._train(_TensorBatches(boards, values, priors, self.device), generator)
+        return self._train(_TensorBatches(boards, values, priors, self.device), generator)
 
-    def _train(self, boards, values, priors, generator):
-        n = int(boards.shape[0])
+    def train_window(self, window, generator=None):
+        """train() over a device-resident ReplayWindow (connect4_amd/replay.py) instead of the materialised tensors: the
+        same shuffles of window.rows (same consumption of torch's RNG), the same batch boundaries, padded ragged batch,
+        eager first steps and captured step -- only that a batch is built from the packed positions by the window's
+        gather kernel (the first node of the captured graph) instead of three tensor indexings.  Row r of the window is
+        row r of TrainingDataStorage.get_dataset, so both forms train on the same batches.  GPU only."""
+        if self.device.type != "cuda":
+            raise RuntimeError("Trainer.train_window needs a GPU trainer: a ReplayWindow is gathered by a HIP kernel "
+                               "(c4_window_gather_dev) and there is no CPU fallback; use train() on materialised tensors")
+        mine = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        if window.device != mine:
+            raise ValueError("the window lives on %s, the trainer on %s" % (window.device, self.device))
+        with torch.cuda.device(self.device):
+            return self._train(_WindowBatches(window), generator)
+
+    def _train(self, batches, generator):
+        n = batches.rows
         bs = self.config.batch_size
-        boards, values, priors = boards.to(self.device), values.to(self.device), priors.to(self.device)
         self.net.train()
         last = None
-        graph = None            # the captured step of THIS call (the data tensors and the learning rate are baked into it)
+        graph = None            # the captured step of THIS call (the data source and the learning rate are baked into it)
         eager_full = 0
         want_graph = self.use_graph and self.device.type == "cuda" and (n // bs) * self.config.n_training_epochs >= 4
         for _ in range(self.config.n_training_epochs):
@@ -113,7 +160,7 @@ class Trainer:
                 k = int(idx.shape[0])
                 if k == bs and want_graph:
                     if graph is None and eager_full >= 2:      # (the first steps run eagerly: momentum buffers, MIOpen's choices)
-                        graph, sidx, sloss = self._capture_step(boards, values, priors)
+                        graph, sidx, sloss = self._capture_step(batches)
                     if graph is not None:
                         sidx.copy_(idx)
                         graph.replay()
@@ -124,7 +171,7 @@ class Trainer:
                 if pad:   # DataLoader's drop_last=False batch (model.py:208-212), at the full batch's shape
                     idx = torch.cat([idx, idx[:1].expand(bs - k)])
                     self._set_valid_rows(k)
-                last = self._eager_step(boards[idx], values[idx], priors[idx], k if pad else None)
+                last = self._eager_step(*batches(idx), k if pad else None)
                 if pad:
                     self._set_valid_rows(None)
         last = None if last is None else float(last)
@@ -147,15 +194,16 @@ class Trainer:
         self.optimiser.step()
         return loss.detach()
 
-    def _capture_step(self, boards, values, priors):
+    def _capture_step(self, batches):
         """One full-batch train step -- gather by a static index tensor, forward, loss, backward, SGD -- captured as a HIP
         graph (torch.cuda.graph): replayed per batch with the batch's indices copied into `sidx`.  Same kernels, same order,
         same arithmetic as the eager step."""
         sidx = torch.zeros(self.config.batch_size, dtype=torch.int64, device=self.device)
+        out = batches.static_out(self.config.batch_size)
         self.optimiser.zero_grad(set_to_none=True)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            b, v, p = boards[sidx], values[sidx], priors[sidx]
+            b, v, p = batches(sidx, out)
             xv, xp = self.net(b)
             loss = self.value_loss(xv, v) + self.prior_loss(xp, p)
             loss.backward()

@@ -305,6 +305,37 @@ int c4_training_tensors_dev(int device, void *hip_stream, const int64_t *boards_
                             const float *policy_dev, int64_t n, int32_t add_fliplr, float *out_boards_dev,
                             float *out_values_dev, float *out_priors_dev);
 
+/* -- the sliding training window on the device (c4_window.hip) ------------------------------- */
+/* TrainingDataStorage.get_dataset (data.py:66-75) + native_to_pytorch (data.py:78-105) without the
+ * materialised tensors: the window is a device table of segments, one per generation, newest first, each the
+ * packed positions of that generation (what c4_export_games_dev wrote: boards int64 [n][2], targets float32 [n],
+ * policy float32 [n][7]).  Segment s contributes 2 n_s virtual rows -- its positions as stored, then their
+ * left-right mirrors (board.py:115-145, priors reversed, value duplicated) -- and rows are numbered across the
+ * segments in table order: the row order of the reference's ConcatDataset over the generations' data.pth.
+ * c4_window_gather_dev writes, for each of m int64 indices, boards_out float32 [m][3][6][7] (board.py:147-154),
+ * values_out float32 [m], priors_out float32 [m][7]: the bits that indexing the concatenated
+ * c4_training_tensors_dev outputs gives.  An index outside [0, rows) reads nothing, its row is zeros, and it is
+ * added to *n_out_of_range_dev (device int32, may be NULL; the caller zeroes it).  1 <= n_segments <=
+ * C4_WINDOW_MAX_SEGMENTS, else C4_EINVAL.  One launch on hip_stream; allocates nothing, waits for nothing
+ * (capturable in a HIP graph).  Messages of both calls: c4_window_last_error(). */
+#define C4_WINDOW_MAX_SEGMENTS 64
+typedef struct {
+    const int64_t *boards;    /* device [n_positions][2] */
+    const float   *targets;   /* device [n_positions] */
+    const float   *policy;    /* device [n_positions][7] */
+    int64_t        n_positions;
+} c4_window_segment;
+int c4_window_gather_dev(int device, void *hip_stream, const c4_window_segment *segments_dev, int32_t n_segments,
+                         const int64_t *index_dev, int64_t m, float *boards_out, float *values_out, float *priors_out,
+                         int32_t *n_out_of_range_dev /* may be NULL */);
+/* The inverse of c4_board_planes (board.py:147-154): planes_dev float32 [n][3][6][7] -> boards_out int64 [n][2].
+ * Adds to *n_bad_dev (device int32; the caller zeroes it) the rows that no board encodes: a cell that is neither
+ * 0.0 nor 1.0, a cell set in both colours, a to-move plane that is not constant, or one that contradicts the
+ * parity of the stone count.  For data.pth files the library did not write.  One launch on hip_stream. */
+int c4_planes_to_boards_dev(int device, void *hip_stream, const float *planes_dev, int64_t n, int64_t *boards_out,
+                            int32_t *n_bad_dev);
+const char *c4_window_last_error(void);
+
 /* Read-out of the evaluation cache (the memo table of evaluators.py:9-25): what it answers for the given
  * positions.  found[i] = 0 when the position is absent (never evaluated, or evicted).  Synchronous.
  * Lets a test replay device games on the oracle with exactly the evaluations the device used. */

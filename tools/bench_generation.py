@@ -4,6 +4,9 @@ finished games -> training tensors with flip augmentation built on the device ->
 5 epochs x batch 4096 of the reference's train recipe on those positions -> checkpoint.  One JSON line.
 
     python tools/bench_generation.py [--games 8192] [--slots 4096] [--sims 800] [--out DIR]
+    python tools/bench_generation.py --generations N ...    N generations in one call (generation.run_generations: the sliding
+                                                            window stays on the GPU as packed positions); one JSON line per
+                                                            generation, then the summary line
 
 (With 8 ranks every GPU plays this share and then trains on the all-gathered 65,536 games; the all-gather
 of ~50 B/position packed tensors is the only collective, connect4_amd/packed.py:all_gather_packed.)"""
@@ -24,12 +27,17 @@ def main():
     ap.add_argument("--sims", type=int, default=800)
     ap.add_argument("--out", default=None)
     ap.add_argument("--games-pkl", type=int, default=0, help="1: also write the object form (games.pkl)")
+    ap.add_argument("--generations", type=int, default=0,
+                    help="N > 0: run N generations with run_generations (device-resident window) and print per-generation timings; "
+                         "with --out pointing at a directory written earlier the run resumes it")
     a = ap.parse_args()
+    if a.generations < 0:
+        ap.error("--generations must be >= 0")
     import torch
     import __graft_entry__ as entry
     entry.build()
     from connect4_amd.config import MCTSConfig
-    from connect4_amd.generation import run_generation
+    from connect4_amd.generation import run_generation, run_generations
     from connect4_amd.training import ModelConfig, Trainer
     torch.manual_seed(0)
     tr = Trainer(ModelConfig(), device="cuda:0")
@@ -45,6 +53,22 @@ def main():
                torch.softmax(torch.rand(wn, 7, device="cuda"), 1))
     del warm
     torch.cuda.synchronize()
+    if a.generations:
+        per_gen = []
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        window, losses = run_generations(tr, MCTSConfig.self_play(a.sims), a.games, out, a.generations, n_slots=a.slots,
+                                         write_games_pkl=bool(a.games_pkl), timings=per_gen)
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t0
+        for t, loss in zip(per_gen, losses):
+            print(json.dumps(dict(t, last_loss=loss)))
+        print(json.dumps({"workload": "%d generations of %d self-play games at %d sims/move on %d slots, sliding window on the device"
+                                      % (a.generations, a.games, a.sims, a.slots),
+                          "generations": [t["generation"] for t in per_gen], "total_s": total, "games_per_s_end_to_end": a.generations * a.games / total,
+                          "window_generations": window.generations, "window_rows": window.rows, "window_bytes": window.nbytes,
+                          "peak_memory_allocated_bytes": int(torch.cuda.max_memory_allocated())}))
+        return
     timings = {}
     t0 = time.perf_counter()
     games, loss = run_generation(tr, MCTSConfig.self_play(a.sims), n_games=a.games, save_dir=out, gen=0, n_slots=a.slots,
