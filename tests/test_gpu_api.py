@@ -403,7 +403,10 @@ def test_end_to_end_net_driven_search_matches_reference():
         IDENTICAL, root value sums within 1e-4;
       * fused net in the opt-in fp16-storage mode (precision="f16"): outputs differ by up to 5e-3, so individual
         visit counts may move; stated tolerance: the visit distribution stays within 0.08 total variation
-        and the chosen move is the same."""
+        and the chosen move is the same.
+    Eight searches, seven of them at 200 simulations.  The same claim at the production simulation count, with root noise
+    and on the positions of whole self-play games -- 130 searches, each marked by whether the reference decides it by a
+    margin or it is a near-tie -- is test_gpu_net_parity.py::test_searches_against_the_reference."""
     import torch
     from connect4_amd.board import Board
     from connect4_amd.evaluators import DeviceNetEvaluator
