@@ -2215,13 +2215,18 @@ __global__ void c4_gather_roots_kernel(Dev d, c4_root_result *out)
     r.color1 = d.root_c1[g];
     const uint32_t rinfo = pool.info(0);
     for (int i = 0; i < 7; ++i) { r.child_status[i] = -2; r.values_policy[i] = d.cold->res_policy[(size_t)g * 7 + i]; }
-    if (info_status(rinfo) == ST_EVALUATED) {
+    // c4_reset does not touch the pools: until a slot's first step its root record is whatever the memory held before
+    // (a freed engine's tree, say), so the root counts as evaluated only if its child block is one this slot allocated
+    const uint32_t blocks = d.n_alloc[g] < d.cap ? d.n_alloc[g] : d.cap;
+    const uint32_t rcb = info_base(rinfo);
+    if (info_status(rinfo) == ST_EVALUATED && rcb >= GROUP && rcb + GROUP <= blocks * GROUP) {
         r.root_visits = pool.n(0);
         r.root_value_sum = pool.w(0);
-        const uint32_t cb = info_base(rinfo), nc = info_nchild(rinfo);
+        const uint32_t cb = rcb, nc = info_nchild(rinfo);
         for (uint32_t k = 0; k < nc; ++k) {
             const uint32_t ci = pool.info(cb + k);
             const int m = (int)info_move(ci);
+            if (m >= 7) continue;
             r.child_visits[m] = pool.n(cb + k);
             r.child_value_sum[m] = pool.w(cb + k);
             r.child_status[m] = info_status(ci) >= ST_XWIN ? (int32_t)(info_status(ci) - ST_XWIN) : -1;

@@ -11,6 +11,55 @@ def table_lookup_fn(c0s, c1s, vs, ps):
     return fn
 
 
+class PlanesAdapter:
+    """A planes-fed evaluator with a FusedNet's exact answers: planes [n,3,6,7] (any float dtype) ->
+    (values f32 [n], priors f32 [n,7]).  It decodes the planes back to bitboards on the device
+    (c4_planes_to_boards_dev) and evaluates those with the fused forward, so a self-play run fed through the
+    planes buffer plays the bitboard path's games bit for bit -- unless c4_step emitted wrong planes.  Two
+    launches on the current stream and no host synchronisation: it can be captured in a HIP graph.  It does not
+    set from_bitboards, so SelfPlay and the searchers treat it like any PyTorch net.  An all-zero row (a slot that
+    has not emitted a leaf yet) decodes to the empty board; planes_to_boards counts it as bad, nobody reads that."""
+
+    def __init__(self, fused_net):
+        self.net = fused_net
+
+    def __call__(self, planes):
+        import torch
+        from connect4_amd.engine import planes_to_boards
+        boards, _ = planes_to_boards(planes.float())
+        n = int(boards.shape[0])
+        c0, c1 = boards[:, 0].contiguous(), boards[:, 1].contiguous()
+        values = torch.empty(n, dtype=torch.float32, device=planes.device)
+        priors = torch.empty((n, 7), dtype=torch.float32, device=planes.device)
+        self.net.forward_bitboards(c0.data_ptr(), c1.data_ptr(), n, values, priors)
+        return values, priors
+
+
+def random_undecided_positions(oracle, n, seed, max_plies=30):
+    """n seeded random positions of 0..max_plies plies that are not decided, as oracle Boards."""
+    rng = np.random.RandomState(seed)
+    boards = []
+    while len(boards) < n:
+        b = oracle.Board.empty()
+        for _ in range(int(rng.randint(0, max_plies + 1))):
+            m = b.valid_mask()
+            if not m or b.result != -1:
+                break
+            b.make_move(int(rng.choice([c for c in range(7) if (m >> c) & 1])))
+        if b.result == -1:
+            boards.append(b)
+    return boards
+
+
+def root_fields(r):
+    """Every field of a c4_root_result, floats as bit patterns (NaN compares equal to itself)."""
+    bits = lambda x: np.asarray(x, dtype=np.float64).view(np.uint64).tolist()  # noqa: E731
+    return dict(state=r.state, move=r.move, value=bits(r.value), root_visits=r.root_visits, root_value_sum=bits(r.root_value_sum),
+                child_visits=list(r.child_visits), child_value_sum=bits(list(r.child_value_sum)), child_status=list(r.child_status),
+                root_prior=bits(list(r.root_prior)), values_policy=bits(list(r.values_policy)), color0=r.color0, color1=r.color1,
+                expansions=r.expansions, simulations=r.simulations)
+
+
 def drive_external(eng, eval_fn, dtype, max_steps=10_000_000):
     """Run an EXTERNAL_* engine to completion with a Python evaluator (c0,c1)->(value, prior[7]).
     Mirrors how evaluators.py:18-25 serves mcts.py:130, one leaf per slot per step."""

@@ -106,6 +106,100 @@ def test_device_export_equals_host_drain():
     assert np.array_equal(b.cpu().numpy(), hb) and np.array_equal(v.cpu().numpy(), hv) and np.array_equal(p.cpu().numpy(), hp)
 
 
+def _play_out(sp):
+    for _ in range(400):
+        sp.run_steps(64)
+        st = sp.stats()
+        if st["active_slots"] == 0:
+            break
+    assert st["active_slots"] == 0 and st["dropped_games"] == 0
+    return st
+
+
+_PACKED_FIELDS = ("boards", "moves", "values", "policy", "targets", "game_index", "lengths", "results", "ids")
+
+
+def test_device_export_with_a_position_cap_takes_the_longest_prefix_that_fits():
+    """c4_export_games_dev into buffers smaller than what waits (k_export_scan's cap_pos prefix, what bench.py's fixed-size
+    export buffers rely on): every part holds whole games, at most `cap` positions, and as many games as fit; a cap of 0
+    takes nothing and loses nothing; all parts together are the uncapped export of the same run."""
+    import torch
+    from connect4_amd.packed import PackedGames
+    cap = 100
+    sp, net = _selfplay(48, 24, 120, 120, seed=9)
+    remaining = _play_out(sp)["moves"]                     # every position of a finished game is one move
+    none = sp.engine.export_games(cap_positions=0)
+    assert none.n_games == 0 and none.n_positions == 0 and sp.engine.finished_games()[0] == 120
+    parts = []
+    while sp.engine.finished_games()[0] > 0:
+        assert len(parts) < 120
+        # (the last part's buffers are exactly as large as what is left: games that fill a buffer to the brim fit)
+        part = sp.engine.export_games(cap_positions=min(cap, remaining))
+        lengths = part.lengths.cpu().long()
+        assert part.n_games >= 1
+        assert part.n_positions == int(lengths.sum()) <= min(cap, remaining)
+        remaining -= part.n_positions
+        assert (lengths >= 1).all()
+        assert torch.equal(part.game_index.cpu().long(), torch.repeat_interleave(torch.arange(part.n_games), lengths))
+        parts.append(part)
+    assert remaining == 0
+    assert sum(p.n_games for p in parts) == 120 and len(parts) > 8      # >= 7 plies a game, <= cap positions a part
+    for this, following in zip(parts, parts[1:]):        # maximal: the next game would not have fitted
+        assert this.n_positions + int(following.lengths[0]) > cap
+    sp.close()
+    capped = PackedGames.cat(parts).sorted_by_id()
+    net.close()
+    sp, net = _selfplay(48, 24, 120, 120, seed=9)
+    _play_out(sp)
+    whole = sp.engine.export_games().sorted_by_id()
+    sp.close()
+    net.close()
+    assert whole.n_games == 120 and whole.ids.tolist() == list(range(120))
+    for k in _PACKED_FIELDS:
+        a, b = getattr(capped, k).cpu(), getattr(whole, k).cpu()
+        if k == "values":
+            a, b = a.nan_to_num(nan=-1.0), b.nan_to_num(nan=-1.0)
+        assert torch.equal(a, b), k
+
+
+def test_device_export_scans_more_than_one_chunk_of_waiting_games(oracle):
+    """1100 games wait in the ring: k_export_scan walks them in two chunks of 1024 and carries the position count from the
+    first into the second.  A cap one position short of everything takes all games but the last one; the next export
+    takes that one.  Together: every id once, every position once, and the boards of a game chain through its moves."""
+    from connect4_amd.packed import PackedGames
+    from oracle.replay import packed_records
+    n = 1100
+    sp, net = _selfplay(256, 16, n, 1200)
+    st = _play_out(sp)
+    assert st["games_finished"] == n and sp.engine.finished_games()[0] == n
+    total = st["moves"]                                    # every position of a finished game is one move
+    first = sp.engine.export_games(max_games=1200, cap_positions=total - 1)
+    second = sp.engine.export_games(max_games=1200)
+    assert sp.engine.finished_games()[0] == 0
+    sp.close()
+    net.close()
+    assert second.n_games == 1 and first.n_games == n - 1
+    assert first.n_positions == total - int(second.lengths[0]) and first.n_positions + second.n_positions == total
+    assert first.n_positions == int(first.lengths.sum()) and second.n_positions == int(second.lengths.sum())
+    both = PackedGames.cat([first, second])
+    assert sorted(both.ids.tolist()) == list(range(n))
+    rng = np.random.RandomState(0)
+    sample = [0, 1022, 1023, 1024, 1025, n - 2, n - 1]     # ring order: both sides of the chunk boundary, and the last game
+    for k in rng.permutation(n).tolist():
+        if len(sample) == 50:
+            break
+        if k not in sample:
+            sample.append(k)
+    for rec in packed_records(both, sample):
+        b = oracle.Board.empty()
+        for i in range(rec.length):
+            assert b.key() == (int(rec.color0[i]), int(rec.color1[i])), "plies of two games mixed in one record"
+            assert (b.valid_mask() >> rec.move[i]) & 1
+            assert abs(float(rec.policy[i].sum()) - 1.0) < 1e-6     # float32 here
+            b.make_move(int(rec.move[i]))
+        assert b.result == rec.result and rec.result in (0, 1, 2)
+
+
 def test_training_tensors_dev_against_reference_fixture():
     """c4_training_tensors_dev vs native_to_pytorch(add_fliplr=True) of the unmodified reference (data.py:78-105)."""
     import torch
