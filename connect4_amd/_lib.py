@@ -95,6 +95,13 @@ class WindowSegment(C.Structure):
     _fields_ = [("boards", C.c_void_p), ("targets", C.c_void_p), ("policy", C.c_void_p), ("n_positions", C.c_int64)]
 
 
+class ScoreAcc(C.Structure):
+    """c4_score_acc: the accumulator of c4_score_update_dev, as read back from the device (112 bytes)."""
+    _fields_ = [("n", C.c_int64), ("total", C.c_int64 * 3), ("correct", C.c_int64 * 3), ("prior_n", C.c_int64),
+                ("prior_correct", C.c_int64), ("non_finite", C.c_int64), ("sum_outputs", C.c_double),
+                ("value_sq_err_sum", C.c_double), ("prior_bce_sum", C.c_double), ("smallest", C.c_float), ("largest", C.c_float)]
+
+
 class NetDesc(C.Structure):
     _fields_ = [("channels", C.c_int32), ("filters", C.c_int32), ("n_residuals", C.c_int32), ("precision", C.c_int32)] + \
         [(n, C.POINTER(C.c_float)) for n in ("stem_w", "stem_b", "conv_w", "conv_b", "head_w", "head_b",
@@ -164,6 +171,10 @@ SIGNATURES = {
     "c4_bn_train_backward": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "c4_conv3x3_wrw_workspace_floats": (C.c_longlong, []),
     "c4_conv3x3_wrw": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "c4_score_workspace_bytes": (C.c_longlong, [C.c_longlong]),
+    "c4_score_reset_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
+    "c4_score_update_dev": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_longlong] * 2 + [C.c_void_p] * 2),
+    "c4_score_last_error": (C.c_char_p, []),
 }
 
 _lib = None

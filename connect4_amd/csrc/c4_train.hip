@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdio>
+
 #include "../../include/c4_engine.h"
 
 namespace {
@@ -445,6 +447,236 @@ int c4_conv3x3_wrw(const float *x_dev, const float *dy_dev, float *dweight_dev, 
     conv3x3_wrw_partial_kernel<<<wgs, WRW_WAVES * 64, 0, s>>>(x_dev, dy_dev, workspace_dev, rows);
     conv3x3_wrw_reduce_kernel<<<9 * 1024 / 32, 256, 0, s>>>(workspace_dev, dweight_dev, wgs);
     return hipGetLastError() == hipSuccess ? C4_OK : C4_EDEVICE;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// c4_score_*: the reference's value and policy statistics (oinkoink/neural/stats.py:53-71, 99-113, fed per batch by
+// ModelWrapper.train(print_stats=True), model.py:228-234, and by evaluate / evaluate_value_only, model.py:307-342)
+// accumulated where the outputs are.  One lane = one row: its value pair, its 2 x 7 priors; counts are integers, min / max
+// are order free, and the three sums -- outputs, (x - y)^2, BCE -- are formed per row in float64 and put on a fixed
+// binary grid (SCORE_Q_* bits below one) BEFORE they are added, as int64.  Integer addition is associative, so the
+// totals depend neither on the lane -> wave -> workgroup tree nor on the grid, the dispatch order, or how a caller
+// splits its rows into calls; the accumulator's doubles stay whole multiples of the grid and their additions exact
+// while a total is below 2^53 grid units (131,072 for the outputs and the squared errors: some 260,000 rows at a mean
+// output of 0.5; 2,097,152 for the BCE); then they round like any float64 sum, still in a fixed order.
+// Two launches: workgroups write one partial record each, a single workgroup adds them up (its threads take the
+// partials strided and reduce by the same tree: integers and min / max, so no order matters) into the accumulator -- the
+// kernel boundary is the only cross-workgroup ordering relied on; no floating-point atomics, no last-block fold.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int SCORE_TB = 256, SCORE_MAX_WGS = 256;
+// grid of the sums: 2^-Q (a term is off by <= 2^-(Q+1): below 1e-10 of a row mean of 0.1 resp. 2); exact up to 2^(53-Q) = 131,072 / 2,097,152
+constexpr int SCORE_Q_OUT = 36, SCORE_Q_VAL = 36, SCORE_Q_BCE = 32;
+constexpr float SCORE_MAX_ABS = 1024.0f;    // value outputs and labels beyond it count as non-finite rows (their terms would leave int64)
+constexpr int SCORE_NI = 11;                                         // int64 fields of a partial
+
+struct ScorePartial {     // what one workgroup saw; fixed layout, one per workgroup in the workspace
+    long long v[SCORE_NI];  // total[3], correct[3], prior_correct, non_finite, sum of outputs / squared errors / BCE in grid units
+    float smallest, largest;
+};
+enum { SP_TOTAL = 0, SP_CORRECT = 3, SP_PCORRECT = 6, SP_NONFINITE = 7, SP_OUT = 8, SP_VAL = 9, SP_BCE = 10 };
+
+thread_local char score_err[256] = "";
+
+__device__ __forceinline__ long long to_grid(double t, int q) { return __double2ll_rn(ldexp(t, q)); }
+
+// workgroup totals of a lane's partial, in thread 0 (integers and min / max: any tree gives the same answer)
+__device__ __forceinline__ void score_block_reduce(ScorePartial &p, long long (*s_v)[SCORE_NI], float (*s_f)[2])
+{
+#pragma unroll
+    for (int i = 0; i < SCORE_NI; ++i)
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) p.v[i] += __shfl_xor(p.v[i], m, 64);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        p.smallest = fminf(p.smallest, __shfl_xor(p.smallest, m, 64));
+        p.largest = fmaxf(p.largest, __shfl_xor(p.largest, m, 64));
+    }
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < SCORE_NI; ++i) s_v[wv][i] = p.v[i];
+        s_f[wv][0] = p.smallest;
+        s_f[wv][1] = p.largest;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < SCORE_TB / 64; ++w) {
+#pragma unroll
+            for (int i = 0; i < SCORE_NI; ++i) p.v[i] += s_v[w][i];
+            p.smallest = fminf(p.smallest, s_f[w][0]);
+            p.largest = fmaxf(p.largest, s_f[w][1]);
+        }
+}
+
+__device__ __forceinline__ void score_empty(ScorePartial &p)
+{
+#pragma unroll
+    for (int i = 0; i < SCORE_NI; ++i) p.v[i] = 0;
+    p.smallest = __builtin_inff();
+    p.largest = -__builtin_inff();
+}
+
+__global__ __launch_bounds__(SCORE_TB) void score_partial_kernel(const float *__restrict__ xv, const float *__restrict__ yv,
+                                                                 const float *__restrict__ xp, const float *__restrict__ yp,
+                                                                 long long valid_rows, ScorePartial *__restrict__ partial)
+{
+    __shared__ long long s_v[SCORE_TB / 64][SCORE_NI];
+    __shared__ float s_f[SCORE_TB / 64][2];
+    ScorePartial p;
+    score_empty(p);
+    for (long long r = (long long)blockIdx.x * SCORE_TB + threadIdx.x; r < valid_rows; r += (long long)gridDim.x * SCORE_TB) {
+        const float x = xv[r], y = yv[r];
+        bool finite = fabsf(x) <= SCORE_MAX_ABS && fabsf(y) <= SCORE_MAX_ABS;     // (false for a NaN)
+        // stats.py:67-71 in float32, as numpy keeps it: an output of exactly 1.0 is category 1.5 and never correct
+        const float cat = floorf(x * 3.0f) / 2.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (y == 0.5f * (float)k) {
+                p.v[SP_TOTAL + k] += 1;
+                p.v[SP_CORRECT + k] += cat == y ? 1 : 0;
+            }
+        p.smallest = x < p.smallest ? x : p.smallest;
+        p.largest = x > p.largest ? x : p.largest;
+        double bce = 0.0;
+        if (xp) {
+            float a[7], b[7];
+#pragma unroll
+            for (int j = 0; j < 7; ++j) { a[j] = xp[r * 7 + j]; b[j] = yp[r * 7 + j]; }
+            int best = 0;                 // np.argmax: the first index of the largest output
+            float ymax = b[0];
+#pragma unroll
+            for (int j = 1; j < 7; ++j) {
+                best = a[j] > a[best] ? j : best;
+                ymax = b[j] > ymax ? b[j] : ymax;
+            }
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {
+                finite = finite && a[j] >= 0.0f && a[j] <= 1.0f;      // (what torch.nn.BCELoss accepts; false for a NaN)
+                const double o = (double)a[j], t = (double)b[j];
+                bce -= t * fmax(log(o), -100.0) + (1.0 - t) * fmax(log(1.0 - o), -100.0);   // torch.nn.BCELoss's clamp
+            }
+            p.v[SP_PCORRECT] += b[best] == ymax ? 1 : 0;   // stats.py:103-113: the move is among the label row's maxima
+        }
+        if (finite) {
+            const double d = (double)x - (double)y;
+            p.v[SP_OUT] += to_grid((double)x, SCORE_Q_OUT);
+            p.v[SP_VAL] += to_grid(d * d, SCORE_Q_VAL);
+            p.v[SP_BCE] += to_grid(bce, SCORE_Q_BCE);
+        } else {
+            p.v[SP_NONFINITE] += 1;
+        }
+    }
+    score_block_reduce(p, s_v, s_f);
+    if (threadIdx.x == 0) partial[blockIdx.x] = p;
+}
+
+__global__ __launch_bounds__(SCORE_TB) void score_fold_kernel(const ScorePartial *__restrict__ partial, int n_partials, long long valid_rows,
+                                                              int with_priors, c4_score_acc *acc)
+{
+    __shared__ long long s_v[SCORE_TB / 64][SCORE_NI];
+    __shared__ float s_f[SCORE_TB / 64][2];
+    ScorePartial p;
+    score_empty(p);
+    for (int i = threadIdx.x; i < n_partials; i += SCORE_TB) {
+        const ScorePartial q = partial[i];
+#pragma unroll
+        for (int k = 0; k < SCORE_NI; ++k) p.v[k] += q.v[k];
+        p.smallest = fminf(p.smallest, q.smallest);
+        p.largest = fmaxf(p.largest, q.largest);
+    }
+    score_block_reduce(p, s_v, s_f);
+    if (threadIdx.x == 0) {
+        acc->n += valid_rows;
+        for (int k = 0; k < 3; ++k) {
+            acc->total[k] += p.v[SP_TOTAL + k];
+            acc->correct[k] += p.v[SP_CORRECT + k];
+        }
+        if (with_priors) {
+            acc->prior_n += valid_rows;
+            acc->prior_correct += p.v[SP_PCORRECT];
+        }
+        acc->non_finite += p.v[SP_NONFINITE];
+        acc->sum_outputs += ldexp((double)p.v[SP_OUT], -SCORE_Q_OUT);
+        acc->value_sq_err_sum += ldexp((double)p.v[SP_VAL], -SCORE_Q_VAL);
+        acc->prior_bce_sum += ldexp((double)p.v[SP_BCE], -SCORE_Q_BCE);
+        acc->smallest = fminf(acc->smallest, p.smallest);
+        acc->largest = fmaxf(acc->largest, p.largest);
+    }
+}
+
+__global__ void score_reset_kernel(c4_score_acc *acc)
+{
+    c4_score_acc z = {};
+    z.smallest = __builtin_inff();      // the reference's starting values 1.0 / 0.0 are applied by the reader (stats.py:9-10, 57-58)
+    z.largest = -__builtin_inff();
+    *acc = z;
+}
+
+int score_grid(long long rows)
+{
+    const long long wgs = (rows + SCORE_TB - 1) / SCORE_TB;
+    return (int)(wgs < SCORE_MAX_WGS ? wgs : SCORE_MAX_WGS);
+}
+
+int score_use_device(int device)
+{
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { snprintf(score_err, sizeof(score_err), "no HIP device available: there is no CPU fallback"); return C4_EDEVICE; }
+    if (device < 0 || device >= count) { snprintf(score_err, sizeof(score_err), "device %d out of range (have %d)", device, count); return C4_EDEVICE; }
+    if (hipSetDevice(device) != hipSuccess) { snprintf(score_err, sizeof(score_err), "hipSetDevice(%d) failed", device); return C4_EDEVICE; }
+    return C4_OK;
+}
+
+}  // namespace
+
+static_assert(sizeof(c4_score_acc) == 112, "c4_score_acc is 112 bytes (connect4_amd/_lib.py: ScoreAcc)");
+
+extern "C" {
+
+const char *c4_score_last_error(void) { return score_err; }
+
+long long c4_score_workspace_bytes(long long rows)
+{
+    if (rows <= 0) return C4_EINVAL;
+    return (long long)score_grid(rows) * (long long)sizeof(ScorePartial);
+}
+
+int c4_score_reset_dev(int device, void *hip_stream, c4_score_acc *acc_dev)
+{
+    if (!acc_dev) { snprintf(score_err, sizeof(score_err), "c4_score_reset_dev: no accumulator"); return C4_EINVAL; }
+    int rc = score_use_device(device);
+    if (rc) return rc;
+    score_reset_kernel<<<1, 1, 0, (hipStream_t)hip_stream>>>(acc_dev);
+    hipError_t r = hipGetLastError();
+    if (r != hipSuccess) { snprintf(score_err, sizeof(score_err), "score_reset_kernel launch failed: %s", hipGetErrorString(r)); return C4_EDEVICE; }
+    return C4_OK;
+}
+
+int c4_score_update_dev(int device, void *hip_stream, const float *x_value, const float *y_value, const float *x_prior, const float *y_prior,
+                        long long rows, long long valid_rows, c4_score_acc *acc_dev, void *workspace_dev)
+{
+    if (rows <= 0 || valid_rows < 0 || valid_rows > rows) {
+        snprintf(score_err, sizeof(score_err), "c4_score_update_dev: rows %lld, valid_rows %lld (rows >= 1, 0 <= valid_rows <= rows)", rows, valid_rows);
+        return C4_EINVAL;
+    }
+    if (!x_value || !y_value || !acc_dev || !workspace_dev || (x_prior == nullptr) != (y_prior == nullptr)) {
+        snprintf(score_err, sizeof(score_err), "c4_score_update_dev: bad argument (the prior pointers come as a pair or not at all)");
+        return C4_EINVAL;
+    }
+    int rc = score_use_device(device);
+    if (rc || valid_rows == 0) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const int wgs = score_grid(rows);     // from `rows`, as c4_score_workspace_bytes(rows) sized the workspace
+    ScorePartial *partial = (ScorePartial *)workspace_dev;
+    score_partial_kernel<<<wgs, SCORE_TB, 0, s>>>(x_value, y_value, x_prior, y_prior, valid_rows, partial);
+    score_fold_kernel<<<1, SCORE_TB, 0, s>>>(partial, wgs, valid_rows, x_prior ? 1 : 0, acc_dev);
+    hipError_t r = hipGetLastError();
+    if (r != hipSuccess) { snprintf(score_err, sizeof(score_err), "c4_score_update_dev launch failed: %s", hipGetErrorString(r)); return C4_EDEVICE; }
+    return C4_OK;
 }
 
 }  // extern "C"

@@ -2,10 +2,14 @@
 rank's GPU -> device-side export of the finished games -> all-gather of the packed tensors (RCCL over xGMI)
 -> on rank 0: data.pth with flip augmentation built on the device, the reference's train recipe on the sliding
 window, checkpoint -> broadcast of the trained state to every rank (one model, as in the reference).  Mirrors TrainingLoop._loop
-(oinkoink/neural/training.py:78-153) with the hot path replaced; the surrounding bookkeeping
-(evaluation sets, match history, visdom) stays with the reference's loop.
+(oinkoink/neural/training.py:78-153) with the hot path replaced.  The evaluation sets of TrainingLoop._evaluate
+(training.py:155-170) are scored here too: after rank 0 has trained and checkpointed, every set of `test_sets` goes through
+Trainer.evaluate / evaluate_value_only (statistics accumulated on the device, connect4_amd/stats.py) and the scores are
+appended to save_dir/<name>.pkl; `train_stats` keeps the reference's per-epoch training statistics (print_stats).  The
+rest of the surrounding bookkeeping (match history, visdom) stays with the reference's loop.
 """
 import os
+import pickle
 import time
 from typing import Optional
 
@@ -26,15 +30,20 @@ def existing_window(save_dir: str, gen: int):
 
 def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir: Optional[str] = None, gen: int = 0,
                    seed: int = 0, device: int = 0, n_slots: Optional[int] = None, write_games_pkl: bool = False,
-                   timings: Optional[dict] = None, precision: Optional[str] = None):
+                   timings: Optional[dict] = None, precision: Optional[str] = None, test_sets: Optional[dict] = None,
+                   train_stats: bool = False):
     """Returns (PackedGames of all ranks, last_loss).  With torch.distributed initialised every rank plays its shard and
     all ranks receive all games.  There is ONE model, as in the reference (training.py:147-153, model.py:143-147): rank 0
     writes save_dir/<gen>/{data.pth, games.pkl} (storage.py:15-16, data.py:47-64), trains on `trainer.device` over the
     window min(20, int((gen+1)/2)) generations (data.py:66-75; the earlier generations that save_dir holds), writes
     net.pth, and then every rank receives rank 0's net / optimiser / scheduler state (broadcast), so the next
-    generation's shards are all played by the same net.  `precision`: see make_selfplay_net (None = the reference's)."""
+    generation's shards are all played by the same net.  `precision`: see make_selfplay_net (None = the reference's).
+    `test_sets` (name -> stats.LabelledSet or the path of a Connect4Dataset file) and `train_stats`: see score_test_sets and
+    Trainer.train(stats=True); both are rank 0's work and add no collective.  A path is loaded on every call: a caller that
+    loops over run_generation passes LabelledSets (load_test_sets once); run_generations loads each path once."""
     import torch
     multi, rank = _ranks()
+    test_sets = load_test_sets(test_sets, trainer.device) if rank == 0 else None
     earlier = existing_window(save_dir, gen) if (save_dir is not None and rank == 0) else []
     t0 = time.perf_counter()
     games = _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision)
@@ -53,7 +62,7 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
         torch.cuda.synchronize(device)
         t2 = time.perf_counter()
         rows = int(boards.shape[0])
-        loss = trainer.train(boards, values, priors)
+        loss = trainer.train(boards, values, priors, stats=True) if train_stats else trainer.train(boards, values, priors)
         _checkpoint(trainer, save_dir, gen)
     if multi:
         loss = trainer.broadcast_state(src=0, extra=loss)
@@ -61,6 +70,8 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
     if timings is not None:
         timings.update(selfplay_and_gather_s=t1 - t0, tensors_and_write_s=t2 - t1, train_s=t3 - t2,
                        positions=int(games.n_positions), training_rows=rows)
+    if rank == 0:
+        _report(trainer, test_sets, train_stats, save_dir, gen, timings)
     return games, loss
 
 
@@ -103,6 +114,52 @@ def _checkpoint(trainer, save_dir, gen):
         torch.cuda.synchronize(trainer.device)
 
 
+# -- scores after a generation (training.py:155-170) ------------------------------------------------------------------
+def load_test_sets(test_sets, device):
+    """name -> LabelledSet, the paths among the values loaded (stats.LabelledSet.load) onto `device`."""
+    if not test_sets:
+        return {}
+    from .stats import LabelledSet
+    return {name: s if not isinstance(s, (str, os.PathLike)) else LabelledSet.load(s, device=device) for name, s in test_sets.items()}
+
+
+def score_test_sets(trainer, test_sets, save_dir=None, gen=0):
+    """TrainingLoop._evaluate: every set scored by the trainer's net -- Trainer.evaluate, or evaluate_value_only for a set
+    without priors (the reference's 7- and 8-ply sets) -- as {name: to_dict() of plain Python numbers}.  With a save_dir each
+    result is also appended to save_dir/<name>.pkl: a pickled list of {"generation": gen, **to_dict()}, the reference's
+    8ply.pkl / 7ply.pkl without pandas.  The file is re-read and extended (a resumed run goes on where it stopped).  The
+    file follows the run: an entry of this generation is replaced, and entries of LATER generations -- left by a run that
+    is being redone from an explicit lower first_gen -- are dropped, as their checkpoints are about to be overwritten."""
+    from .stats import plain_dict
+    out = {}
+    for name, data in test_sets.items():
+        priors = data.priors if hasattr(data, "priors") else (data[2] if len(data) > 2 else None)
+        st = trainer.evaluate(data) if priors is not None else trainer.evaluate_value_only(data)
+        out[name] = plain_dict(st)
+        if save_dir is not None:
+            path = os.path.join(save_dir, "%s.pkl" % name)
+            history = []
+            if os.path.exists(path):
+                with open(path, "rb") as f:
+                    history = [e for e in pickle.load(f) if e["generation"] < gen]
+            history.append(dict(generation=int(gen), **out[name]))
+            history.sort(key=lambda e: e["generation"])
+            with open(path + ".tmp", "wb") as f:
+                pickle.dump(history, f)
+            os.replace(path + ".tmp", path)
+    return out
+
+
+def _report(trainer, test_sets, train_stats, save_dir, gen, timings):
+    """Rank 0, after the checkpoint: test-set scores and per-epoch training statistics into the generation's timings dict."""
+    from .stats import plain_dict
+    scores = score_test_sets(trainer, test_sets, save_dir, gen) if test_sets else {}
+    if timings is not None:
+        timings.update(scores)
+        if train_stats:
+            timings["train_stats"] = [plain_dict(s) for s in trainer.epoch_stats]
+
+
 # -- many generations: the window stays on the device -----------------------------------------------------------------
 def latest_generation(save_dir: str):
     """(next generation, path of the net.pth to resume from or None): the resume rule of TrainingLoop.__init__
@@ -134,7 +191,8 @@ def latest_generation(save_dir: str):
 
 def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir: str, n_generations: int,
                     first_gen: Optional[int] = None, seed: int = 0, device: int = 0, n_slots: Optional[int] = None,
-                    precision: Optional[str] = None, write_games_pkl: bool = False, timings: Optional[list] = None):
+                    precision: Optional[str] = None, write_games_pkl: bool = False, timings: Optional[list] = None,
+                    test_sets: Optional[dict] = None, train_stats: bool = False):
     """n_generations generations of run_generation -- same seeds (seed + 1000 * gen), same files (data.pth, net.pth,
     optional games.pkl), same broadcast of the trained state -- with the sliding window (data.py:66-75) kept on rank 0's GPU
     as packed positions (replay.ReplayWindow): each generation's games are appended to it and trained with
@@ -146,11 +204,14 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
     window is rebuilt from the data.pth files (ReplayWindow.from_directory; each file is verified).  An explicit
     first_gen starts there with the trainer as it is and, like run_generation, with what earlier generations save_dir
     holds.  `timings`: a list that receives one dict per generation -- run_generation's keys, plus window_rows and
-    window_bytes.  Returns (the window -- None on other ranks --, [last loss of each generation])."""
+    window_bytes, and with `test_sets` / `train_stats` (as run_generation: scored on rank 0 after each checkpoint, appended
+    to save_dir/<name>.pkl) the sets' names and train_stats.  Returns (the window -- None on other ranks --, [last loss of
+    each generation])."""
     import torch
     from .replay import ReplayWindow
     multi, rank = _ranks()
     os.makedirs(save_dir, exist_ok=True)
+    test_sets = load_test_sets(test_sets, trainer.device) if rank == 0 else None
     if first_gen is None:
         first_gen, net_path = latest_generation(save_dir)
         if net_path is not None:
@@ -175,13 +236,16 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
             torch.cuda.synchronize(device)
             t2 = time.perf_counter()
             rows, nbytes = window.rows, window.nbytes
-            loss = trainer.train_window(window)
+            loss = trainer.train_window(window, stats=True) if train_stats else trainer.train_window(window)
             _checkpoint(trainer, save_dir, gen)
         if multi:
             loss = trainer.broadcast_state(src=0, extra=loss)
         t3 = time.perf_counter()
         losses.append(loss)
+        report = dict(generation=gen, selfplay_and_gather_s=t1 - t0, tensors_and_write_s=t2 - t1, train_s=t3 - t2,
+                      positions=int(games.n_positions), training_rows=rows, window_rows=rows, window_bytes=nbytes)
+        if rank == 0:
+            _report(trainer, test_sets, train_stats, save_dir, gen, report)
         if timings is not None:
-            timings.append(dict(generation=gen, selfplay_and_gather_s=t1 - t0, tensors_and_write_s=t2 - t1, train_s=t3 - t2,
-                                positions=int(games.n_positions), training_rows=rows, window_rows=rows, window_bytes=nbytes))
+            timings.append(report)
     return window, losses

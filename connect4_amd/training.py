@@ -119,18 +119,21 @@ class Trainer:
             self.scheduler.load_state_dict(ckpt["scheduler_state_dict"])
         self.value_loss = nn.MSELoss()
         self.prior_loss = nn.BCELoss()
+        self.epoch_stats = []       # train(..., stats=True): one CombinedStats per epoch of the last call
         self.net.eval()
 
-    def train(self, boards, values, priors, generator=None):
+    def train(self, boards, values, priors, generator=None, stats=False):
         """One generation (model.py:200-240): n_training_epochs shuffled passes over (boards F32[N,3,6,7],
         values F32[N], priors F32[N,7]) -- tensors on any device; they are moved to the trainer's device once.
-        Returns the last batch's loss."""
+        Returns the last batch's loss.  stats=True is the reference's print_stats (model.py:208-209, 228-237): every
+        step's outputs and labels are added to a device accumulator (stats.DeviceStats; one more launch pair of the step,
+        captured with it) and after the last batch ONE read-back fills self.epoch_stats, a CombinedStats per epoch."""
         if self.device.type == "cuda":
             with torch.cuda.device(self.device):    # graph capture / replay and the library's launches go to the current device
-                return self._train(_TensorBatches(boards, values, priors, self.device), generator)
-        return self._train(_TensorBatches(boards, values, priors, self.device), generator)
+                return self._train(_TensorBatches(boards, values, priors, self.device), generator, stats)
+        return self._train(_TensorBatches(boards, values, priors, self.device), generator, stats)
 
-    def train_window(self, window, generator=None):
+    def train_window(self, window, generator=None, stats=False):
         """train() over a device-resident ReplayWindow (connect4_amd/replay.py) instead of the materialised tensors: the
         same shuffles of window.rows (same consumption of torch's RNG), the same batch boundaries, padded ragged batch,
         eager first steps and captured step -- only that a batch is built from the packed positions by the window's
@@ -143,9 +146,14 @@ class Trainer:
         if window.device != mine:
             raise ValueError("the window lives on %s, the trainer on %s" % (window.device, self.device))
         with torch.cuda.device(self.device):
-            return self._train(_WindowBatches(window), generator)
+            return self._train(_WindowBatches(window), generator, stats)
 
-    def _train(self, batches, generator):
+    def _train(self, batches, generator, stats=False):
+        self.epoch_stats = []
+        ds, snaps = None, []
+        if stats:       # a pure observer of the step's xv, xp, v, p; without it nothing below differs from the plain step
+            from .stats import CombinedStats, DeviceStats
+            ds = DeviceStats(self.device) if self.device.type == "cuda" else CombinedStats()
         n = batches.rows
         bs = self.config.batch_size
         self.net.train()
@@ -160,7 +168,7 @@ class Trainer:
                 k = int(idx.shape[0])
                 if k == bs and want_graph:
                     if graph is None and eager_full >= 2:      # (the first steps run eagerly: momentum buffers, MIOpen's choices)
-                        graph, sidx, sloss = self._capture_step(batches)
+                        graph, sidx, sloss = self._capture_step(batches, ds)
                     if graph is not None:
                         sidx.copy_(idx)
                         graph.replay()
@@ -171,30 +179,43 @@ class Trainer:
                 if pad:   # DataLoader's drop_last=False batch (model.py:208-212), at the full batch's shape
                     idx = torch.cat([idx, idx[:1].expand(bs - k)])
                     self._set_valid_rows(k)
-                last = self._eager_step(*batches(idx), k if pad else None)
+                last = self._eager_step(*batches(idx), k if pad else None, ds)
                 if pad:
                     self._set_valid_rows(None)
+            if ds is not None and self.device.type == "cuda":     # the epoch's statistics stay on the device for now
+                snaps.append(ds.snapshot())
+                ds.reset()
+            elif ds is not None:
+                self.epoch_stats.append(ds)
+                ds = type(ds)()
         last = None if last is None else float(last)
+        if snaps:
+            self.epoch_stats = ds.read(snaps)
         del graph
         self.optimiser.zero_grad()            # (gradients that live in a graph's pool are not kept)
         self.scheduler.step()       # once per generation (model.py:239)
         self.net.eval()
         return last
 
-    def _eager_step(self, b, v, p, k=None):
+    def _eager_step(self, b, v, p, k=None, ds=None):
         """model.py:214-230 for one batch (its first k rows when the batch is a padded ragged one).  Returns the detached
         loss (read back once, after the last batch: no host synchronisation per step); nothing of the step's autograd graph
         outlives the call -- a graph captured later must not find AccumulateGrad nodes bound to this stream."""
         self.optimiser.zero_grad()
         xv, xp = self.net(b)
+        if ds is not None and self.device.type == "cuda":
+            ds.update(xv.detach(), v, xp.detach(), p, valid_rows=k)
         if k is not None:
             xv, xp, v, p = xv[:k], xp[:k], v[:k], p[:k]
-        loss = self.value_loss(xv, v) + self.prior_loss(xp, p)   # model.py:221-225
+        vloss, ploss = self.value_loss(xv, v), self.prior_loss(xp, p)
+        loss = vloss + ploss   # model.py:221-225
         loss.backward()
         self.optimiser.step()
+        if ds is not None and self.device.type != "cuda":     # model.py:228-234, on the host classes
+            ds.update(xv.detach().numpy(), v.numpy(), vloss.detach(), xp.detach().numpy(), p.numpy(), ploss.detach())
         return loss.detach()
 
-    def _capture_step(self, batches):
+    def _capture_step(self, batches, ds=None):
         """One full-batch train step -- gather by a static index tensor, forward, loss, backward, SGD -- captured as a HIP
         graph (torch.cuda.graph): replayed per batch with the batch's indices copied into `sidx`.  Same kernels, same order,
         same arithmetic as the eager step."""
@@ -205,11 +226,68 @@ class Trainer:
         with torch.cuda.graph(graph):
             b, v, p = batches(sidx, out)
             xv, xp = self.net(b)
+            if ds is not None:      # two more launches of the captured step
+                ds.update(xv.detach(), v, xp.detach(), p)
             loss = self.value_loss(xv, v) + self.prior_loss(xp, p)
             loss.backward()
             self.optimiser.step()
             sloss = loss.detach()
         return graph, sidx, sloss
+
+    # -- test-set scores (model.py:180-198, 307-342) ---------------------------------------------------------------------
+    def evaluate(self, data, batch_size=4096, shuffle=True):
+        """ModelWrapper.evaluate: this trainer's net in eval mode over a labelled set -- a stats.LabelledSet or a
+        (boards F32[n,3,6,7], values F32[n], priors F32[n,7]) tuple --, batches drawn as the reference's DataLoader draws
+        them (same consumption of torch's RNG) and forwarded by PyTorch.  On a GPU the outputs go to a DeviceStats and
+        are read back once; on a CPU trainer the host classes are fed as the reference feeds its own.  Returns a
+        CombinedStats."""
+        return self._evaluate(data, batch_size, shuffle, True)
+
+    def evaluate_value_only(self, data):
+        """ModelWrapper.evaluate_value_only (model.py:192-198): the value half, batches of 4096.  Returns a ValueStats."""
+        return self._evaluate(data, 4096, True, False)
+
+    def _evaluate(self, data, batch_size, shuffle, with_priors):
+        from .stats import CombinedStats, DeviceStats, LabelledSet, ValueStats
+        if isinstance(data, LabelledSet):
+            if data.device.type != self.device.type:
+                raise ValueError("the labelled set lives on %s, the trainer on %s" % (data.device, self.device))
+            data = (data.planes(), data.values, data.priors)
+        boards, values = data[0].to(self.device), data[1].to(self.device)
+        priors = data[2].to(self.device) if len(data) > 2 and data[2] is not None else None
+        if with_priors and priors is None:
+            raise ValueError("evaluate needs a set with priors; use evaluate_value_only")
+        n = int(boards.shape[0])
+        on_gpu = self.device.type == "cuda"
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            with torch.no_grad():
+                order = dataloader_permutation(n).to(self.device) if shuffle else torch.arange(n, device=self.device)
+                if on_gpu:
+                    with torch.cuda.device(self.device):
+                        out = DeviceStats(self.device, with_priors=with_priors)
+                        for i in range(0, n, batch_size):
+                            idx = order[i:i + batch_size]
+                            xv, xp = self.net(boards[idx])
+                            if with_priors:
+                                out.update(xv.contiguous(), values[idx], xp.contiguous(), priors[idx])
+                            else:
+                                out.update(xv.contiguous(), values[idx])
+                        return out.read()
+                out = CombinedStats() if with_priors else ValueStats()
+                for i in range(0, n, batch_size):
+                    idx = order[i:i + batch_size]
+                    xv, xp = self.net(boards[idx])
+                    v = values[idx]
+                    if with_priors:     # model.py:318-326: the losses go in as tensors
+                        p = priors[idx]
+                        out.update(xv.numpy(), v.numpy(), self.value_loss(xv, v), xp.numpy(), p.numpy(), self.prior_loss(xp, p))
+                    else:               # model.py:337-341: loss.item()
+                        out.update(xv.numpy(), v.numpy(), self.value_loss(xv, v).item())
+                return out
+        finally:
+            self.net.train(was_training)
 
     def state(self):
         """The checkpoint dict of save() with CPU tensors (model.py:242-250)."""

@@ -505,6 +505,50 @@ long long c4_conv3x3_wrw_workspace_floats(void);
 int c4_conv3x3_wrw(const float *x_dev, const float *dy_dev, float *dweight_dev, float *workspace_dev, int rows, int channels, int height, int width,
                    void *hip_stream);
 
+/* ---- value and policy statistics (c4_train.hip; the reference: neural/stats.py) ---------------------------------------
+ * ValueStats.update / PriorStats.update (stats.py:53-71, 99-113) on device tensors: what ModelWrapper.train(print_stats=True)
+ * feeds per batch (model.py:228-234) and what evaluate / evaluate_value_only accumulate over a labelled set
+ * (model.py:180-198, 307-342), without the .cpu() round trip per batch.  Row by row, as the reference:
+ *   category of an output  floorf(x * 3.0f) / 2.0f in float32 (stats.py:67-71); a row with label k in {0, 0.5, 1} counts in
+ *                          total[2k] and, when its category equals the label, in correct[2k] (an output of exactly 1.0f is
+ *                          category 1.5: never correct); any other label counts in n only;
+ *   policy                 correct when the first index of the largest output (np.argmax) is among the indices where the
+ *                          label row equals its maximum (stats.py:103-113);
+ *   losses                 the reference adds batch_mean_loss * len(batch) (stats.py:56, 101) = the sum of the row losses;
+ *                          these are accumulated directly: (x - y)^2 per value row, and per policy row the sum over 7 of
+ *                          -(y * max(log x, -100) + (1 - y) * max(log(1 - x), -100)) (torch.nn.BCELoss), formed in float64;
+ *                          PriorStats.loss = prior_bce_sum / (7 * prior_n);
+ *   smallest / largest     min / max of the outputs; +inf / -inf after a reset -- the reference's starting values 1.0 / 0.0
+ *                          (stats.py:9-10) are applied by the reader, as min(1.0, .) / max(0.0, .) do there;
+ *   non_finite             rows with a NaN / inf value output, a value output or label beyond +-1024 (the net's outputs lie
+ *                          in [0, 1]; larger terms would not fit the integer sums), or a policy output outside [0, 1];
+ *                          they add nothing to the sums, and whatever else is reported for such a batch is unspecified.
+ * Each row's three float64 terms are rounded to a fixed binary grid (2^-36 for the output and the squared error, 2^-32 for
+ * the BCE row) and added as integers: the result does not depend on the launch grid, on dispatch order or on how the rows
+ * are split over calls, bit for bit, while a sum stays below 2^53 grid units (sum_outputs, value_sq_err_sum: 131,072, i.e.
+ * some 260,000 rows at a mean output of 0.5; prior_bce_sum: 2,097,152); beyond that -- an epoch over a large window --
+ * the doubles round as float64 sums do: still deterministic for a given sequence of calls, no longer independent of the
+ * split.  c4_score_update_dev adds the first valid_rows (0..rows) of `rows` rows to *acc_dev: two
+ * launches on hip_stream (workgroup partials into workspace_dev -- c4_score_workspace_bytes(rows) bytes --, then one
+ * workgroup adds them up: integers and min / max, in no particular order); allocates nothing, waits for nothing, capturable in a HIP graph.  All pointers are
+ * device pointers; x_prior / y_prior float32 [rows][7], both NULL = the value-only form (prior_n stays); rows <= 0, one prior
+ * pointer without the other, or valid_rows outside [0, rows]: C4_EINVAL.  Messages: c4_score_last_error().
+ * (Additions like these leave C4_ABI_VERSION alone: it changes when an existing struct or signature does.) */
+typedef struct {                 /* 112 bytes, all fields naturally aligned */
+    int64_t n;                   /* rows seen (ValueStats.n) */
+    int64_t total[3], correct[3];/* labels == 0.0 / 0.5 / 1.0, and of those the rows categorised alike (stats.py:62-65) */
+    int64_t prior_n, prior_correct;
+    int64_t non_finite;
+    double  sum_outputs, value_sq_err_sum, prior_bce_sum;   /* average_value, total_loss of ValueStats / PriorStats */
+    float   smallest, largest;
+} c4_score_acc;
+long long c4_score_workspace_bytes(long long rows);
+int c4_score_reset_dev(int device, void *hip_stream, c4_score_acc *acc_dev);
+int c4_score_update_dev(int device, void *hip_stream, const float *x_value, const float *y_value,
+                        const float *x_prior /* [rows][7] or NULL */, const float *y_prior /* or NULL */,
+                        long long rows, long long valid_rows, c4_score_acc *acc_dev, void *workspace_dev);
+const char *c4_score_last_error(void);
+
 int c4_abi_version(void);
 
 #ifdef __cplusplus

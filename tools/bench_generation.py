@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--generations", type=int, default=0,
                     help="N > 0: run N generations with run_generations (device-resident window) and print per-generation timings; "
                          "with --out pointing at a directory written earlier the run resumes it")
+    ap.add_argument("--train-stats", type=int, default=0,
+                    help="1: keep the reference's per-epoch training statistics (Trainer.train(stats=True): two more launches per step)")
     a = ap.parse_args()
     if a.generations < 0:
         ap.error("--generations must be >= 0")
@@ -58,7 +60,7 @@ def main():
         torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
         window, losses = run_generations(tr, MCTSConfig.self_play(a.sims), a.games, out, a.generations, n_slots=a.slots,
-                                         write_games_pkl=bool(a.games_pkl), timings=per_gen)
+                                         write_games_pkl=bool(a.games_pkl), timings=per_gen, train_stats=bool(a.train_stats))
         torch.cuda.synchronize()
         total = time.perf_counter() - t0
         for t, loss in zip(per_gen, losses):
@@ -72,7 +74,7 @@ def main():
     timings = {}
     t0 = time.perf_counter()
     games, loss = run_generation(tr, MCTSConfig.self_play(a.sims), n_games=a.games, save_dir=out, gen=0, n_slots=a.slots,
-                                 write_games_pkl=bool(a.games_pkl), timings=timings)
+                                 write_games_pkl=bool(a.games_pkl), timings=timings, train_stats=bool(a.train_stats))
     torch.cuda.synchronize()
     total = time.perf_counter() - t0
     res = {"workload": "one GPU's share of BASELINE config 5: %d self-play games at %d sims/move on %d slots, export + data.pth "
@@ -82,6 +84,10 @@ def main():
            "train_and_checkpoint_s": timings["train_s"], "games_per_s_end_to_end": a.games / total,
            "games_per_s_selfplay": a.games / timings["selfplay_and_gather_s"], "last_loss": loss,
            "data_pth_bytes": os.path.getsize(os.path.join(out, "0", "data.pth"))}
+    steps = tr.config.n_training_epochs * -(-timings["training_rows"] // tr.config.batch_size)
+    res.update(train_stats=bool(a.train_stats), train_steps=steps, train_and_checkpoint_ms_per_step=timings["train_s"] / steps * 1e3)
+    if a.train_stats:
+        res["last_epoch_stats"] = repr(tr.epoch_stats[-1])
     print(json.dumps(res))
 
 
