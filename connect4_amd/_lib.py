@@ -21,6 +21,7 @@ PLANES_F32, PLANES_F16, PLANES_BF16 = 0, 1, 2
 SLOT_ACTIVE, SLOT_PARKED, SLOT_MOVE_DONE = 0, 1, 2
 PRIOR_NONE, PRIOR_F32, PRIOR_F64 = 0, 1, 2
 PV_VALUE, PV_VISITS = 0, 1
+NET_F16, NET_F32X3, NET_F32X3_WIDE = 0, 1, 2   # c4_net_desc.precision
 
 
 class EngineError(RuntimeError):

@@ -1898,6 +1898,10 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
     __shared__ uint32_t s_simd[4];     // waves seen per SIMD (role assignment)
     __shared__ uint8_t s_perm[TW * SPW];   // the slot a (tree wave, group) pair walks (0xff: none), see the launch prologue
     __shared__ uint32_t s_tree_done;   // tree waves past the deadline
+    // (the 64-filter reference-precision planes are 24,768 B per network wave: four of them, 99 KB, next to everything above)
+    static_assert(sizeof(act) + sizeof(mlp) + sizeof(smem) + sizeof(s_val) + sizeof(s_pri) + sizeof(s_stats) + sizeof(s_bias) + sizeof(s_tab16) +
+                  sizeof(s_w0) + sizeof(s_path) + sizeof(s_l1) + sizeof(s_req) + sizeof(s_simd) + sizeof(s_perm) + 64 <= 160 * 1024,
+                  "the split kernel's LDS must fit a CU's 160 KiB");
     // slot p of this workgroup.  Dense: TS consecutive slots per workgroup.  Spread (fewer slots than TS per CU): slot
     // blockIdx.x + p * gridDim.x, so that a batch smaller than TS x CUs still puts work on EVERY CU (1,200 games -- the
     // reference's generation, config.py:64 -- are 4-5 slots on each of 256 CUs instead of 16 slots on 75 of them).
@@ -1934,7 +1938,7 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
     for (int i = threadIdx.x; i < MLP_F4; i += NTHREADS) mlp[i] = nd.mlp[i];
     stage_bias_lds(nd, s_bias);
     if (W0Lds<MODE>::FRAGS > 1) stage_w0_lds(nd, s_w0);
-    if (threadIdx.x < 64) build_tab16<MODE == NETMODE_F64 ? CS64 : CS16>(s_tab16, threadIdx.x);
+    if (threadIdx.x < 64) build_tab16<WaveRow<MODE>::CS>(s_tab16, threadIdx.x);
     for (int i = threadIdx.x; i < TS * MAX_DEPTH; i += NTHREADS) {   // paths of leaves pending from the previous launch
         const int p = i / MAX_DEPTH, k = i - p * MAX_DEPTH;
         if (gslot(p) < d.G) s_path[p][k] = d.path[(size_t)gslot(p) * MAX_DEPTH + k];
@@ -2888,7 +2892,16 @@ int c4_selfplay_steps(c4_engine *e, c4_net *net, float *values_dev, float *prior
         } else if (e->fused_slots == 32) hipLaunchKernelGGL((c4_selfplay_wave_kernel<32, MODE>), g32, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps); \
         else hipLaunchKernelGGL((c4_selfplay_wave_kernel<16, MODE>), g16, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps); \
     } while (0)
-        if (nd.mode == c4net::NETMODE_F64) C4_LAUNCH_WAVE(c4net::NETMODE_F64);
+        if (nd.mode == c4net::NETMODE_F64_PRECISE) {
+            // 24,768 B of planes per network wave: four network waves (99 KB) fit next to the tree state, eight forwards per
+            // workgroup (the wave-autonomous kernel) do not.  Four tree waves and four network waves at 16 and at 32 slots.
+            if (e->fused_wave != 2) {
+                set_err(e->err, "C4_FUSED_MODE=wave cannot hold the 64-filter reference-precision net (eight waves' planes exceed a CU's LDS); use the default split kernel");
+                return C4_ESTATE;
+            }
+            if (e->fused_slots == 32) C4_LAUNCH_SPLIT(32, c4net::NETMODE_F64_PRECISE, 4);
+            else C4_LAUNCH_SPLIT(16, c4net::NETMODE_F64_PRECISE, 4);
+        } else if (nd.mode == c4net::NETMODE_F64) C4_LAUNCH_WAVE(c4net::NETMODE_F64);
         else if (nd.mode == c4net::NETMODE_F32_PRECISE) C4_LAUNCH_WAVE(c4net::NETMODE_F32_PRECISE);
         else C4_LAUNCH_WAVE(c4net::NETMODE_F32_F16);
 #undef C4_LAUNCH_WAVE

@@ -26,7 +26,8 @@
 // workgroup-synchronous self-play kernel) and the wave-private forwards on 16-row MFMA tiles -- one wave = one position,
 // private LDS planes, weights streamed from L2 into registers, no workgroup barrier: net_forward_wave16 (32 filters, fp16;
 // bit-identical to the block forward; c4_net_forward_wave and the self-play kernels), net_forward_wave16q (32 filters,
-// reference precision), net_forward_wave16w (64 filters).  All live in c4_net_dev.h.
+// reference precision), net_forward_wave16w (64 filters), net_forward_wave16x (64 filters, reference precision).  All live
+// in c4_net_dev.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -75,6 +76,31 @@ __global__ __launch_bounds__(NTHREADS) void c4_net_wave1_kernel(NetDev nd, const
     if (p >= n) return;
     if (wv >= active_waves) return;                       // diagnostic (C4_NET_WAVE_ACTIVE): fewer waves per CU
     net_forward_wave1_mode<MODE>(nd, &act[wv][0], mlp, s_bias, s_tab, c0[p], c1[p], values, priors, p, nd.w0,   /* (eight waves' planes fill this kernel's LDS: the pass-start fragments come from L2 here) */
+                                 (nd.stamps && blockIdx.x == 0) ? nd.stamps + wv * 16 : nullptr);
+}
+
+// The 64-filter reference-precision forward (net_forward_wave16x) needs 24,768 B of planes per wave: eight waves' planes
+// (198 KB) exceed a CU's 160 KiB, so this mode runs FOUR waves per workgroup (99 KB).  As above, both entry points run it.
+constexpr int XWAVES = 4;
+__global__ __launch_bounds__(XWAVES * 64) void c4_net_wave1x_kernel(NetDev nd, const uint64_t *__restrict__ c0,
+                                                                    const uint64_t *__restrict__ c1, int n,
+                                                                    float *__restrict__ values, float *__restrict__ priors, int active_waves)
+{
+    constexpr int MODE = NETMODE_F64_PRECISE;
+    __shared__ __attribute__((aligned(16))) _Float16 act[XWAVES][WaveBuf<MODE>::HALVES];
+    __shared__ __attribute__((aligned(16))) float4 mlp[MLP_F4];
+    __shared__ __attribute__((aligned(16))) float s_bias[BIAS_LDS_FLOATS];
+    __shared__ __attribute__((aligned(16))) uint16_t s_tab[64 * TAB16];
+    static_assert(sizeof(act) + sizeof(mlp) + sizeof(s_bias) + sizeof(s_tab) <= 160 * 1024, "the four waves' planes must fit a CU's LDS");
+    for (int i = threadIdx.x; i < MLP_F4; i += XWAVES * 64) mlp[i] = nd.mlp[i];
+    for (int i = threadIdx.x; i < 64 * (1 + 2 * nd.n_res); i += XWAVES * 64) s_bias[i] = i < 64 ? nd.stem_b[i] : nd.conv_b[i - 64];   // (stage_bias_lds strides by eight waves)
+    if (threadIdx.x < 64) build_tab16<WaveRow<MODE>::CS>(s_tab, threadIdx.x);
+    __syncthreads();
+    const int wv = threadIdx.x >> 6;
+    const int p = blockIdx.x * XWAVES + wv;
+    if (p >= n) return;
+    if (wv >= active_waves) return;                       // diagnostic (C4_NET_WAVE_ACTIVE): fewer waves per CU
+    net_forward_wave1_mode<MODE>(nd, &act[wv][0], mlp, s_bias, s_tab, c0[p], c1[p], values, priors, p, nd.w0,
                                  (nd.stamps && blockIdx.x == 0) ? nd.stamps + wv * 16 : nullptr);
 }
 
@@ -141,13 +167,18 @@ int c4_net_create(int device, const c4_net_desc *desc, c4_net **out)
                  "(got channels=%d filters=%d residuals=%d)", desc->channels, desc->filters, desc->n_residuals);
         return C4_EINVAL;
     }
-    if (desc->precision != C4_NET_F16 && desc->precision != C4_NET_F32X3) {
+    if (desc->precision != C4_NET_F16 && desc->precision != C4_NET_F32X3 && desc->precision != C4_NET_F32X3_WIDE) {
         snprintf(n_err, 512, "c4_net_create: unknown precision %d", desc->precision);
         return C4_EINVAL;
     }
     if (FW != 32 && desc->precision == C4_NET_F32X3) {
-        snprintf(n_err, 512, "c4_net_create: the reference-precision forward is offered for 32 filters only "
-                 "(the hi/lo planes of %d filters do not fit a wave's private LDS)", FW);
+        snprintf(n_err, 512, "c4_net_create: C4_NET_F32X3 is the 32-filter reference-precision forward; at %d filters ask for "
+                 "C4_NET_F32X3_WIDE (precision \"f32x3w\")", FW);
+        return C4_EINVAL;
+    }
+    if (FW != 64 && desc->precision == C4_NET_F32X3_WIDE) {
+        snprintf(n_err, 512, "c4_net_create: C4_NET_F32X3_WIDE is the 64-filter reference-precision forward; at %d filters ask for "
+                 "C4_NET_F32X3 (precision \"f32x3\")", FW);
         return C4_EINVAL;
     }
     // the folded conv weights are stored in fp16 (the hi parts in C4_NET_F32X3): one beyond +-65504 would become inf and,
@@ -258,6 +289,18 @@ int c4_net_create(int device, const c4_net_desc *desc, c4_net **out)
                     conv16p[((T * 4 + 2 * ct) * 64 * 8) + e] = conv16[((T * 2 + ct) * 64 * 8) + e];
                     conv16p[((T * 4 + 2 * ct + 1) * 64 * 8) + e] = conv16l[((T * 2 + ct) * 64 * 8) + e];
                 }
+    } else if (FW == 64 && R > 0 && desc->precision == C4_NET_F32X3_WIDE) {
+        // the 64-filter tower as one linear stream for net_forward_wave16x, in the order a pass consumes it: a layer runs as two
+        // cout halves c, each over all 18 (tap, k-step) units u: [(L * 2 + c) * 18 + u][ct 2c hi | ct 2c lo | ct 2c+1 hi | ct 2c+1 lo][64][8]
+        conv16p.resize((size_t)2 * R * 2 * 18 * 4 * 64 * 8);
+        for (size_t L = 0; L < (size_t)2 * R; ++L)
+            for (int c = 0; c < 2; ++c)
+                for (int u = 0; u < 18; ++u)
+                    for (int ct = 0; ct < 2; ++ct) {
+                        const size_t src = ((L * 18 + u) * 4 + 2 * c + ct) * 64 * 8, dst = (((L * 2 + c) * 18 + u) * 4 + 2 * ct) * 64 * 8;
+                        std::copy(conv16.begin() + src, conv16.begin() + src + 64 * 8, conv16p.begin() + dst);
+                        std::copy(conv16l.begin() + src, conv16l.begin() + src + 64 * 8, conv16p.begin() + dst + 64 * 8);
+                    }
     } else conv16p.resize(8);
     // ... and what a pass needs first, in the order of c4net::W0_*: stem hi (4 fragments), stem lo (4), heads hi, heads lo, tower taps 0 and 1
     std::vector<_Float16> w0v((size_t)W0_FRAGS * 64 * 8, (_Float16)0.0f);
@@ -318,9 +361,9 @@ int c4_net_create(int device, const c4_net_desc *desc, c4_net **out)
     net->d.w1 = desc->w1;
     net->d.w2 = desc->w2;
     net->d.n_res = R;
-    net->d.precise = desc->precision == C4_NET_F32X3 ? 1 : 0;
+    net->d.precise = desc->precision != C4_NET_F16 ? 1 : 0;
     net->d.filters = FW;
-    net->d.mode = FW == 64 ? NETMODE_F64 : (net->d.precise ? NETMODE_F32_PRECISE : NETMODE_F32_F16);
+    net->d.mode = FW == 64 ? (net->d.precise ? NETMODE_F64_PRECISE : NETMODE_F64) : (net->d.precise ? NETMODE_F32_PRECISE : NETMODE_F32_F16);
     if (getenv("C4_NET_STAMPS")) {
         void *q = nullptr;
         if (hipMalloc(&q, 8 * 16 * sizeof(unsigned long long)) == hipSuccess) {
@@ -374,6 +417,16 @@ int c4_net_forward_wave(c4_net *net, void *hip_stream, const uint64_t *color0_de
     if (n == 0) return C4_OK;
     const char *ea16 = getenv("C4_NET_WAVE_ACTIVE");   // timing experiments only: fewer waves per CU
     const int active = ea16 ? atoi(ea16) : NWAVES;
+    if (net->d.mode == NETMODE_F64_PRECISE) {
+        hipLaunchKernelGGL(c4_net_wave1x_kernel, dim3((n + XWAVES - 1) / XWAVES), dim3(XWAVES * 64), 0, (hipStream_t)hip_stream, net->d,
+                           color0_dev, color1_dev, (int)n, values_dev, priors_dev, active);
+        hipError_t xr = hipGetLastError();
+        if (xr != hipSuccess) {
+            snprintf(n_err, 512, "c4_net_wave1x_kernel launch failed: %s", hipGetErrorString(xr));
+            return C4_EDEVICE;
+        }
+        return C4_OK;
+    }
     if (net->d.mode != NETMODE_F32_F16) {
         const dim3 g1((n + NWAVES - 1) / NWAVES), b1(NTHREADS);
         if (net->d.mode == NETMODE_F64)

@@ -439,6 +439,7 @@ __device__ __forceinline__ void net_forward_block(const NetDev &nd, const NetLds
 //   net_forward_wave16n<NP>     32 filters, fp16 storage: the self-play kernels' hot forward, NP positions per pass
 //   net_forward_wave16q         32 filters, reference precision (fp16 hi + lo split)
 //   net_forward_wave16w         64 filters, fp16 storage
+//   net_forward_wave16x         64 filters, reference precision, a layer in two cout halves
 // (Earlier rounds had forwards on 32-row tiles -- two positions per pass, then one position in two half-empty tiles:
 // 22-27 k cycles per pass at 32 filters where the 16-row forward takes 17-20 k; retired.)
 // ------------------------------------------------------------------------------------------------
@@ -1378,11 +1379,299 @@ __device__ __forceinline__ void net_forward_wave16w(const NetDev &nd, _Float16 *
     stamp(10);
 }
 
+// ------------------------------------------------------------------------------------------------
+// net_forward_wave16x: the 64-filter net in reference precision (C4_NET_F32X3_WIDE): the hi/lo arithmetic of
+// net_forward_wave16q on the geometry of net_forward_wave16w -- 9 taps x 2 k-steps x 4 cout tiles x 3 row tiles x 3 = 648
+// MFMAs of 16 cycles per layer, four planes (ping/pong x hi/lo) of 43 rows x 144 bytes = 24,768 B per wave.
+// Twelve accumulator tiles twice over plus hi and lo weight windows do not fit next to the tree code, so a layer runs as
+// TWO COUT HALVES: half c computes cout tiles 2c and 2c + 1 over all 18 (tap, k-step) units -- 2 cout tiles x 3 row tiles
+// x 2 accumulators, the register picture and the k-loop of net_forward_wave16q with 18 units in place of its 9 taps.  The
+// source planes are read once per half; the skip of half c reads, and its epilogue overwrites, channels 32c .. 32c + 31 of
+// the destination planes only, so the second half still finds its block input.  The tower's weights are one linear stream
+// (conv_w16p) in exactly the order the pass consumes them: [layer][half][unit][ct hi | ct lo | ct+1 hi | ct+1 lo], read
+// with buffer loads through the rolling window of three units.  The stem, the heads and the tower's first two units are
+// requested from L2 at the start of the pass (a round trip of ~2 k cycles in a pass of ~100 k: no LDS is kept for them).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void net_forward_wave16x(const NetDev &nd, _Float16 *buf, const float4 *mlp, const float *bias_lds,
+                                                    const uint16_t *tab, uint64_t b0, uint64_t b1, float *__restrict__ values,
+                                                    float *__restrict__ priors, int out, unsigned long long *stamps = nullptr)
+{
+    constexpr int FW = 64;
+    int lane_ = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane_));     // keep lane-derived addresses out of a persistent caller's loop (see net_forward_wave16)
+    const int lane = lane_;
+    const int n = lane & 15, g = lane >> 4;
+    auto stamp = [&](int i) { if (stamps && lane == 0) stamps[i] = __builtin_amdgcn_s_memtime(); };
+    stamp(0);
+    _Float16 *const p0h = buf, *const p0l = buf + PLANE64, *const p1h = buf + 2 * PLANE64, *const p1l = buf + 3 * PLANE64;
+    const __amdgpu_buffer_rsrc_t wr = wq_rsrc(nd);
+    const int voff = lane * 16;
+    // rolling weight window, slot = unit % 3 (18 units per half layer: the slot of a unit is the same in every half);
+    // units 0 and 1 of the tower are requested here, slot 2 by the first unit (a request past the end of the stream returns zeros)
+    half8 wh[WTAPS][2], wl[WTAPS][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            wh[t][ct] = wq_load(wr, voff + (2 * ct) * 1024, t * 4096);
+            wl[t][ct] = wq_load(wr, voff + (2 * ct + 1) * 1024, t * 4096);
+        }
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) { wh[2][ct] = wh[0][ct]; wl[2][ct] = wl[0][ct]; }
+    int soff = 2 * 4096;                // stream offset of the unit the NEXT refill requests
+    const float hb0 = nd.head_b[0], hb1 = nd.head_b[1], hb2 = nd.head_b[2];
+    uint32_t tb[TAB16 / 2];
+    {
+        const uint4 *t4 = reinterpret_cast<const uint4 *>(tab + lane * TAB16);
+#pragma unroll
+        for (int i = 0; i < TAB16 / 8; ++i) { const uint4 v = t4[i]; tb[4 * i] = v.x; tb[4 * i + 1] = v.y; tb[4 * i + 2] = v.z; tb[4 * i + 3] = v.w; }
+    }
+    auto tof = [&](int idx) -> int { return (int)((tb[idx >> 1] >> (16 * (idx & 1))) & 0xffffu); };
+    // input planes (board.py:147-154), 4 halves per row, at the start of p1h (the tower writes it only after the stem)
+    _Float16 *inp = p1h;
+    if (lane <= PIX) {
+        half4 v = {};
+        if (lane < PIX) {
+            const int y = lane / 7, x = lane - y * 7;
+            const int bit = x * 7 + (5 - y);
+            v[0] = (_Float16)((__popcll(b0 | b1) & 1) ? 0.0f : 1.0f);
+            v[1] = (_Float16)(float)((b0 >> bit) & 1);
+            v[2] = (_Float16)(float)((b1 >> bit) & 1);
+        }
+        *reinterpret_cast<half4 *>(inp + lane * 4) = v;   // lane == PIX: the zero row of the planes
+    }
+    for (int i = lane; i < CS64; i += 64) {
+        p0h[PIX * CS64 + i] = (_Float16)0.0f; p0l[PIX * CS64 + i] = (_Float16)0.0f;
+        p1h[PIX * CS64 + i] = (_Float16)0.0f; p1l[PIX * CS64 + i] = (_Float16)0.0f;
+    }
+    bool real[RT16];
+    int rbase[RT16];
+#pragma unroll
+    for (int rt = 0; rt < RT16; ++rt) {
+        real[rt] = 16 * rt + n < PIX;
+        rbase[rt] = (real[rt] ? 16 * rt + n : PIX) * CS64;
+    }
+    auto bias4 = [&](const float *b, int ct) -> floatx4 {
+        const float4 v = *reinterpret_cast<const float4 *>(b + 16 * ct + 4 * g);
+        return floatx4{v.x, v.y, v.z, v.w};
+    };
+    const floatx4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+    // ------------------------------------------------------------------ stem (0/1 inputs: two MFMAs per step), by cout half
+#pragma unroll 1
+    for (int ch = 0; ch < 2; ++ch) {
+        half8 swh[2][2], swl[2][2];     // [k-step][cout tile of the half]
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+                swh[s][ct] = nd.stem_w16[(s * 4 + 2 * ch + ct) * 64 + lane];
+                swl[s][ct] = nd.stem_w16l[(s * 4 + 2 * ch + ct) * 64 + lane];
+            }
+        floatx4 ah[RT16][2], al[RT16][2];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            const floatx4 bv = bias4(bias_lds + 32 * ch, ct);
+#pragma unroll
+            for (int rt = 0; rt < RT16; ++rt) { ah[rt][ct] = bv; al[rt][ct] = zero4; }
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int rt = 0; rt < RT16; ++rt) {
+                const half4 va = *reinterpret_cast<const half4 *>(inp + tof(27 + rt * 4 + s * 2));
+                const half4 vb = *reinterpret_cast<const half4 *>(inp + tof(27 + rt * 4 + s * 2 + 1));
+                half8 bf;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { bf[j] = va[j]; bf[4 + j] = vb[j]; }
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+                    ah[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(swh[s][ct], bf, ah[rt][ct], 0, 0, 0);
+                    al[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(swl[s][ct], bf, al[rt][ct], 0, 0, 0);
+                }
+            }
+#pragma unroll
+        for (int rt = 0; rt < RT16; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) store16q(ah[rt][ct], al[rt][ct], p0h, p0l, rbase[rt] + 32 * ch + 16 * ct + 4 * g, real[rt]);
+    }
+    stamp(1);
+    // ------------------------------------------------------------------ residual tower
+    // one conv layer; `second` is a compile-time constant (plane addresses are immediates), the cout half a run-time loop
+    // (its offset of 32 channels enters the bias, skip and store addresses only)
+    auto layer = [&](auto second_tag, const int L) {
+        constexpr bool second = decltype(second_tag)::value;
+        const _Float16 *sh = second ? p1h : p0h, *sl = second ? p1l : p0l;
+        _Float16 *dh = second ? p0h : p1h, *dl = second ? p0l : p1l;
+#pragma unroll 1
+        for (int ch = 0; ch < 2; ++ch) {
+            floatx4 ah[RT16][2], al[RT16][2];
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+                const floatx4 bv = bias4(bias_lds + FW * (1 + L) + 32 * ch, ct);
+#pragma unroll
+                for (int rt = 0; rt < RT16; ++rt) { ah[rt][ct] = bv; al[rt][ct] = zero4; }
+            }
+            half8 bh[RT16], bl[RT16], nh[RT16], nl[RT16];
+#pragma unroll
+            for (int rt = 0; rt < RT16; ++rt) {
+                bh[rt] = *reinterpret_cast<const half8 *>(sh + tof(rt * 9));
+                bl[rt] = *reinterpret_cast<const half8 *>(sl + tof(rt * 9));
+            }
+#if C4_F32X3_SGB
+            __builtin_amdgcn_sched_barrier(0);   // the group barriers below order the k-loop's own reads: the first unit's stay in front of it
+#endif
+#pragma unroll
+            for (int u = 0; u < 18; ++u) {   // unit u = (tap u / 2, k-step u % 2)
+                {   // refill: the slot the PREVIOUS unit used gets the unit two ahead of this one
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) {
+                        wh[(u + 2) % WTAPS][ct] = wq_load(wr, voff + (2 * ct) * 1024, soff);
+                        wl[(u + 2) % WTAPS][ct] = wq_load(wr, voff + (2 * ct + 1) * 1024, soff);
+                    }
+                    soff += 4096;
+                }
+                if (u + 1 < 18) {
+#pragma unroll
+                    for (int rt = 0; rt < RT16; ++rt) {
+                        nh[rt] = *reinterpret_cast<const half8 *>(sh + tof(rt * 9 + (u + 1) / 2) + 32 * ((u + 1) % 2));
+                        nl[rt] = *reinterpret_cast<const half8 *>(sl + tof(rt * 9 + (u + 1) / 2) + 32 * ((u + 1) % 2));
+                    }
+                }
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+                    const half8 cwh = wh[u % WTAPS][ct], cwl = wl[u % WTAPS][ct];
+#pragma unroll
+                    for (int rt = 0; rt < RT16; ++rt) {
+                        ah[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cwh, bh[rt], ah[rt][ct], 0, 0, 0);
+                        al[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cwl, bh[rt], al[rt][ct], 0, 0, 0);
+                        al[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cwh, bl[rt], al[rt][ct], 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int rt = 0; rt < RT16; ++rt) { bh[rt] = nh[rt]; bl[rt] = nl[rt]; }
+#if C4_F32X3_SGB
+                // this unit's instruction order (as net_forward_wave16q's tap): the four weight requests behind the first
+                // MFMAs, then one operand read of the next unit per two MFMAs
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
+                if (u + 1 < 18) {
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
+                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                } else {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 14, 0);
+                }
+#endif
+            }
+#if C4_F32X3_SGB
+            __builtin_amdgcn_sched_barrier(0);
+#endif
+            if (second) {   // + block input (lives in dh/dl): the half's 32 channels are k-step ch of the destination rows; identity
+                            // MFMAs add hi into the first accumulator and lo into the second, exactly
+#pragma unroll
+                for (int rt = 0; rt < RT16; ++rt) {
+                    const half8 xh = *reinterpret_cast<const half8 *>(dh + rbase[rt] + 32 * ch + 8 * g);
+                    const half8 xl = *reinterpret_cast<const half8 *>(dl + rbase[rt] + 32 * ch + 8 * g);
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) {
+                        half8 idf;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) idf[j] = (_Float16)((8 * g + j) == 16 * ct + n ? 1.0f : 0.0f);
+                        ah[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(idf, xh, ah[rt][ct], 0, 0, 0);
+                        al[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(idf, xl, al[rt][ct], 0, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int rt = 0; rt < RT16; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) store16q(ah[rt][ct], al[rt][ct], dh, dl, rbase[rt] + 32 * ch + 16 * ct + 4 * g, real[rt]);
+        }
+        if (L < 6) stamp(2 + L);
+    };
+    for (int blk = 0; blk < nd.n_res; ++blk) {
+        layer(std::false_type{}, 2 * blk);
+        layer(std::true_type{}, 2 * blk + 1);
+    }
+    stamp(8);
+    // ------------------------------------------------------------------ 1x1 head convs: two k-steps, hi/lo operands
+    float *hs = reinterpret_cast<float *>(p1h);   // [HSTR] fp32 (p1 is free)
+    {
+        const half8 hwh0 = nd.head_w16[lane], hwh1 = nd.head_w16[64 + lane];
+        const half8 hwl0 = nd.head_w16l[lane], hwl1 = nd.head_w16l[64 + lane];
+        floatx4 a[RT16], b[RT16];
+#pragma unroll
+        for (int rt = 0; rt < RT16; ++rt) {
+            const half8 xh0 = *reinterpret_cast<const half8 *>(p0h + rbase[rt] + 8 * g);
+            const half8 xl0 = *reinterpret_cast<const half8 *>(p0l + rbase[rt] + 8 * g);
+            const half8 xh1 = *reinterpret_cast<const half8 *>(p0h + rbase[rt] + 32 + 8 * g);
+            const half8 xl1 = *reinterpret_cast<const half8 *>(p0l + rbase[rt] + 32 + 8 * g);
+            a[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwh0, xh0, zero4, 0, 0, 0);
+            a[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwh1, xh1, a[rt], 0, 0, 0);
+            b[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwl0, xh0, zero4, 0, 0, 0);
+            b[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwh0, xl0, b[rt], 0, 0, 0);
+            b[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwl1, xh1, b[rt], 0, 0, 0);
+            b[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwh1, xl1, b[rt], 0, 0, 0);
+        }
+#pragma unroll
+        for (int rt = 0; rt < RT16; ++rt) {
+            const int r = 16 * rt + n;
+            if (g == 0 && r < PIX) {
+                hs[0 * PIX + r] = lrelu(a[rt][0] + b[rt][0] * LO_INV + hb0);
+                hs[1 * PIX + r] = lrelu(a[rt][1] + b[rt][1] * LO_INV + hb1);
+                hs[2 * PIX + r] = lrelu(a[rt][2] + b[rt][2] * LO_INV + hb2);
+            }
+        }
+        if (lane < 2) hs[HEADV + lane] = 0.0f;   // pad 126,127
+    }
+    stamp(9);
+    // ------------------------------------------------------------------ MLP heads (fp32 VALU), as in net_forward_block
+    {
+        const float *vt_b = reinterpret_cast<const float *>(mlp + VT_F4 + PT_F / 4);   // fc_b | vout_w | pfc_b
+        const float *pt = reinterpret_cast<const float *>(mlp + VT_F4);
+        const float4 *hA4 = reinterpret_cast<const float4 *>(hs);
+        float v0 = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 11; ++q) {
+            const float4 wv = mlp[q * 64 + lane];
+            const float4 xa = hA4[q];
+            v0 += wv.x * xa.x + wv.y * xa.y + wv.z * xa.z + wv.w * xa.w;
+        }
+        const int seg = lane >> 3;
+        const float *hpA = hs + PIX + seg * 11;
+        float l0 = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 11; ++c) {
+            const float wv = pt[c * 64 + lane];      // zero where seg*11 + c >= 84 or (lane & 7) == 7
+            const int cc = seg * 11 + c < 2 * PIX ? c : 2 * PIX - 1 - seg * 11;
+            l0 += wv * hpA[cc];
+        }
+        l0 += dppf<0x128>(l0);
+#pragma unroll
+        for (int m = 16; m <= 32; m <<= 1) l0 += __shfl_xor(l0, m, 64);
+        const float fb = vt_b[lane], vw = vt_b[64 + lane], pb = vt_b[128 + lane];
+        const bool is_pol = lane < 7;
+        const float a = v0 + fb;
+        const float lg = l0 + pb;
+        const float rs = sum16(lane < PIX ? vw * lrelu(a) : 0.0f);               // model.py:83-85
+        const float vsum = readlane_f(rs, 0) + readlane_f(rs, 16) + readlane_f(rs, 32);
+        const float value = (tanhf(vsum + nd.vout_b) + nd.w1) * nd.w2;           // model.py:86-88
+        const float mx = max8(is_pol ? lg : -INFINITY);
+        const float e = is_pol ? expf(lg - mx) : 0.0f;
+        const float sum = sum8(e);
+        if (lane == 0) values[out] = value;
+        if (is_pol) priors[(size_t)out * 7 + lane] = e / sum;
+    }
+    stamp(10);
+}
+
 // net mode of a NetDev, as the kernels are specialised
 constexpr int NETMODE_F32_F16 = 0;    // 32 filters, fp16 storage: net_forward_wave16 / net_forward_block
 constexpr int NETMODE_F32_PRECISE = 1;
 constexpr int NETMODE_F64 = 2;        // 64 filters, fp16 storage, one position per pass
-// LDS for the fragments a pass needs first (only the reference-precision forward keeps any)
+constexpr int NETMODE_F64_PRECISE = 3;   // 64 filters, reference precision (C4_NET_F32X3_WIDE): net_forward_wave16x
+// LDS for the fragments a pass needs first (only the 32-filter reference-precision forward keeps any: the 64-filter one
+// requests them from L2, its planes leave no room and its pass is long enough to hide the round trip)
 template <int MODE> struct W0Lds { static constexpr int FRAGS = MODE == NETMODE_F32_PRECISE ? W0_FRAGS * 64 : 1; };
 template <int MODE>
 __device__ __forceinline__ void net_forward_wave1_mode(const NetDev &nd, _Float16 *buf, const float4 *mlp, const float *bias_lds,
@@ -1391,13 +1680,17 @@ __device__ __forceinline__ void net_forward_wave1_mode(const NetDev &nd, _Float1
                                                        unsigned long long *stamps = nullptr)
 {
     if constexpr (MODE == NETMODE_F64) net_forward_wave16w(nd, buf, mlp, bias_lds, tab, b0, b1, values, priors, out, stamps);
+    else if constexpr (MODE == NETMODE_F64_PRECISE) net_forward_wave16x(nd, buf, mlp, bias_lds, tab, b0, b1, values, priors, out, stamps);
     else if constexpr (MODE == NETMODE_F32_PRECISE) net_forward_wave16q(nd, buf, mlp, bias_lds, tab, b0, b1, values, priors, out, w0, stamps);
     else net_forward_wave16(nd, buf, mlp, bias_lds, tab, b0, b1, values, priors, out, stamps);
 }
 // halves of private LDS a wave needs for its planes in each mode
 template <int MODE> struct WaveBuf {
-    static constexpr int HALVES = MODE == NETMODE_F64 ? 2 * PLANE64 : (MODE == NETMODE_F32_PRECISE ? 4 * PLANE16 : 2 * PLANE16);
+    static constexpr int HALVES = MODE == NETMODE_F64_PRECISE ? 4 * PLANE64
+                                  : (MODE == NETMODE_F64 ? 2 * PLANE64 : (MODE == NETMODE_F32_PRECISE ? 4 * PLANE16 : 2 * PLANE16));
 };
+// halves per LDS row of a mode's planes (the tap-offset table is built for it)
+template <int MODE> struct WaveRow { static constexpr int CS = (MODE == NETMODE_F64 || MODE == NETMODE_F64_PRECISE) ? CS64 : CS16; };
 
 constexpr int BIAS_LDS_FLOATS = 32 * (1 + 32);    // 4.2 KB: stem + conv biases of up to 16 residual blocks at 32 filters, 7 at 64
 // cooperative fill of the LDS bias copy by the whole workgroup (the caller synchronises afterwards)

@@ -56,7 +56,7 @@ def fold_for_fused(state_dict, dtype=np.float32) -> dict:
 class FusedNet:
     from_bitboards = True
 
-    PRECISIONS = {"f16": 0, "f32x3": 1}
+    PRECISIONS = {"f16": L.NET_F16, "f32x3": L.NET_F32X3, "f32x3w": L.NET_F32X3_WIDE}
 
     @staticmethod
     def default_precision(filters: int) -> str:
@@ -64,10 +64,17 @@ class FusedNet:
         visit counts: "f32x3" wherever the engine offers it (32 filters); the 64-filter forward exists in fp16 storage only."""
         return "f32x3" if filters == 32 else "f16"
 
+    @staticmethod
+    def reference_precision(filters: int) -> str:
+        """The mode that reproduces the reference's float32 answers at this width, whichever kernel serves it: "f32x3" at 32
+        filters, "f32x3w" at 64 (not the default there: see default_precision)."""
+        return "f32x3" if filters == 32 else "f32x3w"
+
     def __init__(self, state_dict, device: int = 0, precision: Optional[str] = None):
         """precision: "f32x3" = reference precision (the default at 32 filters): every fp32 operand split into fp16 hi +
         scaled lo parts, three MFMAs per k-step, fp32 accumulation; "f16" = fp16 storage / fp32 accumulation (one MFMA
-        per k-step), opt-in: faster, answers within 2e-2 of the reference's instead of 5e-5."""
+        per k-step), opt-in: faster, answers within 2e-2 of the reference's instead of 5e-5; "f32x3w" = the arithmetic of
+        "f32x3" for 64 filters (a forward of its own: "f32x3" stays refused there, "f32x3w" is refused at 32)."""
         sd = {k: v.detach().cpu() for k, v in state_dict.items()}
         cfg = PolicyValueNet.config_from_state_dict(sd)
         if precision is None:
@@ -130,16 +137,17 @@ class FusedNet:
 def make_selfplay_net(state_dict, device: int = 0, precision: Optional[str] = None):
     """The fastest evaluator this build has for a checkpoint at the requested precision: the fused MFMA forwards for 32
     filters (the reference's default, config.py:8-12; reference precision "f32x3" unless "f16" is asked for) and for
-    64 filters (its example_config, data/example_config.py:8-16; fp16 storage only, so precision=None or "f16"), up to
-    16 / 7 residual blocks (their biases live in LDS) and any number of value-head Linear layers; anything else -- 64
-    filters with precision="f32x3", and a net with a folded conv weight beyond fp16's range (c4_net_create refuses it
-    with C4_EINVAL) -- runs through the PyTorch-ROCm plan (connect4_amd.net.InferenceNet, fp32).
+    64 filters (its example_config, data/example_config.py:8-16; fp16 storage for precision=None or "f16", reference
+    precision for "f32x3w"), up to 16 / 7 residual blocks (their biases live in LDS) and any number of value-head Linear
+    layers; anything else -- 64 filters with precision="f32x3" (the 32-filter forward's name), 32 filters with "f32x3w",
+    and a net with a folded conv weight beyond fp16's range (c4_net_create refuses it with C4_EINVAL) -- runs through
+    the PyTorch-ROCm plan (connect4_amd.net.InferenceNet, fp32).
     All plug into SelfPlay / generate_games / DeviceNetEvaluator unchanged."""
     import torch
     cfg = PolicyValueNet.config_from_state_dict(state_dict)
     if precision is None:
         precision = FusedNet.default_precision(cfg.filters)
-    fits = (cfg.filters == 32 and cfg.n_residuals <= 16) or (cfg.filters == 64 and cfg.n_residuals <= 7 and precision == "f16")
+    fits = (cfg.filters == 32 and cfg.n_residuals <= 16) or (cfg.filters == 64 and cfg.n_residuals <= 7 and precision in ("f16", "f32x3w"))
     if cfg.channels == 3 and fits:
         try:
             return FusedNet(state_dict, device=device, precision=precision)

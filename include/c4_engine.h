@@ -414,10 +414,13 @@ const char *c4_grid_last_error(void);
  *   w1, w2                                     value_head.w1/w2 (model.py:74-75,88) */
 /* arithmetic of the fused forwards */
 #define C4_NET_F16 0    /* fp16 storage, fp32 accumulation: one MFMA per k-step */
-#define C4_NET_F32X3 1  /* reference precision: fp32 operands split into fp16 hi + scaled lo, three MFMAs per k-step */
+#define C4_NET_F32X3 1  /* reference precision: fp32 operands split into fp16 hi + scaled lo, three MFMAs per k-step; 32 filters */
+#define C4_NET_F32X3_WIDE 2  /* the same arithmetic for 64 filters (a layer in two cout halves); the stand-alone forward runs
+                              * four waves per workgroup, c4_selfplay_steps four tree + four network waves (split kernel only:
+                              * C4_FUSED_MODE=wave / block return C4_ESTATE) */
 typedef struct {
     int32_t channels, filters, n_residuals;
-    int32_t precision;   /* C4_NET_F16 or C4_NET_F32X3 */
+    int32_t precision;   /* C4_NET_F16, C4_NET_F32X3 (32 filters only) or C4_NET_F32X3_WIDE (64 filters only) */
     const float *stem_w, *stem_b, *conv_w, *conv_b, *head_w, *head_b;
     const float *vfc_w, *vfc_b, *vout_w, *pfc_w, *pfc_b;
     float vout_b, w1, w2, reserved2;

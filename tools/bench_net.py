@@ -15,12 +15,15 @@ def main():
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--wave", type=int, default=0, help="1: the wave-private forward (one position per wave)")
-    ap.add_argument("--precision", default="f16", choices=["f16", "f32x3"])
+    ap.add_argument("--precision", default="f16", choices=["f16", "f32x3", "f32x3w"])
+    ap.add_argument("--filters", type=int, default=32)
+    ap.add_argument("--residuals", type=int, default=3)
+    ap.add_argument("--fc-layers", type=int, default=4)
     args = ap.parse_args()
     from connect4_amd.fused_net import FusedNet
-    from connect4_amd.net import InferenceNet, random_init_state_dict
+    from connect4_amd.net import InferenceNet, NetConfig, random_init_state_dict
     from connect4_amd.engine import board_planes
-    sd = random_init_state_dict(seed=0)
+    sd = random_init_state_dict(NetConfig(filters=args.filters, n_residuals=args.residuals, n_fc_layers=args.fc_layers), seed=0)
     net = FusedNet(sd, precision=args.precision)
     rng = np.random.RandomState(0)
     c0 = rng.randint(0, 2 ** 40, size=args.n).astype(np.uint64) & np.uint64(0x7EFDFBF7EFDF)
@@ -40,7 +43,8 @@ def main():
     b.record()
     torch.cuda.synchronize()
     us = a.elapsed_time(b) * 1000 / args.iters
-    tf = 4.74e6 * args.n / (us * 1e-6) / 1e12
+    flops = 2 * 42 * (27 * args.filters + 2 * args.residuals * 9 * args.filters ** 2 + 3 * args.filters)   # convs only (4.7e6 for 32/3)
+    tf = flops * args.n / (us * 1e-6) / 1e12
     print("fused net (%s, wave=%d, active waves per CU %s): n=%d  %.1f us/forward  %.1f TFLOP/s (%.1f%% of 2.5 PF fp16 dense)" % (args.precision, int(wave), os.environ.get("C4_NET_WAVE_ACTIVE", "8"), args.n, us, tf, tf / 25.0))
     ref = InferenceNet(sd, device="cuda", dtype=torch.float32)
     planes = torch.from_numpy(board_planes(c0, c1)).cuda()

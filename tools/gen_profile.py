@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Time line of a FINITE self-play batch (one generation's share) on one GPU: engine creation, then every `--poll` quanta
 the games finished, simulations, cache hit rate and active slots; at the end the batch's games/s against the steady-state
-rate of the same slot count (bench.py).  python tools/gen_profile.py --games 1200 --slots 1200 [--precision f32x3]"""
+rate of the same slot count (bench.py).  python tools/gen_profile.py --games 1200 --slots 1200 [--precision f32x3]
+[--filters 64 --residuals 6 --fc-layers 6].  The net is what make_selfplay_net returns for the precision: a FusedNet inside
+the persistent self-play kernel, or (64 filters with --precision f32x3) the fp32 PyTorch plan stepped from the host as
+generate_games drives it (HIP graph, 8 inner iterations)."""
 import argparse
 import json
 import os
@@ -18,24 +21,29 @@ def main():
     ap.add_argument("--sims", type=int, default=800)
     ap.add_argument("--poll", type=int, default=64)
     ap.add_argument("--precision", default=None)
+    ap.add_argument("--filters", type=int, default=32)
+    ap.add_argument("--residuals", type=int, default=3)
+    ap.add_argument("--fc-layers", type=int, default=4)
     ap.add_argument("--series", type=int, default=0, help="1: print the time line")
     a = ap.parse_args()
     import torch
     from connect4_amd.config import MCTSConfig
-    from connect4_amd.fused_net import FusedNet
-    from connect4_amd.net import random_init_state_dict
+    from connect4_amd.fused_net import make_selfplay_net
+    from connect4_amd.net import NetConfig, random_init_state_dict
     from connect4_amd.selfplay import SelfPlay
     slots = a.slots or min(a.games, 4096)
-    net = FusedNet(random_init_state_dict(seed=0), precision=a.precision)
+    net = make_selfplay_net(random_init_state_dict(NetConfig(filters=a.filters, n_residuals=a.residuals, n_fc_layers=a.fc_layers), seed=0),
+                            precision=a.precision)
+    fused = bool(getattr(net, "from_bitboards", False))
     # warm the runtime
-    sp = SelfPlay(net, 64, MCTSConfig.self_play(32), seed=0, games_target=64, record_capacity_games=64, use_graph=False, fused_loop=True)
+    sp = SelfPlay(net, 64, MCTSConfig.self_play(32), seed=0, games_target=64, record_capacity_games=64, use_graph=False, fused_loop=fused)
     sp.run_steps(64)
     sp.synchronize()
     sp.close()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     sp = SelfPlay(net, slots, MCTSConfig.self_play(a.sims), seed=1, games_target=a.games, record_capacity_games=a.games,
-                  use_graph=False, fused_loop=True, max_inner_iters=32)
+                  use_graph=not fused, fused_loop=fused, max_inner_iters=32 if fused else 8)
     torch.cuda.synchronize()
     t_create = time.perf_counter() - t0
     series = []
@@ -54,7 +62,8 @@ def main():
     t_export = time.perf_counter() - t1
     sp.close()
     half = next(t for t, g, *_ in series if g >= a.games // 2)
-    out = {"games": a.games, "slots": slots, "sims": a.sims, "precision": net.precision, "engine_create_s": t_create, "play_s": t_play,
+    out = {"games": a.games, "slots": slots, "sims": a.sims, "net": type(net).__name__,
+           "filters": a.filters, "residuals": a.residuals, "fc_layers": a.fc_layers, "precision": getattr(net, "precision", "fp32"), "engine_create_s": t_create, "play_s": t_play,
            "export_s": t_export, "total_s": t_create + t_play + t_export, "games_per_s": a.games / (t_create + t_play + t_export),
            "games_per_s_play_only": a.games / t_play, "time_to_half_the_games_s": half - t_create,
            "sims_per_s_play_only": series[-1][2] / t_play, "final_hit_rate": series[-1][3] / max(1, series[-1][4]),

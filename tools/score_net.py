@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Score checkpoints on a labelled set with the reference's statistics (neural/stats.py), on the GPU.
 
-    python tools/score_net.py NET DATASET [--precision f32x3|f16] [--device 0]
+    python tools/score_net.py NET DATASET [--precision f32x3|f16|f32x3w] [--device 0]
     python tools/score_net.py --bench          wall time of stats.score on tests/golden's 3,000 labelled rows and on 135,000
 
 NET is a net.pth (ModelWrapper.save / Trainer.save) or a directory of generations (<g>/net.pth, as run_generations writes
@@ -57,7 +57,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("net", nargs="?")
     ap.add_argument("dataset", nargs="?")
-    ap.add_argument("--precision", default=None, choices=("f32x3", "f16"))
+    ap.add_argument("--precision", default=None, choices=("f32x3", "f16", "f32x3w"))
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--bench", action="store_true")
     a = ap.parse_args()
