@@ -22,6 +22,7 @@ SLOT_ACTIVE, SLOT_PARKED, SLOT_MOVE_DONE = 0, 1, 2
 PRIOR_NONE, PRIOR_F32, PRIOR_F64 = 0, 1, 2
 PV_VALUE, PV_VISITS = 0, 1
 NET_F16, NET_F32X3, NET_F32X3_WIDE = 0, 1, 2   # c4_net_desc.precision
+MATCH_MAX_NETS = 16
 
 
 class EngineError(RuntimeError):
@@ -166,6 +167,8 @@ SIGNATURES = {
     "c4_net_forward_wave": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "c4_net_last_error": (C.c_char_p, []),
     "c4_selfplay_steps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "c4_match_assign": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int32]),
+    "c4_match_steps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "c4_net_debug_stamps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "c4_bn_workspace_floats": (C.c_longlong, [C.c_int, C.c_int]),
     "c4_bn_train_forward": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p]),

@@ -1831,6 +1831,191 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_wave_kernel(const
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// c4_match_wave_kernel<TS, MODE>: net-vs-net matches (the reference's Match, oinkoink/match.py:15-70).
+// The wave-autonomous kernel above with one more rule: a launch serves ONE net (nd, evaluation cache d.cache) and
+// only the slots whose game has that net to move.  side_o[g] / side_x[g] name the net that moves o / x in slot g
+// (c4_match_assign); the net to move is side_o when the root holds an even number of stones, side_x otherwise.
+// Every other slot is masked out of tree_step and of the network phase; its state passes through LDS unchanged,
+// and so does its row of the hand-off buffers: a leaf this net answered at the end of its previous launch is still
+// there, answered, when its next launch applies it.
+// The move itself: `d` is the engine description with stop_after_move set (c4_match_steps keeps one such copy per
+// net), so tree_step leaves the loop when it has chosen a move -- its own re-rooting would probe the new root in
+// d.cache, the table of the net that just MOVED, where the position almost always sits (that net evaluated it as a
+// child), and the opponent's search would start from the wrong net's answer.  The kernel then does what
+// tree_step's continuous branch does (stage the move, make it, publish a finished game) and hands the slot over
+// with need_root set: the opponent's launch probes the opponent's table and evaluates the root with its own net.
+// A wave none of whose slots is (or can become) active leaves the loop at once: there is no spin and no
+// rendezvous, the only wait is the launch deadline of the wave kernel.  Each slot plays one game and parks.
+// ------------------------------------------------------------------------------------------
+template <int TS, int MODE>
+__global__ __launch_bounds__(c4net::NTHREADS) void c4_match_wave_kernel(const Dev *d_dev, c4net::NetDev nd, float *__restrict__ values,
+                                                                        float *__restrict__ priors, int n_steps,
+                                                                        const uint8_t *__restrict__ side_o, const uint8_t *__restrict__ side_x,
+                                                                        int net_index)
+{
+    using namespace c4net;
+    const_dev &d = *(const_dev *)d_dev;
+    constexpr int SPW = TS / NWAVES;   // slots per wave
+    static_assert(TS % NWAVES == 0 && SPW >= 1 && SPW <= 8, "slots per workgroup");
+    constexpr int WBUF = WaveBuf<MODE>::HALVES;
+    __shared__ __attribute__((aligned(16))) _Float16 act[NWAVES][WBUF];
+    __shared__ __attribute__((aligned(16))) float4 mlp[MLP_F4];
+    __shared__ SlotMem smem[TS];
+    __shared__ float s_val[TS];
+    __shared__ float s_pri[TS * 7];
+    __shared__ uint32_t s_stats[N_STATS];
+    __shared__ __attribute__((aligned(16))) float s_bias[BIAS_LDS_FLOATS];
+    __shared__ __attribute__((aligned(16))) uint16_t s_tab16[64 * TAB16];
+    __shared__ uint8_t s_side[2][TS];   // net that moves o / x in each slot (0xff: no game)
+    constexpr bool OWN_PATH = MODE == NETMODE_F32_F16;
+    __shared__ __attribute__((aligned(16))) PathEntry s_path_own[OWN_PATH ? TS : 1][MAX_DEPTH];
+    __shared__ __attribute__((aligned(16))) Rec s_l1_own[OWN_PATH ? TS : 1][GROUP];
+    static_assert(OWN_PATH || (sizeof(PathEntry) * MAX_DEPTH + sizeof(Rec) * GROUP) * SPW <= sizeof(_Float16) * WBUF, "a wave's path stacks must fit its activation planes");
+    const int slot0 = blockIdx.x * TS;
+    const int wv = threadIdx.x >> 6;
+    // ---- launch prologue: as c4_selfplay_wave_kernel, plus the slots' player assignment
+    if (threadIdx.x < TS) {
+        const int p = threadIdx.x, g = slot0 + p;
+        SlotMem m = {};
+        m.flags = SlotMem::pack(SLOT_PARKED, 0, 0);
+        uint8_t so = 0xff, sx = 0xff;
+        if (g < d.G) {
+            m.root0 = d.root_c0[g]; m.root1 = d.root_c1[g]; m.leaf0 = d.leaf_c0[g]; m.leaf1 = d.leaf_c1[g];
+            m.gid = d.game_id[g]; m.sims = d.sims_done[g]; m.nalloc = d.n_alloc[g]; m.pend = d.pending[g];
+            m.pdepth = d.pending_depth[g]; m.pinfo = d.pending_info[g];
+            m.ply = d.ply[g]; m.flags = SlotMem::pack(d.state[g], d.has_leaf[g], d.need_root[g]);
+            m.root_w = *(const double *)(d.pool + (size_t)g * d.cap * (BLOCK_BYTES / 8));   // Rec::w of node 0
+            so = side_o[g];
+            sx = side_x[g];
+        }
+        smem[p] = m;
+        s_side[0][p] = so;
+        s_side[1][p] = sx;
+    }
+    if (threadIdx.x < N_STATS) s_stats[threadIdx.x] = 0;
+    for (int i = threadIdx.x; i < TS * 8; i += NTHREADS) {   // answers of earlier launches (every net's rows)
+        const int p = i >> 3, k = i & 7;
+        const bool ok = slot0 + p < d.G;
+        if (k == 7) s_val[p] = ok ? values[slot0 + p] : 0.0f;
+        else s_pri[p * 7 + k] = ok ? priors[(size_t)(slot0 + p) * 7 + k] : 0.0f;
+    }
+    for (int i = threadIdx.x; i < MLP_F4; i += NTHREADS) mlp[i] = nd.mlp[i];
+    stage_bias_lds(nd, s_bias);
+    if (threadIdx.x < 64) build_tab16<MODE == NETMODE_F64 ? CS64 : CS16>(s_tab16, threadIdx.x);
+    if (OWN_PATH)
+        for (int i = threadIdx.x; i < TS * MAX_DEPTH; i += NTHREADS) {   // paths of leaves pending from earlier launches
+            const int p = i / MAX_DEPTH, k = i - p * MAX_DEPTH;
+            if (slot0 + p < d.G) s_path_own[p][k] = d.path[(size_t)(slot0 + p) * MAX_DEPTH + k];
+        }
+    __syncthreads();
+    PathEntry (*s_path)[MAX_DEPTH] = OWN_PATH ? s_path_own : reinterpret_cast<PathEntry (*)[MAX_DEPTH]>(&act[wv][0]);
+    Rec (*s_l1)[GROUP] = OWN_PATH ? s_l1_own : reinterpret_cast<Rec (*)[GROUP]>(&act[wv][0] + sizeof(PathEntry) * MAX_DEPTH * SPW / sizeof(_Float16));
+    // a slot is active in this launch iff it has a game and this launch's net is to move in it
+    auto active = [&](int p) {
+        const SlotMem &m = smem[p];
+        return m.state() == SLOT_ACTIVE && (int)s_side[popc64(m.root0 | m.root1) & 1][p] == net_index;
+    };
+    const unsigned long long t_launch = __builtin_amdgcn_s_memtime();
+    const unsigned long long quantum = (unsigned long long)n_steps * (unsigned long long)(d.time_budget > 0 ? d.time_budget : 80000);
+    while (__builtin_amdgcn_s_memtime() - t_launch < quantum) {
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));   // see c4_selfplay_kernel: keep the tree phase's addresses out of the net phase
+        const int lane = tid & (GROUP - 1);
+        const int grp = (tid & 63) / GROUP;
+        const int sl = (tid >> 6) + NWAVES * grp;     // slot of this 8-lane group inside the workgroup
+        const bool mine = grp < SPW && active(sl);
+        if (__builtin_amdgcn_ballot_w64(mine) == 0) break;   // only this wave's own moves change who is to move in its slots
+        if (mine) {
+            tree_step<C4_EVAL_EXTERNAL_F32, false, true, true, OWN_PATH>(d, slot0 + sl, lane, OWN_PATH ? sl : grp, s_path, s_l1, s_val, s_pri, nullptr,
+                                                                         nullptr, &smem[sl], sl, s_stats, t_launch + quantum);
+            lds_fence();   // the slot state written by the group's first lane
+            SlotMem *m = &smem[sl];
+            if (m->state() == SLOT_MOVE_DONE) {   // mcts.py:78-88 returned a move: match.py:44-50 plays it, the opponent is next
+                const int g = slot0 + sl;
+                uint64_t r0 = m->root0, r1 = m->root1;
+                const uint32_t ply = m->ply;
+                const long long gid = m->gid;
+                // what tree_step's move choice left in the result rows (each lane reads back its own stores)
+                int mv = 0;
+                double absv = 0.0, pol = 0.0;
+                if (lane == 0) { mv = d.cold->res_move[g]; absv = d.cold->res_value[g]; }
+                if (lane < 7) pol = d.cold->res_policy[(size_t)g * 7 + lane];
+                mv = gshfl(mv, 0);
+                if (d.rec_cap > 0) {   // training_game.py:12-15 record (board before the move), staged until the game ends
+                    const size_t r = (size_t)g * 42 + ply;
+                    if (lane == 0) {
+                        d.cold->stg_c0[r] = r0;
+                        d.cold->stg_c1[r] = r1;
+                        d.cold->stg_move[r] = mv;
+                        d.cold->stg_value[r] = absv;
+                    }
+                    if (lane < 7) d.cold->stg_policy[r * 7 + lane] = pol;
+                }
+                const uint32_t cst = make_move(r0, r1, mv);   // board.make_move(move)
+                int state = SLOT_ACTIVE, need_root = 1;
+                if (cst >= ST_XWIN) {   // game over: the slot's one game is recorded and the slot parks
+                    if (d.rec_cap > 0) publish_game(d, g, gid, (int)ply + 1, (int32_t)(cst - ST_XWIN), lane);
+                    if (lane == 0) atomicAdd(&s_stats[offsetof(SlotStats, games_finished) / sizeof(uint64_t)], 1u);
+                    state = SLOT_PARKED;
+                    need_root = 0;
+                }
+                if (lane == 0) {
+                    m->root0 = r0;
+                    m->root1 = r1;
+                    m->ply = ply + 1;
+                    m->flags = SlotMem::pack(state, 0, need_root);
+                }
+            }
+        }
+        lds_fence();   // the slot states written by the groups' first lanes are read by the whole wave
+        // the wave's own leaves of this launch's net
+        int pend_slot[SPW];
+        int cnt = 0;
+#pragma unroll
+        for (int q = 0; q < SPW; ++q) {
+            const int sq = wv + NWAVES * q;
+            const int has = __builtin_amdgcn_readfirstlane((smem[sq].has_leaf() && active(sq)) ? 1 : 0);
+            if (has) pend_slot[cnt++] = sq;
+        }
+        if (MODE == NETMODE_F32_F16) {   // 32 filters, fp16: one position per pass on 16-row MFMA tiles
+            for (int i = 0; i < cnt; ++i) {
+                const int sa = pend_slot[i];
+                net_forward_wave16(nd, &act[wv][0], mlp, s_bias, s_tab16, smem[sa].leaf0, smem[sa].leaf1, s_val, s_pri, sa, nullptr);
+            }
+        } else {   // reference-precision net or 64 filters: one position per pass on 32-row tiles
+            for (int i = 0; i < cnt; ++i) {
+                const int sa = pend_slot[i];
+                net_forward_wave1_mode<MODE>(nd, &act[wv][0], mlp, s_bias, s_tab16, smem[sa].leaf0, smem[sa].leaf1, s_val, s_pri, sa, nd.w0);
+            }
+        }
+        lds_fence();   // answers (LDS) before the next tree_step reads them
+    }
+    __syncthreads();
+    // ---- launch epilogue: LDS -> global
+    if (OWN_PATH)
+        for (int i = threadIdx.x; i < TS * MAX_DEPTH; i += NTHREADS) {   // paths of the leaves of THIS launch that wait for their application
+            const int p = i / MAX_DEPTH, k = i - p * MAX_DEPTH;
+            if (slot0 + p < d.G && smem[p].has_leaf() && active(p)) d.path[(size_t)(slot0 + p) * MAX_DEPTH + k] = s_path_own[p][k];
+        }
+    if (threadIdx.x < TS && slot0 + threadIdx.x < d.G) {
+        const int p = threadIdx.x, g = slot0 + p;
+        const SlotMem m = smem[p];
+        d.root_c0[g] = m.root0; d.root_c1[g] = m.root1; d.leaf_c0[g] = m.leaf0; d.leaf_c1[g] = m.leaf1;
+        d.game_id[g] = m.gid; d.sims_done[g] = m.sims; d.n_alloc[g] = m.nalloc; d.pending[g] = m.pend;
+        d.pending_depth[g] = m.pdepth; d.pending_info[g] = m.pinfo; d.need_root[g] = m.need_root();
+        d.ply[g] = m.ply; d.state[g] = m.state(); d.has_leaf[g] = m.has_leaf() ? 1 : 0;
+    }
+    if (threadIdx.x < N_STATS) d.stats[(size_t)slot0 * N_STATS + threadIdx.x] += s_stats[threadIdx.x];
+    for (int i = threadIdx.x; i < TS * 8; i += NTHREADS) {
+        const int p = i >> 3, k = i & 7;
+        if (slot0 + p < d.G) {
+            if (k == 7) values[slot0 + p] = s_val[p];
+            else priors[(size_t)(slot0 + p) * 7 + k] = s_pri[p * 7 + k];
+        }
+    }
+}
+
 // A network wave looks at an answer before it publishes it (the eight lanes 0..7 of the wave: value, prior[lane]): a value
 // outside [0, 1] or a prior that is not a finite non-negative number is replaced (0.5 / 0) and counted (bad_evals), as
 // tree_step's apply does it in the other kernels.
@@ -2494,6 +2679,13 @@ struct c4_engine {
     int split_tw;         // tuning aid (C4_SPLIT_TW=2|4): tree waves of the split kernel at 16 slots per workgroup; 0 = by net mode
     int tape_games;
     double *tape_noise, *tape_u;
+    // net-vs-net matches (c4_match_assign / c4_match_steps); n_match_nets = c4_config.reserved[0], 0 = none of this exists
+    int n_match_nets;
+    CacheEntry *match_cache[C4_MATCH_MAX_NETS];   // one evaluation cache per net ([0] = d.cache); null = caches off
+    Dev *d_match_dev;                             // [n_match_nets] device copies of `d`: cache = the net's table, stop_after_move = 1
+    Dev d_match_uploaded;
+    uint8_t *match_side_o, *match_side_x;         // [G] net that moves o / x in each slot, 0xff = none
+    int match_assigned;
     char err[512];
 };
 
@@ -2615,8 +2807,18 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
     int rc = check_device(device, g_err);
     if (rc) return rc;
 
+    const int n_match = cfg->reserved[0];
+    if (n_match < 0 || n_match > C4_MATCH_MAX_NETS) { set_err(g_err, "n_match_nets (reserved[0]) = %d out of range [0,%d]", n_match, C4_MATCH_MAX_NETS); return C4_EINVAL; }
+    if (n_match > 0 && (cfg->eval_mode != C4_EVAL_EXTERNAL_F32 || cfg->stop_after_move)) { set_err(g_err, "a match engine (n_match_nets > 0) needs C4_EVAL_EXTERNAL_F32 and stop_after_move = 0"); return C4_EINVAL; }
+
     c4_engine *e = new c4_engine();
     e->cfg = *cfg;
+    e->n_match_nets = n_match;
+    memset(e->match_cache, 0, sizeof(e->match_cache));
+    e->d_match_dev = nullptr;
+    memset(&e->d_match_uploaded, 0xff, sizeof(Dev));
+    e->match_side_o = e->match_side_x = nullptr;
+    e->match_assigned = 0;
     e->device = device;
     e->stream = nullptr;
     e->launches = 0;
@@ -2718,11 +2920,13 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
             // reference-precision net in round 3, where a miss costs twice as much: 2^28 239 M, 2^29 245 M, 2^30 248 M), at most
             // 2^30 entries and a quarter of the FREE device memory as it is after this engine's node pools are allocated (288 GB
             // of HBM is there to be used; ranks that share a card in rehearsals each take a quarter of what they find).
-            const uint64_t want = 256ULL * (uint64_t)cfg->n_slots * ((uint64_t)cfg->simulations + 1);
+            // A match engine keeps one table per net: each gets its share of the entries and of the memory.
+            const uint64_t tables = (uint64_t)(n_match > 0 ? n_match : 1);
+            const uint64_t want = 256ULL * (uint64_t)cfg->n_slots * ((uint64_t)cfg->simulations + 1) / tables;
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)8 << 30;
             bits = 16;
-            while (bits < 30 && (1ULL << bits) < want && (sizeof(CacheEntry) << (bits + 1)) <= free_b / 4) ++bits;
+            while (bits < 30 && (1ULL << bits) < want && (sizeof(CacheEntry) << (bits + 1)) <= free_b / 4 / tables) ++bits;
         }
         if (bits > 0 && cfg->eval_mode == C4_EVAL_EXTERNAL_F32) {
             if (bits < 8 || bits > 30) { set_err(g_err, "eval_cache_log2_entries=%d out of range [8,30]", bits); c4_engine_destroy(e); *out = nullptr; return C4_EINVAL; }
@@ -2731,7 +2935,20 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
             if (hipMemset(c, 0xFF, sizeof(CacheEntry) << bits) != hipSuccess) { set_err(g_err, "cache memset failed"); c4_engine_destroy(e); *out = nullptr; return C4_EDEVICE; }
             d.cache = c;
             d.cache_bits = bits;
+            e->match_cache[0] = c;
+            for (int k = 1; k < n_match; ++k) {   // the other nets' tables: the evaluation cache must not mix two nets' answers
+                CacheEntry *ck = nullptr;
+                if (dev_alloc(e, &ck, (size_t)1 << bits) != C4_OK) { strncpy(g_err, e->err, 511); c4_engine_destroy(e); *out = nullptr; return C4_ENOMEM; }
+                if (hipMemset(ck, 0xFF, sizeof(CacheEntry) << bits) != hipSuccess) { set_err(g_err, "cache memset failed"); c4_engine_destroy(e); *out = nullptr; return C4_EDEVICE; }
+                e->match_cache[k] = ck;
+            }
         }
+    }
+    if (n_match > 0) {
+        ALLOC(e->d_match_dev, (size_t)n_match);
+        ALLOC(e->match_side_o, G);
+        ALLOC(e->match_side_x, G);
+        if (hipMemset(e->match_side_o, 0xFF, G) != hipSuccess || hipMemset(e->match_side_x, 0xFF, G) != hipSuccess) { set_err(g_err, "match assignment memset failed"); c4_engine_destroy(e); *out = nullptr; return C4_EDEVICE; }
     }
     if (getenv("C4_TREE_STAMPS")) {
         unsigned long long *q = nullptr;
@@ -2768,6 +2985,8 @@ int c4_clear_eval_cache(c4_engine *e)
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipDeviceSynchronize());
     HIPCHK(e, hipMemset(e->d.cache, 0xFF, sizeof(CacheEntry) << e->d.cache_bits));
+    for (int k = 1; k < e->n_match_nets; ++k)   // a match engine: every net's table
+        if (e->match_cache[k]) HIPCHK(e, hipMemset(e->match_cache[k], 0xFF, sizeof(CacheEntry) << e->d.cache_bits));
     return C4_OK;
 }
 
@@ -2913,6 +3132,65 @@ int c4_selfplay_steps(c4_engine *e, c4_net *net, float *values_dev, float *prior
         hipLaunchKernelGGL(c4_selfplay_kernel<32>, dim3((e->d.G + 31) / 32), dim3(c4net::NTHREADS), 0, st, e->d, nd, values_dev, priors_dev, (int)n_steps);
     else
         hipLaunchKernelGGL(c4_selfplay_kernel<16>, dim3((e->d.G + 15) / 16), dim3(c4net::NTHREADS), 0, st, e->d, nd, values_dev, priors_dev, (int)n_steps);
+    HIPCHK(e, hipGetLastError());
+    e->launches += n_steps;
+    return C4_OK;
+}
+
+int c4_match_assign(c4_engine *e, const int32_t *net_o, const int32_t *net_x, int32_t n)
+{
+    if (!e) return C4_EINVAL;
+    if (e->n_match_nets <= 0) { set_err(e->err, "c4_match_assign: the engine was not created for matches (c4_config.reserved[0] = n_match_nets)"); return C4_ESTATE; }
+    if (!net_o || !net_x || n < 0 || n > e->d.G) { set_err(e->err, "c4_match_assign: bad argument (n = %d, slots = %d)", n, e->d.G); return C4_EINVAL; }
+    std::vector<uint8_t> so((size_t)e->d.G, 0xff), sx((size_t)e->d.G, 0xff);
+    for (int i = 0; i < n; ++i) {
+        if (net_o[i] < 0 || net_o[i] >= e->n_match_nets || net_x[i] < 0 || net_x[i] >= e->n_match_nets) {
+            set_err(e->err, "c4_match_assign: slot %d names net %d / %d, the engine has %d", i, net_o[i], net_x[i], e->n_match_nets);
+            return C4_EINVAL;
+        }
+        so[(size_t)i] = (uint8_t)net_o[i];
+        sx[(size_t)i] = (uint8_t)net_x[i];
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipDeviceSynchronize());
+    HIPCHK(e, hipMemcpy(e->match_side_o, so.data(), so.size(), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->match_side_x, sx.data(), sx.size(), hipMemcpyHostToDevice));
+    e->match_assigned = 1;
+    return C4_OK;
+}
+
+int c4_match_steps(c4_engine *e, c4_net *net, int32_t net_index, float *values_dev, float *priors_dev, int32_t n_steps, void *hip_stream)
+{
+    if (!e || !net || !values_dev || !priors_dev || n_steps <= 0) { if (e) set_err(e->err, "c4_match_steps: bad argument"); return C4_EINVAL; }
+    if (e->n_match_nets <= 0) { set_err(e->err, "c4_match_steps: the engine was not created for matches (c4_config.reserved[0] = n_match_nets)"); return C4_ESTATE; }
+    if (net_index < 0 || net_index >= e->n_match_nets) { set_err(e->err, "c4_match_steps: net_index %d out of range [0,%d)", net_index, e->n_match_nets); return C4_EINVAL; }
+    if (!e->match_assigned) { set_err(e->err, "c4_match_steps needs c4_match_assign first"); return C4_ESTATE; }
+    if (net->device != e->device) { set_err(e->err, "engine and net live on different devices"); return C4_EINVAL; }
+    if (e->d.use_noise || e->d.nsm > 0) { set_err(e->err, "c4_match_steps plays without root noise and without sampled moves"); return C4_ESTATE; }
+    c4net::NetDev nd = net->d;
+    nd.stamps = nullptr;
+    if (nd.mode == c4net::NETMODE_F64_PRECISE) {
+        set_err(e->err, "c4_match_steps cannot hold the 64-filter reference-precision net (eight waves' planes exceed a CU's LDS)");
+        return C4_ESTATE;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    if (memcmp(&e->d_match_uploaded, &e->d, sizeof(Dev)) != 0) {   // one description per net: its table, and tree_step stops at the move
+        std::vector<Dev> copies((size_t)e->n_match_nets, e->d);
+        for (int k = 0; k < e->n_match_nets; ++k) {
+            copies[(size_t)k].cache = e->match_cache[k];
+            copies[(size_t)k].stop_after_move = 1;
+        }
+        HIPCHK(e, hipMemcpyAsync(e->d_match_dev, copies.data(), sizeof(Dev) * copies.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipStreamSynchronize(st));   // the source dies with this scope
+        e->d_match_uploaded = e->d;
+    }
+    const Dev *dk = e->d_match_dev + net_index;
+    const dim3 grid((e->d.G + 15) / 16), blk(c4net::NTHREADS);
+#define C4_LAUNCH_MATCH(MODE) hipLaunchKernelGGL((c4_match_wave_kernel<16, MODE>), grid, blk, 0, st, dk, nd, values_dev, priors_dev, (int)n_steps, (const uint8_t *)e->match_side_o, (const uint8_t *)e->match_side_x, (int)net_index)
+    if (nd.mode == c4net::NETMODE_F64) C4_LAUNCH_MATCH(c4net::NETMODE_F64);
+    else if (nd.mode == c4net::NETMODE_F32_PRECISE) C4_LAUNCH_MATCH(c4net::NETMODE_F32_PRECISE);
+    else C4_LAUNCH_MATCH(c4net::NETMODE_F32_F16);
+#undef C4_LAUNCH_MATCH
     HIPCHK(e, hipGetLastError());
     e->launches += n_steps;
     return C4_OK;

@@ -25,7 +25,8 @@ class Engine:
                  root_dirichlet_alpha=0.0, root_exploration_fraction=0.0, num_sampling_moves=0,
                  eval_mode=L.EVAL_EXTERNAL_F32, rng_mode=L.RNG_PHILOX, seed=0, stop_after_move=False,
                  games_target=-1, record_capacity_games=0, max_inner_iters=0,
-                 planes_dtype=L.PLANES_F32, eval_cache_log2_entries=0, level_budget=0, time_budget_cycles=0, device=0):
+                 planes_dtype=L.PLANES_F32, eval_cache_log2_entries=0, level_budget=0, time_budget_cycles=0, device=0,
+                 n_match_nets=0):
         self._lib = L.load()
         self.cfg = L.Config()
         self.cfg.abi_version = L.ABI_VERSION
@@ -47,6 +48,8 @@ class Engine:
         self.cfg.eval_cache_log2_entries = int(eval_cache_log2_entries)
         self.cfg.level_budget = int(level_budget)
         self.cfg.time_budget_cycles = int(time_budget_cycles)
+        self.cfg.reserved[0] = int(n_match_nets)     # > 0: a match engine, one evaluation cache per net (match_steps)
+        self.n_match_nets = int(n_match_nets)
         self.n_slots = int(n_slots)
         self.device = int(device)
         self._h = C.c_void_p()
@@ -113,6 +116,20 @@ class Engine:
             self._h, C.c_void_p(0 if values is None else values.data_ptr()),
             C.c_void_p(0 if priors is None else priors.data_ptr()),
             C.c_void_p(0 if planes is None else planes.data_ptr()), int(slot_lo), int(slot_count), C.c_void_p(stream or 0)))
+
+    def match_assign(self, net_o, net_x):
+        """Per slot, the index of the net that moves o and of the net that moves x (c4_match_assign); slots beyond
+        len(net_o) have no game.  Call after reset() with the openings."""
+        o = np.ascontiguousarray(net_o, dtype=np.int32)
+        x = np.ascontiguousarray(net_x, dtype=np.int32)
+        assert o.shape == x.shape and o.ndim == 1
+        self._check(self._lib.c4_match_assign(self._h, _ptr(o, C.c_int32), _ptr(x, C.c_int32), len(o)))
+
+    def match_steps(self, net, net_index, values, priors, n_steps, stream=0):
+        """One launch of the match kernel for net `net_index` (a FusedNet): the slots where that net is to move search,
+        choose and make their move; all others pass through (c4_match_steps).  Asynchronous on `stream`."""
+        self._check(self._lib.c4_match_steps(self._h, net._h, int(net_index), C.c_void_p(values.data_ptr()),
+                                             C.c_void_p(priors.data_ptr()), int(n_steps), C.c_void_p(stream or 0)))
 
     def run_centre(self, max_launches=64):
         self._check(self._lib.c4_run_centre(self._h, int(max_launches)))

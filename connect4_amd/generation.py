@@ -5,8 +5,11 @@ window, checkpoint -> broadcast of the trained state to every rank (one model, a
 (oinkoink/neural/training.py:78-153) with the hot path replaced.  The evaluation sets of TrainingLoop._evaluate
 (training.py:155-170) are scored here too: after rank 0 has trained and checkpointed, every set of `test_sets` goes through
 Trainer.evaluate / evaluate_value_only (statistics accumulated on the device, connect4_amd/stats.py) and the scores are
-appended to save_dir/<name>.pkl; `train_stats` keeps the reference's per-epoch training statistics (print_stats).  The
-rest of the surrounding bookkeeping (match history, visdom) stays with the reference's loop.
+appended to save_dir/<name>.pkl; `train_stats` keeps the reference's per-epoch training statistics (print_stats).
+TrainingLoop._match (training.py:176-207) is here as well: with `match_every`, rank 0 plays the freshly trained net against
+the net of ten generations ago -- inside the fused kernel (connect4_amd.match.DeviceMatch) -- or, while gen <= 10, against
+evaluate_centre_with_prior on the host lock-step Match, and appends the result to save_dir/match_results.pkl.  Visdom
+stays with the reference's loop.
 """
 import os
 import pickle
@@ -31,7 +34,7 @@ def existing_window(save_dir: str, gen: int):
 def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir: Optional[str] = None, gen: int = 0,
                    seed: int = 0, device: int = 0, n_slots: Optional[int] = None, write_games_pkl: bool = False,
                    timings: Optional[dict] = None, precision: Optional[str] = None, test_sets: Optional[dict] = None,
-                   train_stats: bool = False):
+                   train_stats: bool = False, match_every: Optional[int] = None, match_plies: int = 1):
     """Returns (PackedGames of all ranks, last_loss).  With torch.distributed initialised every rank plays its shard and
     all ranks receive all games.  There is ONE model, as in the reference (training.py:147-153, model.py:143-147): rank 0
     writes save_dir/<gen>/{data.pth, games.pkl} (storage.py:15-16, data.py:47-64), trains on `trainer.device` over the
@@ -40,7 +43,8 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
     generation's shards are all played by the same net.  `precision`: see make_selfplay_net (None = the reference's).
     `test_sets` (name -> stats.LabelledSet or the path of a Connect4Dataset file) and `train_stats`: see score_test_sets and
     Trainer.train(stats=True); both are rank 0's work and add no collective.  A path is loaded on every call: a caller that
-    loops over run_generation passes LabelledSets (load_test_sets once); run_generations loads each path once."""
+    loops over run_generation passes LabelledSets (load_test_sets once); run_generations loads each path once.
+    `match_every` / `match_plies`: see generation_match (rank 0, after the checkpoint, when gen % match_every == 0)."""
     import torch
     multi, rank = _ranks()
     test_sets = load_test_sets(test_sets, trainer.device) if rank == 0 else None
@@ -72,6 +76,8 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
                        positions=int(games.n_positions), training_rows=rows)
     if rank == 0:
         _report(trainer, test_sets, train_stats, save_dir, gen, timings)
+        if match_every and gen % match_every == 0:
+            generation_match(trainer, config, save_dir, gen, device, precision, match_plies, timings)
     return games, loss
 
 
@@ -137,17 +143,68 @@ def score_test_sets(trainer, test_sets, save_dir=None, gen=0):
         st = trainer.evaluate(data) if priors is not None else trainer.evaluate_value_only(data)
         out[name] = plain_dict(st)
         if save_dir is not None:
-            path = os.path.join(save_dir, "%s.pkl" % name)
-            history = []
-            if os.path.exists(path):
-                with open(path, "rb") as f:
-                    history = [e for e in pickle.load(f) if e["generation"] < gen]
-            history.append(dict(generation=int(gen), **out[name]))
-            history.sort(key=lambda e: e["generation"])
-            with open(path + ".tmp", "wb") as f:
-                pickle.dump(history, f)
-            os.replace(path + ".tmp", path)
+            append_history(os.path.join(save_dir, "%s.pkl" % name), gen, out[name])
     return out
+
+
+def append_history(path, gen, row):
+    """The history files of a run (score_test_sets' <name>.pkl, generation_match's match_results.pkl): a pickled list of
+    {"generation": gen, **row}, re-read and extended.  An entry of this generation is replaced and entries of later
+    generations are dropped; the file is replaced atomically.  Returns the list written."""
+    history = []
+    if os.path.exists(path):
+        with open(path, "rb") as f:
+            history = [e for e in pickle.load(f) if e["generation"] < gen]
+    history.append(dict(generation=int(gen), **row))
+    history.sort(key=lambda e: e["generation"])
+    with open(path + ".tmp", "wb") as f:
+        pickle.dump(history, f)
+    os.replace(path + ".tmp", path)
+    return history
+
+
+# -- strength after a generation (training.py:176-207) ----------------------------------------------------------------
+def generation_match(trainer, config, save_dir, gen, device=0, precision=None, plies=1, timings=None):
+    """TrainingLoop._match: the trainer's net ("AlphaZero", the run's simulations / pb_c_base / pb_c_init, no noise, no
+    sampled moves) against "Evaluate_centre_with_prior" while gen <= 10 and against "Older net" -- save_dir/<gen-10>/net.pth,
+    MCTSConfig(simulations) -- afterwards, as Match(plies, switch=True).  Two nets meet inside the fused kernel
+    (match.DeviceMatch); the centre opponent, and any pairing the device path refuses (match.device_match_reason), go
+    through the host lock-step Match.  The result -- wins / draws / losses / return from the new net's side -- is appended
+    to save_dir/match_results.pkl (append_history) and, with "opponent" and the "path" taken ("device" / "host"), put into
+    timings["match"].  Rank 0's work; no collective."""
+    import torch
+    from .evaluators import DeviceNetEvaluator, Evaluator, evaluate_centre_with_prior
+    from .match import play_match
+    from .mcts import MCTS
+    nets = [make_selfplay_net(trainer.net.state_dict(), device=device, precision=precision)]
+    players = [MCTS("AlphaZero", MCTSConfig(config.simulations, config.pb_c_base, config.pb_c_init),
+                    DeviceNetEvaluator(nets[0], device), device=device)]
+    try:
+        if gen <= 10:
+            players.append(MCTS("Evaluate_centre_with_prior", MCTSConfig(config.simulations), Evaluator(evaluate_centre_with_prior),
+                                device=device))
+        else:
+            if save_dir is None:
+                raise ValueError("the match of generation %d needs save_dir/%d/net.pth" % (gen, gen - 10))
+            old = torch.load(os.path.join(save_dir, str(gen - 10), "net.pth"), map_location="cpu", weights_only=True)
+            nets.append(make_selfplay_net(old["net_state_dict"], device=device, precision=precision))
+            players.append(MCTS("Older net", MCTSConfig(config.simulations), DeviceNetEvaluator(nets[1], device), device=device))
+        t0 = time.perf_counter()
+        result, path = play_match(False, players[0], players[1], plies=plies, switch=True)
+        seconds = time.perf_counter() - t0
+    finally:
+        for p in players:
+            if p._searcher is not None:
+                p._searcher.close()
+        for n in nets:
+            if hasattr(n, "close"):
+                n.close()
+    row = {k: (float(v) if k == "return" else int(v)) for k, v in result.items()}
+    if save_dir is not None:
+        append_history(os.path.join(save_dir, "match_results.pkl"), gen, row)
+    if timings is not None:
+        timings["match"] = dict(row, opponent=players[1].name, path=path, match_s=seconds)
+    return row, path
 
 
 def _report(trainer, test_sets, train_stats, save_dir, gen, timings):
@@ -192,7 +249,8 @@ def latest_generation(save_dir: str):
 def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir: str, n_generations: int,
                     first_gen: Optional[int] = None, seed: int = 0, device: int = 0, n_slots: Optional[int] = None,
                     precision: Optional[str] = None, write_games_pkl: bool = False, timings: Optional[list] = None,
-                    test_sets: Optional[dict] = None, train_stats: bool = False):
+                    test_sets: Optional[dict] = None, train_stats: bool = False, match_every: Optional[int] = None,
+                    match_plies: int = 1):
     """n_generations generations of run_generation -- same seeds (seed + 1000 * gen), same files (data.pth, net.pth,
     optional games.pkl), same broadcast of the trained state -- with the sliding window (data.py:66-75) kept on rank 0's GPU
     as packed positions (replay.ReplayWindow): each generation's games are appended to it and trained with
@@ -205,8 +263,9 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
     first_gen starts there with the trainer as it is and, like run_generation, with what earlier generations save_dir
     holds.  `timings`: a list that receives one dict per generation -- run_generation's keys, plus window_rows and
     window_bytes, and with `test_sets` / `train_stats` (as run_generation: scored on rank 0 after each checkpoint, appended
-    to save_dir/<name>.pkl) the sets' names and train_stats.  Returns (the window -- None on other ranks --, [last loss of
-    each generation])."""
+    to save_dir/<name>.pkl) the sets' names and train_stats, and with `match_every` (generation_match on rank 0 after the
+    checkpoint of every generation with gen % match_every == 0; save_dir/match_results.pkl) "match".  Returns (the window --
+    None on other ranks --, [last loss of each generation])."""
     import torch
     from .replay import ReplayWindow
     multi, rank = _ranks()
@@ -246,6 +305,8 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
                       positions=int(games.n_positions), training_rows=rows, window_rows=rows, window_bytes=nbytes)
         if rank == 0:
             _report(trainer, test_sets, train_stats, save_dir, gen, report)
+            if match_every and gen % match_every == 0:
+                generation_match(trainer, config, save_dir, gen, device, precision, match_plies, report)
         if timings is not None:
             timings.append(report)
     return window, losses

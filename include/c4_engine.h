@@ -101,7 +101,9 @@ typedef struct {
                                           the waves of a launch by cost instead of by count).  Wave-autonomous
                                           fused kernel: length of one step in shader cycles.  Which launch runs
                                           a simulation never changes results.  0 = off / 80,000 */
-    int32_t reserved[4];               /* must be 0 */
+    int32_t reserved[4];               /* must be 0; reserved[0] = n_match_nets: > 0 creates a match engine (c4_match_steps) with that
+                                          many evaluation caches, one per net (at most C4_MATCH_MAX_NETS); the auto size is
+                                          divided among them.  Needs C4_EVAL_EXTERNAL_F32 and stop_after_move = 0 */
 } c4_config;
 
 typedef struct c4_engine c4_engine;
@@ -457,6 +459,25 @@ const char *c4_net_last_error(void);
  * workgroup after this call (c4_get_stats sums them; the sums are exact). */
 int c4_selfplay_steps(c4_engine *e, c4_net *net, float *values_dev, float *priors_dev, int32_t n_steps,
                       void *hip_stream);
+/* -- net-vs-net matches (the reference's Match, match.py:15-70; TrainingLoop._match, neural/training.py:176-207) ----
+ * An engine created with c4_config.reserved[0] = n_match_nets > 0 (continuous: stop_after_move = 0, games_target = the
+ * number of games, no root noise, num_sampling_moves = 0) plays one game per slot between nets 0 .. n_match_nets - 1,
+ * each with an evaluation cache of its own (c4_clear_eval_cache clears them all).
+ * c4_match_assign: net_o[i] / net_x[i] (host, n <= n_slots entries) = the net that moves o / x in slot i; the other
+ * slots have no game.  Call it after c4_reset with the openings; synchronous.
+ * c4_match_steps: one launch of c4_match_wave_kernel for net `net_index` -- c4_selfplay_steps' wave-autonomous kernel
+ * restricted to the slots where that net is to move (o moves when the root holds an even number of stones).  A slot
+ * that chooses its move records it, makes it and waits for a launch of the opponent's net; every other slot passes
+ * through unchanged.  The host cycles over the nets until c4_stats.active_slots == 0; every slot plays ONE game and
+ * parks, and the games come out of the record ring (c4_drain_games / c4_export_games_dev; game_id = slot).
+ * Which launch runs a simulation, and in which order the nets are served, never changes a game: the games are those
+ * that alternating c4_step / c4_net_forward searches of the two nets play, position by position.
+ * values_dev / priors_dev as c4_selfplay_steps (one pair of buffers for all nets, persisting between the calls).
+ * The 64-filter C4_NET_F32X3_WIDE net cannot be held (C4_ESTATE), as with C4_FUSED_MODE=wave. */
+#define C4_MATCH_MAX_NETS 16
+int c4_match_assign(c4_engine *e, const int32_t *net_o, const int32_t *net_x, int32_t n);
+int c4_match_steps(c4_engine *e, c4_net *net, int32_t net_index, float *values_dev, float *priors_dev, int32_t n_steps,
+                   void *hip_stream);
 /* diagnostic build aid: per-phase s_memtime stamps of workgroup 0, [8 waves][16]; needs the
  * environment variable C4_NET_STAMPS=1 when the net is created, else C4_ESTATE. */
 int c4_net_debug_stamps(c4_net *net, unsigned long long *out);
