@@ -60,6 +60,23 @@ class RootResult(C.Structure):
                 ("expansions", C.c_int64), ("simulations", C.c_int64)]
 
 
+class SearchResult(C.Structure):
+    """c4_search_result: one row of a position queue's result table -- the fields of RootResult, so whatever reads a
+    root read-out (connect4_amd.tree.Tree) reads a row (search_result_dtype is the same layout for NumPy)."""
+    _fields_ = list(RootResult._fields_)
+
+
+def search_result_dtype():
+    import numpy as np
+    dt = np.dtype({"names": ["state", "move", "value", "root_visits", "root_value_sum", "child_visits", "child_value_sum",
+                             "child_status", "root_prior", "values_policy", "color0", "color1", "expansions", "simulations"],
+                   "formats": ["<i4", "<i4", "<f8", "<u4", "<f8", ("<u4", (7,)), ("<f8", (7,)), ("<i4", (7,)), ("<f8", (7,)),
+                               ("<f8", (7,)), "<u8", "<u8", "<i8", "<i8"],
+                   "offsets": [getattr(SearchResult, n).offset for n, _ in SearchResult._fields_],
+                   "itemsize": C.sizeof(SearchResult)})
+    return dt
+
+
 class TreeNode(C.Structure):
     """c4_tree_node: one row of an exported tree (TREE_NODE_DTYPE is the same layout for NumPy)."""
     _fields_ = [("parent", C.c_int32), ("first_child", C.c_int32), ("visits", C.c_int32), ("move", C.c_int8),
@@ -169,6 +186,12 @@ SIGNATURES = {
     "c4_selfplay_steps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "c4_match_assign": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int32]),
     "c4_match_steps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "c4_queue_positions": (C.c_int, [C.c_void_p, _u64p, _u64p, C.c_int64]),
+    "c4_queue_positions_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "c4_queue_progress": (C.c_int, [C.c_void_p, _i64p, _i64p]),
+    "c4_queue_results": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "c4_queue_results_dev": (C.c_int, [C.c_void_p, _P(C.c_void_p), _i64p]),
+    "c4_queue_export_dev": (C.c_int, [C.c_void_p] * 7),
     "c4_net_debug_stamps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "c4_bn_workspace_floats": (C.c_longlong, [C.c_int, C.c_int]),
     "c4_bn_train_forward": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p]),

@@ -226,6 +226,11 @@ struct Cold {
     unsigned long long *ring_head, *ring_tail, *dropped;
     unsigned long long *next_game;
     unsigned long long *stamps;   // diagnostic (C4_TREE_STAMPS=1): [block][8] s_memtime values, first 256 blocks
+    // position queue (c4_queue_positions): a stop-after-move slot that has chosen its move writes row `game id` of
+    // `results`, takes the next index from next_game and starts on queue[index]; queue_n == 0: no queue
+    const uint64_t *queue;        // [queue_n][2] color0, color1
+    c4_search_result *results;    // [queue_n]
+    long long queue_n;
 };
 
 struct Dev {
@@ -717,6 +722,62 @@ template <> __device__ __forceinline__ void store_plane<float>(void *p, size_t i
 template <> __device__ __forceinline__ void store_plane<__half>(void *p, size_t i, float v) { ((__half *)p)[i] = __float2half(v); }
 template <> __device__ __forceinline__ void store_plane<hip_bfloat16>(void *p, size_t i, float v) { ((hip_bfloat16 *)p)[i] = hip_bfloat16(v); }
 
+// Position queue: the root read-out of a finished search (what c4_gather_roots_kernel collects for c4_read_roots) written by
+// the slot's own group into its row of the result table.  Everything comes from the pool -- the root record, and lane k's
+// child record k, whose column is info_move -- so the caller keeps nothing alive for it; not inlined: the call sits in the
+// move-choice block, outside the level loop's live ranges.  The lanes of the columns the root cannot play write "absent".
+// expansions: the per-slot counters are per workgroup in the fused kernels, so the count is taken from the tree itself: an
+// expand_node call is the first descent THROUGH an evaluated node (tree_step: cN == 1), after which its visit count is >= 2,
+// and no other record has status ST_EVALUATED -- so it is the number of evaluated records with n >= 2 (NOT the number of
+// sibling blocks: a block is allocated when a node is evaluated, and most evaluated leaves are never visited again).
+// Blocks 1 .. nalloc - 1 were written whole by this search (C4_FILLERS); of block 0 only the root record exists.
+// `state` is stored last, behind a fence: a row is untouched or whole.
+__device__ __noinline__ void queue_write_row(c4_search_result *row, const uint8_t *pool_base, uint32_t nalloc, uint64_t root0,
+                                             uint64_t root1, int mv, double absv, double pol_col, uint32_t sims, int lane)
+{
+    static_assert(C4_FILLERS, "the expansion count reads all eight records of every allocated block");
+    const Rec *rec = reinterpret_cast<const Rec *>(pool_base);
+    const uint32_t rinfo = rec[0].info, rn = rec[0].n;
+    const uint32_t cb = info_base(rinfo), nc = info_nchild(rinfo);
+    const int rmask = legal_mask(root0 | root1);
+    if (lane < 7) {
+        row->values_policy[lane] = pol_col;
+        if (!((rmask >> lane) & 1)) {
+            row->child_visits[lane] = 0;
+            row->child_value_sum[lane] = 0.0;
+            row->child_status[lane] = -2;
+            row->root_prior[lane] = 0.0;
+        }
+    }
+    if (lane < (int)nc) {
+        const Rec c = rec[cb + lane];
+        const uint32_t m = info_move(c.info), cst = info_status(c.info);
+        if (m < 7) {
+            row->child_visits[m] = c.n;
+            row->child_value_sum[m] = c.w;
+            row->child_status[m] = cst >= ST_XWIN ? (int32_t)(cst - ST_XWIN) : -1;
+            row->root_prior[m] = c.p;
+        }
+    }
+    uint32_t cnt = 0;
+    for (uint32_t i = GROUP + (uint32_t)lane; i < nalloc * GROUP; i += GROUP)
+        cnt += (info_status(rec[i].info) == ST_EVALUATED && rec[i].n >= 2u) ? 1u : 0u;
+#pragma unroll
+    for (int s = 1; s < GROUP; s <<= 1) cnt += (uint32_t)__shfl_xor((int)cnt, s, GROUP);
+    if (lane == 0) {
+        row->move = mv;
+        row->value = absv;
+        row->root_visits = rn;
+        row->root_value_sum = rec[0].w;
+        row->color0 = root0;
+        row->color1 = root1;
+        row->expansions = (int64_t)(cnt + ((info_status(rinfo) == ST_EVALUATED && rn >= 2u) ? 1u : 0u));
+        row->simulations = (int64_t)sims;
+    }
+    __threadfence();
+    if (lane == 0) row->state = SLOT_MOVE_DONE;
+}
+
 // ------------------------------------------------------------------------------------------
 // the rollout-step kernel
 // ------------------------------------------------------------------------------------------
@@ -736,8 +797,10 @@ template <> __device__ __forceinline__ void store_plane<hip_bfloat16>(void *p, s
 // every iteration it looks at `*req` and applies the answer once a network wave has written REQ_ANSWERED.  The call
 // ends at the deadline; a slot still waiting then carries its leaf into the next launch.
 constexpr uint32_t REQ_IDLE = 0, REQ_POSTED = 1, REQ_TAKEN = 2, REQ_ANSWERED = 3;
+// QUEUE (kernels instantiated for position-queue engines only, so that every other instantiation is the code it was): a slot
+// that has chosen its move leaves its read-out in the result table and starts on the next queued position.
 template <int EVAL, bool STAMPS = true, bool LDS_STATE = false, bool WAVE_SYNC = false, bool PATH_KEPT = false, class DevT = const Dev,
-          bool SPLIT = false>
+          bool SPLIT = false, bool QUEUE = false>
 __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, const int gl,
                                           PathEntry (*s_path)[MAX_DEPTH], Rec (*s_l1)[GROUP],
                                           const void *__restrict__ values_in,
@@ -1126,6 +1189,24 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
             if (lane < 7) d.cold->res_policy[(size_t)g * 7 + lane] = pol_col;
             st.moves += 1;
             if (d.stop_after_move) {   // MCTS.make_move returns here; the tree stays readable
+                const long long qn = QUEUE ? d.cold->queue_n : 0;
+                if (QUEUE && qn > 0) {   // position queue: leave the read-out in row `gid`, start on the next queued position
+                    queue_write_row(d.cold->results + gid, pool.base, nalloc, root0, root1, mv, absv, pol_col, sims, lane);
+                    unsigned long long ng = 0;
+                    if (lane == 0) ng = atomicAdd(d.cold->next_game, 1ULL);
+                    ng = ((unsigned long long)gshfl((uint32_t)(ng >> 32), 0) << 32) | gshfl((uint32_t)ng, 0);
+                    if ((long long)ng >= qn) {
+                        state = SLOT_PARKED;
+                        break;
+                    }
+                    gid = (long long)ng;
+                    ply = 0;
+                    root0 = d.cold->queue[2 * ng];
+                    root1 = d.cold->queue[2 * ng + 1];
+                    st.games_started += 1;
+                    need_root = 1;
+                    continue;
+                }
                 state = SLOT_MOVE_DONE;
                 break;
             }
@@ -1553,7 +1634,7 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
     stamp(5);
 }
 
-template <int EVAL>
+template <int EVAL, bool QUEUE = false>
 __global__ __launch_bounds__(BLOCK) void c4_step_kernel(Dev d, const void *__restrict__ values_in,
                                                         const void *__restrict__ priors_in,
                                                         void *__restrict__ planes_out)
@@ -1563,7 +1644,7 @@ __global__ __launch_bounds__(BLOCK) void c4_step_kernel(Dev d, const void *__res
     const int lane = threadIdx.x & (GROUP - 1);
     const int gl = threadIdx.x / GROUP;
     const int g = d.slot_lo + blockIdx.x * SLOTS_PER_BLOCK + gl;
-    tree_step<EVAL>(d, g, lane, gl, s_path, s_l1, values_in, priors_in, planes_out, nullptr);
+    tree_step<EVAL, true, false, false, false, const Dev, false, QUEUE>(d, g, lane, gl, s_path, s_l1, values_in, priors_in, planes_out, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1576,7 +1657,7 @@ __global__ __launch_bounds__(BLOCK) void c4_step_kernel(Dev d, const void *__res
 // more slots per wave cost it little while every network pass stays a full 16-position batch:
 // TS = 32 when the batch is large enough to give every CU such a workgroup, else 16.
 // ------------------------------------------------------------------------------------------
-template <int TS>
+template <int TS, bool QUEUE = false>
 __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_kernel(Dev d, c4net::NetDev nd, float *__restrict__ values,
                                                                       float *__restrict__ priors, int n_steps)
 {
@@ -1633,7 +1714,7 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_kernel(Dev d, c4n
         const int grp = (tid & 63) / GROUP;
         const int sl = (tid >> 6) + NWAVES * grp;     // slot of this 8-lane group inside the workgroup
         if (grp < TS / NWAVES)
-            tree_step<C4_EVAL_EXTERNAL_F32, false, true>(d, slot0 + sl, lane, sl, s_path, s_l1, s_val, s_pri, nullptr, nullptr,
+            tree_step<C4_EVAL_EXTERNAL_F32, false, true, false, false, const Dev, false, QUEUE>(d, slot0 + sl, lane, sl, s_path, s_l1, s_val, s_pri, nullptr, nullptr,
                                                          &smem[sl], sl, s_stats);
         const unsigned long long tb = d.has_stamps ? __builtin_amdgcn_s_memtime() : 0;
         __syncthreads();   // slot states (LDS) are visible to the whole workgroup
@@ -1698,7 +1779,7 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_kernel(Dev d, c4n
 // bit-identical to net_forward_block's).
 // ------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(4))) const Dev const_dev;
-template <int TS, int MODE>
+template <int TS, int MODE, bool QUEUE = false>
 __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_wave_kernel(const Dev *d_dev, c4net::NetDev nd, float *__restrict__ values,
                                                                            float *__restrict__ priors, int n_steps)
 {
@@ -1774,7 +1855,7 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_wave_kernel(const
         const int grp = (tid & 63) / GROUP;
         const int sl = (tid >> 6) + NWAVES * grp;     // slot of this 8-lane group inside the workgroup
         if (grp < SPW)
-            tree_step<C4_EVAL_EXTERNAL_F32, false, true, true, OWN_PATH>(d, slot0 + sl, lane, OWN_PATH ? sl : grp, s_path, s_l1, s_val, s_pri, nullptr,
+            tree_step<C4_EVAL_EXTERNAL_F32, false, true, true, OWN_PATH, const_dev, false, QUEUE>(d, slot0 + sl, lane, OWN_PATH ? sl : grp, s_path, s_l1, s_val, s_pri, nullptr,
                                                                          nullptr, &smem[sl], sl, s_stats, t_launch + quantum);
         lds_fence();   // the slot states written by the groups' first lanes are read by the whole wave
         const unsigned long long tb = d.has_stamps ? __builtin_amdgcn_s_memtime() : 0;
@@ -2045,7 +2126,7 @@ __device__ __forceinline__ void sanitise_answer(float *s_val, float *s_pri, int 
 // so between launches "has a leaf" means "answered", exactly as with the wave kernel (the two are interchangeable
 // launch by launch and play the same games).
 // ------------------------------------------------------------------------------------------
-template <int TS, int MODE, int TW = 4>
+template <int TS, int MODE, int TW = 4, bool QUEUE = false>
 __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(const Dev *d_dev, c4net::NetDev nd, float *__restrict__ values,
                                                                             float *__restrict__ priors, int n_steps, int spread)
 {
@@ -2203,7 +2284,7 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
                 continue;
             }
             if (grp < SPW && sl < TS)
-                tree_step<C4_EVAL_EXTERNAL_F32, false, true, true, true, const_dev, true>(d, wg_first + sl * wg_stride, lane, sl, s_path, s_l1, s_val, s_pri, nullptr,
+                tree_step<C4_EVAL_EXTERNAL_F32, false, true, true, true, const_dev, true, QUEUE>(d, wg_first + sl * wg_stride, lane, sl, s_path, s_l1, s_val, s_pri, nullptr,
                                                                                           nullptr, &smem[sl], sl, s_stats, t_launch + quantum,
                                                                                           &s_req[sl], TS);
             lds_fence();
@@ -2426,6 +2507,62 @@ __global__ void c4_gather_roots_kernel(Dev d, c4_root_result *out)
     r.expansions = (int64_t)sp[offsetof(SlotStats, expansions) / 8];
     r.simulations = (int64_t)sp[offsetof(SlotStats, sims) / 8];
     out[g] = r;
+}
+
+// -- position queue ----------------------------------------------------------------------------
+// the rule of c4_reset, on the device: out[0] = index of the first decided or inconsistent position (the caller sets it to n)
+__global__ void k_queue_validate(const uint64_t *boards, long long n, unsigned long long *out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t c0 = boards[2 * i], c1 = boards[2 * i + 1];
+    if (position_status(c0, c1) != ST_FRESH || (c0 & c1)) atomicMin(out, (unsigned long long)i);
+}
+
+// the first n_active slots start on the first n_active queued positions (after c4_reset_kernel: game id = slot = index)
+__global__ void k_queue_roots(Dev d, const uint64_t *boards, int n_active)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= d.G || g >= n_active) return;
+    d.root_c0[g] = boards[2 * (size_t)g];
+    d.root_c1[g] = boards[2 * (size_t)g + 1];
+}
+
+__global__ void k_queue_count(const c4_search_result *rows, long long n, unsigned long long *out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool done = i < n && rows[i].state == SLOT_MOVE_DONE;
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(done);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(out, (unsigned long long)__popcll(b));
+}
+
+// rows -> the replay window's packed float32 layout; one thread per row
+__global__ void k_queue_export(const c4_search_result *rows, long long n, float *policy, float *visit_policy, float *root_values,
+                               float *move_values, uint8_t *moves)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const c4_search_result &r = rows[i];
+    const bool done = r.state == SLOT_MOVE_DONE;
+    const float nan = __int_as_float(0x7fc00000);
+    if (policy)
+        for (int c = 0; c < 7; ++c) policy[i * 7 + c] = done ? (float)r.values_policy[c] : 0.0f;
+    if (visit_policy) {   // tree.py:111-117: the visit counts, normalised as the values policy is (tree.py:139-147)
+        double s = 0.0;
+        int nc = 0;
+        for (int c = 0; c < 7; ++c) {
+            s = s + (double)r.child_visits[c];
+            nc += r.child_status[c] != -2;
+        }
+        for (int c = 0; c < 7; ++c) {
+            double p = 0.0;
+            if (done) p = s == 0.0 ? (r.child_status[c] != -2 ? 1.0 / (double)nc : 0.0) : (double)r.child_visits[c] / s;
+            visit_policy[i * 7 + c] = (float)p;
+        }
+    }
+    if (root_values) root_values[i] = done ? (float)(r.root_value_sum / (double)r.root_visits) : nan;
+    if (move_values) move_values[i] = done ? (float)r.value : nan;
+    if (moves) moves[i] = done ? (uint8_t)r.move : (uint8_t)255;
 }
 
 __global__ void k_make_move(const uint64_t *c0, const uint64_t *c1, const int32_t *col, int n, uint64_t *o0,
@@ -2686,6 +2823,12 @@ struct c4_engine {
     Dev d_match_uploaded;
     uint8_t *match_side_o, *match_side_x;         // [G] net that moves o / x in each slot, 0xff = none
     int match_assigned;
+    // position queue (c4_queue_positions); is_queue = c4_config.reserved[1]
+    int is_queue;
+    uint64_t *queue_dev;                          // [queue_n][2], the engine's own copy of the queued positions
+    c4_search_result *results_dev;                // [queue_n]
+    long long queue_n;
+    unsigned long long *queue_scratch;            // device: one word (first bad index / finished rows)
     char err[512];
 };
 
@@ -2741,6 +2884,21 @@ int check_device(int device, char *err)
         return C4_EDEVICE;
     }
     return C4_OK;
+}
+
+// forget the position queue and its result table (the device is idle)
+int queue_drop(c4_engine *e)
+{
+    e->cold.queue = nullptr;
+    e->cold.results = nullptr;
+    e->cold.queue_n = 0;
+    int rc = sync_cold(e);
+    if (e->queue_dev) (void)hipFree(e->queue_dev);
+    if (e->results_dev) (void)hipFree(e->results_dev);
+    e->queue_dev = nullptr;
+    e->results_dev = nullptr;
+    e->queue_n = 0;
+    return rc;
 }
 
 // scratch helper for the pure board entry points
@@ -2810,6 +2968,10 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
     const int n_match = cfg->reserved[0];
     if (n_match < 0 || n_match > C4_MATCH_MAX_NETS) { set_err(g_err, "n_match_nets (reserved[0]) = %d out of range [0,%d]", n_match, C4_MATCH_MAX_NETS); return C4_EINVAL; }
     if (n_match > 0 && (cfg->eval_mode != C4_EVAL_EXTERNAL_F32 || cfg->stop_after_move)) { set_err(g_err, "a match engine (n_match_nets > 0) needs C4_EVAL_EXTERNAL_F32 and stop_after_move = 0"); return C4_EINVAL; }
+    const int is_queue = cfg->reserved[1];
+    if (is_queue != 0 && is_queue != 1) { set_err(g_err, "reserved[1] = %d: 1 creates a position-queue engine, 0 none", is_queue); return C4_EINVAL; }
+    if (is_queue && n_match > 0) { set_err(g_err, "a match engine (reserved[0]) cannot be a position-queue engine (reserved[1]) as well"); return C4_EINVAL; }
+    if (is_queue && !cfg->stop_after_move) { set_err(g_err, "a position-queue engine (reserved[1] = 1) needs stop_after_move = 1: one search per position"); return C4_EINVAL; }
 
     c4_engine *e = new c4_engine();
     e->cfg = *cfg;
@@ -2819,6 +2981,11 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
     memset(&e->d_match_uploaded, 0xff, sizeof(Dev));
     e->match_side_o = e->match_side_x = nullptr;
     e->match_assigned = 0;
+    e->is_queue = is_queue;
+    e->queue_dev = nullptr;
+    e->results_dev = nullptr;
+    e->queue_n = 0;
+    e->queue_scratch = nullptr;
     e->device = device;
     e->stream = nullptr;
     e->launches = 0;
@@ -2896,6 +3063,7 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
     ALLOC(e->cold.ring_head, 1); ALLOC(e->cold.ring_tail, 1); ALLOC(e->cold.dropped, 1);
     ALLOC(e->active_dev, 1);
     ALLOC(e->export_scratch, R + 4);
+    ALLOC(e->queue_scratch, 1);
     // score tables (host libm so that log() is the very function Python's math.log calls)
     {
         const size_t nt = (size_t)cfg->simulations + 4;
@@ -2911,7 +3079,7 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
     }
     {   // evaluation cache: <0 off, 0 auto (self-play with a float32 evaluator only), else log2(entries)
         int bits = cfg->eval_cache_log2_entries;
-        if (bits == 0 && cfg->eval_mode == C4_EVAL_EXTERNAL_F32 && !cfg->stop_after_move) {
+        if (bits == 0 && cfg->eval_mode == C4_EVAL_EXTERNAL_F32 && (!cfg->stop_after_move || is_queue)) {   // (a position queue shares the table across its positions)
             // The reference's table lives as long as its player and is shared by all its games
             // (evaluators.py:9-25), so positions of earlier games keep answering: size it for many
             // games' worth of evaluations -- 256 x slots x simulations entries (2^30 = 51.5 GB for the 4096-game
@@ -2974,6 +3142,8 @@ int c4_engine_destroy(c4_engine *e)
     for (void *p : e->allocs) (void)hipFree(p);
     if (e->tape_noise) (void)hipFree(e->tape_noise);
     if (e->tape_u) (void)hipFree(e->tape_u);
+    if (e->queue_dev) (void)hipFree(e->queue_dev);
+    if (e->results_dev) (void)hipFree(e->results_dev);
     delete e;
     return C4_OK;
 }
@@ -3004,6 +3174,10 @@ int c4_reset(c4_engine *e, const uint64_t *color0, const uint64_t *color1, int32
     if ((color0 == nullptr) != (color1 == nullptr)) { set_err(e->err, "color0/color1 must both be given or both NULL"); return C4_EINVAL; }
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipDeviceSynchronize());
+    if (e->queue_n > 0) {   // a reset drops the queue: the engine is a plain stop-after-move engine again
+        int rc = queue_drop(e);
+        if (rc) return rc;
+    }
     uint64_t *d0 = nullptr, *d1 = nullptr;
     if (color0) {
         for (int i = 0; i < n_active; ++i)
@@ -3058,17 +3232,18 @@ int c4_step_range(c4_engine *e, const void *values_dev, const void *priors_dev, 
     d.slot_hi = slot_lo + slot_count;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
     const dim3 grid((slot_count + SLOTS_PER_BLOCK - 1) / SLOTS_PER_BLOCK), block(BLOCK);
+    // (a position-queue engine runs the QUEUE instantiations; every other engine the kernels it always ran)
+#define C4_LAUNCH_STEP(EVAL)                                                                                                      \
+    do {                                                                                                                          \
+        if (e->is_queue) hipLaunchKernelGGL((c4_step_kernel<EVAL, true>), grid, block, 0, st, d, values_dev, priors_dev, planes_dev); \
+        else hipLaunchKernelGGL((c4_step_kernel<EVAL>), grid, block, 0, st, d, values_dev, priors_dev, planes_dev);                \
+    } while (0)
     switch (e->cfg.eval_mode) {
-    case C4_EVAL_EXTERNAL_F32:
-        hipLaunchKernelGGL(c4_step_kernel<C4_EVAL_EXTERNAL_F32>, grid, block, 0, st, d, values_dev, priors_dev, planes_dev);
-        break;
-    case C4_EVAL_EXTERNAL_F64:
-        hipLaunchKernelGGL(c4_step_kernel<C4_EVAL_EXTERNAL_F64>, grid, block, 0, st, d, values_dev, priors_dev, planes_dev);
-        break;
-    default:
-        hipLaunchKernelGGL(c4_step_kernel<C4_EVAL_CENTRE>, grid, block, 0, st, d, values_dev, priors_dev, planes_dev);
-        break;
+    case C4_EVAL_EXTERNAL_F32: C4_LAUNCH_STEP(C4_EVAL_EXTERNAL_F32); break;
+    case C4_EVAL_EXTERNAL_F64: C4_LAUNCH_STEP(C4_EVAL_EXTERNAL_F64); break;
+    default: C4_LAUNCH_STEP(C4_EVAL_CENTRE); break;
     }
+#undef C4_LAUNCH_STEP
     HIPCHK(e, hipGetLastError());
     e->launches += 1;
     return C4_OK;
@@ -3095,15 +3270,24 @@ int c4_selfplay_steps(c4_engine *e, c4_net *net, float *values_dev, float *prior
         // tree waves of the split kernel: 4 (one per SIMD) for the 32-filter nets (f32x3: 230 M expansions/s against 222 M with
         // 2 tree waves); the 64-filter forward is slow enough to want more network waves: 2 tree waves of 8 slots and 6
         // network waves at 16 slots per CU (111 against 104 M)
-        const int tw = e->split_tw ? e->split_tw : (nd.mode == c4net::NETMODE_F64 ? 2 : 4);
+        // (the position-queue instantiations exist for the default split only: C4_SPLIT_TW is a tuning aid of self-play)
+        const int tw = (e->split_tw && !e->is_queue) ? e->split_tw : (nd.mode == c4net::NETMODE_F64 ? 2 : 4);
         // the split kernel spreads a batch that would leave CUs without a workgroup over all of them (slot = workgroup + p x workgroups)
         const int dense_wgs = (e->d.G + e->fused_slots - 1) / e->fused_slots;
         const int spread = (!e->pack_dense && dense_wgs < e->cus && e->d.G > dense_wgs) ? 1 : 0;
         const dim3 gsp(spread ? std::min(e->cus, e->d.G) : dense_wgs);
 #define C4_LAUNCH_SPLIT(TSV, MODE, TWV) hipLaunchKernelGGL((c4_selfplay_split_kernel<TSV, MODE, TWV>), gsp, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps, spread)
+#define C4_LAUNCH_SPLIT_Q(TSV, MODE, TWV) hipLaunchKernelGGL((c4_selfplay_split_kernel<TSV, MODE, TWV, true>), gsp, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps, spread)
 #define C4_LAUNCH_WAVE(MODE)                                                                                                       \
     do {                                                                                                                           \
-        if (e->fused_wave == 2) {                                                                                                  \
+        if (e->is_queue) {                                                                                                         \
+            if (e->fused_wave == 2) {                                                                                              \
+                if (e->fused_slots == 32) C4_LAUNCH_SPLIT_Q(32, MODE, 4);                                                          \
+                else if (tw == 2) C4_LAUNCH_SPLIT_Q(16, MODE, 2);                                                                  \
+                else C4_LAUNCH_SPLIT_Q(16, MODE, 4);                                                                               \
+            } else if (e->fused_slots == 32) hipLaunchKernelGGL((c4_selfplay_wave_kernel<32, MODE, true>), g32, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps); \
+            else hipLaunchKernelGGL((c4_selfplay_wave_kernel<16, MODE, true>), g16, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps); \
+        } else if (e->fused_wave == 2) {                                                                                           \
             if (e->fused_slots == 32) C4_LAUNCH_SPLIT(32, MODE, 4);   /* (a wave holds at most 8 slots: no fewer than 4 tree waves) */ \
             else if (tw == 2) C4_LAUNCH_SPLIT(16, MODE, 2);                                                                        \
             else if (tw == 3) C4_LAUNCH_SPLIT(16, MODE, 3);                                                                        \
@@ -3118,16 +3302,23 @@ int c4_selfplay_steps(c4_engine *e, c4_net *net, float *values_dev, float *prior
                 set_err(e->err, "C4_FUSED_MODE=wave cannot hold the 64-filter reference-precision net (eight waves' planes exceed a CU's LDS); use the default split kernel");
                 return C4_ESTATE;
             }
-            if (e->fused_slots == 32) C4_LAUNCH_SPLIT(32, c4net::NETMODE_F64_PRECISE, 4);
+            if (e->is_queue) {
+                if (e->fused_slots == 32) C4_LAUNCH_SPLIT_Q(32, c4net::NETMODE_F64_PRECISE, 4);
+                else C4_LAUNCH_SPLIT_Q(16, c4net::NETMODE_F64_PRECISE, 4);
+            } else if (e->fused_slots == 32) C4_LAUNCH_SPLIT(32, c4net::NETMODE_F64_PRECISE, 4);
             else C4_LAUNCH_SPLIT(16, c4net::NETMODE_F64_PRECISE, 4);
         } else if (nd.mode == c4net::NETMODE_F64) C4_LAUNCH_WAVE(c4net::NETMODE_F64);
         else if (nd.mode == c4net::NETMODE_F32_PRECISE) C4_LAUNCH_WAVE(c4net::NETMODE_F32_PRECISE);
         else C4_LAUNCH_WAVE(c4net::NETMODE_F32_F16);
 #undef C4_LAUNCH_WAVE
+#undef C4_LAUNCH_SPLIT_Q
 #undef C4_LAUNCH_SPLIT
     } else if (nd.mode != c4net::NETMODE_F32_F16) {
         set_err(e->err, "C4_FUSED_MODE=block serves only the 32-filter fp16 net; use the default wave-autonomous kernel");
         return C4_ESTATE;
+    } else if (e->is_queue) {
+        if (e->fused_slots == 32) hipLaunchKernelGGL((c4_selfplay_kernel<32, true>), dim3((e->d.G + 31) / 32), dim3(c4net::NTHREADS), 0, st, e->d, nd, values_dev, priors_dev, (int)n_steps);
+        else hipLaunchKernelGGL((c4_selfplay_kernel<16, true>), dim3((e->d.G + 15) / 16), dim3(c4net::NTHREADS), 0, st, e->d, nd, values_dev, priors_dev, (int)n_steps);
     } else if (e->fused_slots == 32)
         hipLaunchKernelGGL(c4_selfplay_kernel<32>, dim3((e->d.G + 31) / 32), dim3(c4net::NTHREADS), 0, st, e->d, nd, values_dev, priors_dev, (int)n_steps);
     else
@@ -3193,6 +3384,145 @@ int c4_match_steps(c4_engine *e, c4_net *net, int32_t net_index, float *values_d
 #undef C4_LAUNCH_MATCH
     HIPCHK(e, hipGetLastError());
     e->launches += n_steps;
+    return C4_OK;
+}
+
+// -- position queue ----------------------------------------------------------------------------
+namespace {
+
+// `boards` (device, [n][2], owned by the caller of this function and handed over on success): validate, install, reset
+int queue_install(c4_engine *e, uint64_t *boards, long long n)
+{
+    const unsigned long long none = (unsigned long long)n;
+    hipError_t r = hipMemcpy(e->queue_scratch, &none, sizeof(none), hipMemcpyHostToDevice);
+    if (r == hipSuccess) r = hipDeviceSynchronize();   // the copy into `boards` may still be in flight on the null stream
+    if (r == hipSuccess) {
+        hipLaunchKernelGGL(k_queue_validate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, (const uint64_t *)boards, n, e->queue_scratch);
+        r = hipGetLastError();
+    }
+    if (r == hipSuccess) r = hipDeviceSynchronize();
+    unsigned long long bad = none;
+    if (r == hipSuccess) r = hipMemcpy(&bad, e->queue_scratch, sizeof(bad), hipMemcpyDeviceToHost);
+    c4_search_result *rows = nullptr;
+    if (r == hipSuccess && bad == none) r = hipMalloc((void **)&rows, sizeof(c4_search_result) * (size_t)n);
+    if (r == hipSuccess && bad == none) r = hipMemset(rows, 0, sizeof(c4_search_result) * (size_t)n);
+    if (r != hipSuccess || bad != none) {
+        (void)hipFree(boards);
+        if (rows) (void)hipFree(rows);
+        if (r != hipSuccess) { set_err(e->err, "c4_queue_positions: %s", hipGetErrorString(r)); return r == hipErrorOutOfMemory ? C4_ENOMEM : C4_EDEVICE; }
+        set_err(e->err, "queued position %llu is decided or inconsistent (search on a finished board is an error in the reference too); nothing was queued", bad);
+        return C4_EINVAL;
+    }
+    if (e->queue_dev) (void)hipFree(e->queue_dev);
+    if (e->results_dev) (void)hipFree(e->results_dev);
+    e->queue_dev = boards;
+    e->results_dev = rows;
+    e->queue_n = n;
+    e->cold.queue = boards;
+    e->cold.results = rows;
+    e->cold.queue_n = n;
+    int rc = sync_cold(e);
+    if (rc) return rc;
+    const int na = (int)std::min<long long>((long long)e->d.G, n);
+    hipLaunchKernelGGL(c4_reset_kernel, dim3((e->d.G + 255) / 256), dim3(256), 0, e->stream, e->d, (const uint64_t *)nullptr, (const uint64_t *)nullptr, na);
+    hipLaunchKernelGGL(k_queue_roots, dim3((e->d.G + 255) / 256), dim3(256), 0, e->stream, e->d, (const uint64_t *)boards, na);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipDeviceSynchronize());
+    e->launches = 0;
+    return C4_OK;
+}
+
+int queue_check(c4_engine *e, const char *what, bool need_queue)
+{
+    if (!e->is_queue) { set_err(e->err, "%s: the engine was not created as a position-queue engine (c4_config.reserved[1] = 1)", what); return C4_ESTATE; }
+    if (need_queue && e->queue_n <= 0) { set_err(e->err, "%s: no positions are queued (c4_queue_positions)", what); return C4_ESTATE; }
+    return C4_OK;
+}
+
+}  // namespace
+
+int c4_queue_positions(c4_engine *e, const uint64_t *color0, const uint64_t *color1, int64_t n)
+{
+    if (!e) return C4_EINVAL;
+    int rc = queue_check(e, "c4_queue_positions", false);
+    if (rc) return rc;
+    if (!color0 || !color1 || n <= 0) { set_err(e->err, "c4_queue_positions: null positions or n = %lld", (long long)n); return C4_EINVAL; }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipDeviceSynchronize());
+    std::vector<uint64_t> packed((size_t)n * 2);
+    for (size_t i = 0; i < (size_t)n; ++i) { packed[2 * i] = color0[i]; packed[2 * i + 1] = color1[i]; }
+    uint64_t *boards = nullptr;
+    HIPCHK(e, hipMalloc((void **)&boards, sizeof(uint64_t) * 2 * (size_t)n));
+    hipError_t r = hipMemcpy(boards, packed.data(), sizeof(uint64_t) * 2 * (size_t)n, hipMemcpyHostToDevice);
+    if (r != hipSuccess) { (void)hipFree(boards); HIPCHK(e, r); }
+    return queue_install(e, boards, (long long)n);
+}
+
+int c4_queue_positions_dev(c4_engine *e, const int64_t *boards_dev, int64_t n)
+{
+    if (!e) return C4_EINVAL;
+    int rc = queue_check(e, "c4_queue_positions_dev", false);
+    if (rc) return rc;
+    if (!boards_dev || n <= 0) { set_err(e->err, "c4_queue_positions_dev: null positions or n = %lld", (long long)n); return C4_EINVAL; }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipDeviceSynchronize());   // whatever stream filled boards_dev has finished
+    uint64_t *boards = nullptr;
+    HIPCHK(e, hipMalloc((void **)&boards, sizeof(uint64_t) * 2 * (size_t)n));
+    hipError_t r = hipMemcpy(boards, boards_dev, sizeof(uint64_t) * 2 * (size_t)n, hipMemcpyDeviceToDevice);
+    if (r != hipSuccess) { (void)hipFree(boards); HIPCHK(e, r); }
+    return queue_install(e, boards, (long long)n);
+}
+
+int c4_queue_progress(c4_engine *e, int64_t *n_done, int64_t *n_total)
+{
+    if (!e) return C4_EINVAL;
+    int rc = queue_check(e, "c4_queue_progress", true);
+    if (rc) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipDeviceSynchronize());
+    unsigned long long done = 0;
+    HIPCHK(e, hipMemcpy(e->queue_scratch, &done, sizeof(done), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_queue_count, dim3((unsigned)((e->queue_n + 255) / 256)), dim3(256), 0, e->stream, (const c4_search_result *)e->results_dev, e->queue_n, e->queue_scratch);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipDeviceSynchronize());
+    HIPCHK(e, hipMemcpy(&done, e->queue_scratch, sizeof(done), hipMemcpyDeviceToHost));
+    if (n_done) *n_done = (int64_t)done;
+    if (n_total) *n_total = (int64_t)e->queue_n;
+    return C4_OK;
+}
+
+int c4_queue_results(c4_engine *e, c4_search_result *out, int64_t first, int64_t n)
+{
+    if (!e) return C4_EINVAL;
+    int rc = queue_check(e, "c4_queue_results", true);
+    if (rc) return rc;
+    if (first < 0 || n < 0 || first > e->queue_n || n > e->queue_n - first || (n > 0 && !out)) { set_err(e->err, "c4_queue_results: rows [%lld,+%lld) are not inside the table of %lld", (long long)first, (long long)n, e->queue_n); return C4_EINVAL; }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipDeviceSynchronize());
+    if (n > 0) HIPCHK(e, hipMemcpy(out, e->results_dev + first, sizeof(c4_search_result) * (size_t)n, hipMemcpyDeviceToHost));
+    return C4_OK;
+}
+
+int c4_queue_results_dev(c4_engine *e, const c4_search_result **rows_dev, int64_t *n)
+{
+    if (!e) return C4_EINVAL;
+    int rc = queue_check(e, "c4_queue_results_dev", true);
+    if (rc) return rc;
+    if (rows_dev) *rows_dev = e->results_dev;
+    if (n) *n = (int64_t)e->queue_n;
+    return C4_OK;
+}
+
+int c4_queue_export_dev(c4_engine *e, void *hip_stream, float *policy_dev, float *visit_policy_dev, float *root_values_dev,
+                        float *move_values_dev, uint8_t *moves_dev)
+{
+    if (!e) return C4_EINVAL;
+    int rc = queue_check(e, "c4_queue_export_dev", true);
+    if (rc) return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    hipLaunchKernelGGL(k_queue_export, dim3((unsigned)((e->queue_n + 255) / 256)), dim3(256), 0, st, (const c4_search_result *)e->results_dev, e->queue_n,
+                       policy_dev, visit_policy_dev, root_values_dev, move_values_dev, moves_dev);
+    HIPCHK(e, hipGetLastError());
     return C4_OK;
 }
 

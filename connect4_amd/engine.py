@@ -18,6 +18,16 @@ def _ptr(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
 
 
+def check_packed_boards(boards):
+    """ValueError unless `boards` is a non-empty torch int64 [n, 2] tensor of packed boards {color0, color1}."""
+    import torch
+    if not isinstance(boards, torch.Tensor) or boards.dtype != torch.int64 or boards.dim() != 2 or boards.shape[1] != 2:
+        raise ValueError("packed boards are a torch int64 tensor [n, 2] = {color0, color1} per row; got %s %s" % (
+            getattr(boards, "dtype", type(boards).__name__), tuple(getattr(boards, "shape", ()))))
+    if boards.shape[0] == 0:
+        raise ValueError("no positions to search: the tensor is empty")
+
+
 class Engine:
     """One engine per GPU per process; not thread safe (one host thread drives it)."""
 
@@ -26,7 +36,7 @@ class Engine:
                  eval_mode=L.EVAL_EXTERNAL_F32, rng_mode=L.RNG_PHILOX, seed=0, stop_after_move=False,
                  games_target=-1, record_capacity_games=0, max_inner_iters=0,
                  planes_dtype=L.PLANES_F32, eval_cache_log2_entries=0, level_budget=0, time_budget_cycles=0, device=0,
-                 n_match_nets=0):
+                 n_match_nets=0, position_queue=False):
         self._lib = L.load()
         self.cfg = L.Config()
         self.cfg.abi_version = L.ABI_VERSION
@@ -50,6 +60,8 @@ class Engine:
         self.cfg.time_budget_cycles = int(time_budget_cycles)
         self.cfg.reserved[0] = int(n_match_nets)     # > 0: a match engine, one evaluation cache per net (match_steps)
         self.n_match_nets = int(n_match_nets)
+        self.cfg.reserved[1] = 1 if position_queue else 0   # a position-queue engine (queue_positions); stop_after_move
+        self.position_queue = bool(position_queue)
         self.n_slots = int(n_slots)
         self.device = int(device)
         self._h = C.c_void_p()
@@ -130,6 +142,59 @@ class Engine:
         choose and make their move; all others pass through (c4_match_steps).  Asynchronous on `stream`."""
         self._check(self._lib.c4_match_steps(self._h, net._h, int(net_index), C.c_void_p(values.data_ptr()),
                                              C.c_void_p(priors.data_ptr()), int(n_steps), C.c_void_p(stream or 0)))
+
+    # -- position queue (c4_queue_positions ...; Engine(..., stop_after_move=True, position_queue=True)) ------
+    def queue_positions(self, color0, color1):
+        """Queue len(color0) positions of any number for the engine's slots: slot i starts on position i, and a slot
+        that finishes one takes the next inside the kernel.  Resets counters and the result table like reset()."""
+        c0, c1 = _u64(color0), _u64(color1)
+        if c0.ndim != 1 or c0.shape != c1.shape or len(c0) == 0:
+            raise ValueError("queue_positions takes two equally long, non-empty lists of bitboards")
+        self._check(self._lib.c4_queue_positions(self._h, _ptr(c0, C.c_uint64), _ptr(c1, C.c_uint64), len(c0)))
+
+    def queue_positions_dev(self, boards):
+        """The same from a torch int64 [n, 2] device tensor of packed boards (PackedGames.boards, LabelledSet.boards):
+        no host copy; the engine keeps a copy of its own."""
+        check_packed_boards(boards)
+        if boards.device.type != "cuda" or (boards.device.index or 0) != self.device:
+            raise ValueError("queue_positions_dev takes a tensor on cuda:%d, got %s" % (self.device, boards.device))
+        boards = boards.contiguous()
+        self._check(self._lib.c4_queue_positions_dev(self._h, C.c_void_p(boards.data_ptr()), int(boards.shape[0])))
+
+    def queue_progress(self):
+        """(rows finished, rows in all); waits for the device."""
+        done, total = C.c_int64(), C.c_int64()
+        self._check(self._lib.c4_queue_progress(self._h, C.byref(done), C.byref(total)))
+        return done.value, total.value
+
+    def queue_results(self, first=0, n=None):
+        """Rows [first, first + n) of the result table (default: all) as a NumPy record array of c4_search_result:
+        rows[i].child_visits, rows.move, ...; a row reads like the RootResult of read_roots().  state 0: not searched yet."""
+        if n is None:
+            n = self.queue_progress()[1] - int(first)
+        out = np.zeros(max(int(n), 0), dtype=L.search_result_dtype())
+        self._check(self._lib.c4_queue_results(self._h, C.c_void_p(out.ctypes.data), int(first), int(n)))
+        return out.view(np.recarray)
+
+    def queue_export(self, fields=("policy", "visit_policy", "root_values", "move_values", "moves"), stream=0):
+        """The rows as packed device tensors in the replay window's layout (c4_queue_export_dev): a dict with the asked
+        ones of policy F32[n,7] (values policy), visit_policy F32[n,7], root_values F32[n] (root value sum / visits),
+        move_values F32[n] (NaN for None) and moves U8[n].  One launch on `stream` (default: torch's current stream),
+        no host synchronisation beyond the row count."""
+        import torch
+        n = self.queue_progress()[1]
+        dev = torch.device("cuda", self.device)
+        shapes = dict(policy=((n, 7), torch.float32), visit_policy=((n, 7), torch.float32), root_values=((n,), torch.float32),
+                      move_values=((n,), torch.float32), moves=((n,), torch.uint8))
+        for f in fields:
+            if f not in shapes:
+                raise ValueError("queue_export fields are %s" % ", ".join(shapes))
+        t = {f: torch.empty(shapes[f][0], dtype=shapes[f][1], device=dev) for f in fields}
+        if not stream:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._lib.c4_queue_export_dev(self._h, C.c_void_p(stream), *[
+            C.c_void_p(t[f].data_ptr()) if f in t else None for f in ("policy", "visit_policy", "root_values", "move_values", "moves")]))
+        return t
 
     def run_centre(self, max_launches=64):
         self._check(self._lib.c4_run_centre(self._h, int(max_launches)))

@@ -7,7 +7,7 @@ tests/test_stats_host.py.  Each also builds itself from a read-back device accum
 ``DeviceStats`` owns such an accumulator (c4_score_acc, include/c4_engine.h) and feeds it with c4_score_update_dev: two
 launches per batch on the caller's stream, capturable in the train step's HIP graph, nothing read back until ``read()``.
 ``LabelledSet`` is a labelled test set on the device as packed boards; ``score(net, labelled_set)`` gives any self-play
-evaluator's statistics on one.  What the device reports differs from ``update`` fed batch by batch in one documented way:
+evaluator's statistics on one, ``score_search(config, net, labelled_set)`` those of the net with a search on top.  What the device reports differs from ``update`` fed batch by batch in one documented way:
 the losses are sums of float64 row losses instead of float32 batch means times the batch length (include/c4_engine.h).
 """
 import ctypes as C
@@ -348,3 +348,32 @@ def score(net, labelled_set, batch_size=32768):
             else:
                 ds.update(xv, ls.values[a:b])
         return ds.read()
+
+
+def score_search(config, net, labelled_set, n_slots=None, eval_cache_log2_entries=0, steps_per_launch=64):
+    """score() for net + search: every position of the LabelledSet is searched with `config` (the position queue of
+    connect4_amd.analysis: packed boards queued straight from the device, n_slots engine slots, default min(n, 4096)), and
+    what the search says -- the root's mean value (root value sum / root visits) as the value output, the values policy
+    (tree.get_values_policy()) as the policy output -- goes through the accumulator score() uses, against the same labels.
+    The difference to score(net, labelled_set) is what the simulations add to the checkpoint.  net: what make_selfplay_net
+    returns (or a DeviceNetEvaluator); CombinedStats, or ValueStats for a set without priors."""
+    import torch
+    from .analysis import run_queue
+    from .evaluators import DeviceNetEvaluator
+    ls = labelled_set
+    if ls.device.type != "cuda":
+        raise RuntimeError("score_search() runs on the GPU: the labelled set must live on a cuda device")
+    dev_index = ls.device.index if ls.device.index is not None else torch.cuda.current_device()
+    evaluator = net if isinstance(net, DeviceNetEvaluator) else DeviceNetEvaluator(net, dev_index)
+    with torch.cuda.device(ls.device), torch.no_grad():
+        eng = run_queue(config, ls.boards, evaluator, n_slots, dev_index, eval_cache_log2_entries, steps_per_launch)
+        try:
+            out = eng.queue_export(("policy", "root_values"))
+            ds = DeviceStats(ls.device, with_priors=ls.priors is not None)
+            if ls.priors is not None:
+                ds.update(out["root_values"], ls.values, out["policy"], ls.priors)
+            else:
+                ds.update(out["root_values"], ls.values)
+            return ds.read()
+        finally:
+            eng.close()

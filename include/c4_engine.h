@@ -103,7 +103,10 @@ typedef struct {
                                           a simulation never changes results.  0 = off / 80,000 */
     int32_t reserved[4];               /* must be 0; reserved[0] = n_match_nets: > 0 creates a match engine (c4_match_steps) with that
                                           many evaluation caches, one per net (at most C4_MATCH_MAX_NETS); the auto size is
-                                          divided among them.  Needs C4_EVAL_EXTERNAL_F32 and stop_after_move = 0 */
+                                          divided among them.  Needs C4_EVAL_EXTERNAL_F32 and stop_after_move = 0;
+                                          reserved[1] = 1 creates a position-queue engine (c4_queue_positions): needs stop_after_move = 1,
+                                          any eval_mode; with C4_EVAL_EXTERNAL_F32 the auto size of the evaluation cache applies.
+                                          reserved[0] > 0 together with reserved[1] is C4_EINVAL */
 } c4_config;
 
 typedef struct c4_engine c4_engine;
@@ -478,6 +481,64 @@ int c4_selfplay_steps(c4_engine *e, c4_net *net, float *values_dev, float *prior
 int c4_match_assign(c4_engine *e, const int32_t *net_o, const int32_t *net_x, int32_t n);
 int c4_match_steps(c4_engine *e, c4_net *net, int32_t net_index, float *values_dev, float *priors_dev, int32_t n_steps,
                    void *hip_stream);
+/* -- position queue: search a list of positions of any length on the engine's slots -------------------------------
+ * (stands in for a loop of mcts.search(config, board, evaluator), mcts.py:94-121, over a test set or a generation's
+ * positions.)  An engine created with c4_config.reserved[1] = 1 (and stop_after_move = 1; any eval_mode) searches N
+ * queued positions with its G slots, N of any size: a slot that has chosen its move writes its root read-out into row
+ * `index` of a device result table, takes the next index with one atomic add and starts on that position -- inside the
+ * kernel, in whichever stepping call is running: c4_step / c4_step_range with any evaluator, c4_run_centre, and
+ * c4_selfplay_steps (all three kernels, the 64-filter C4_NET_F32X3_WIDE net in the split kernel included).  The
+ * evaluation cache is shared by all positions.  A slot that finds the queue empty parks; the queue is done when
+ * c4_stats.active_slots == 0.  Which slot searches a position, and in which launch, never changes its row: the rows are
+ * those of one c4_reset / c4_read_roots search per position.  Without a queue the engine is a plain stop-after-move
+ * engine.  c4_match_steps has no match to play on it (C4_ESTATE).
+ * A row has the fields of c4_root_result, so whatever reads one reads the other; `state` is 0 until the row's search
+ * is finished and 2 from then on, and is written after every other field: a row read between launches is either
+ * untouched or whole.  `expansions` counts the expand_node calls of this search (the evaluated nodes that were visited
+ * again), `simulations` its simulations. */
+typedef struct {
+    int32_t  state;             /* 0 not searched yet, 2 done */
+    int32_t  move;              /* chosen column */
+    double   value;             /* child.data.absolute_value of the chosen child (NaN if None) */
+    uint32_t root_visits;
+    double   root_value_sum;
+    uint32_t child_visits[7];
+    double   child_value_sum[7];
+    int32_t  child_status[7];   /* -2 absent, -1 non-terminal, else C4_RESULT_* */
+    double   root_prior[7];     /* normalised (+ noise) prior used at the root */
+    double   values_policy[7];  /* tree.py:104-109 */
+    uint64_t color0, color1;    /* the position searched */
+    int64_t  expansions;
+    int64_t  simulations;
+} c4_search_result;
+/* c4_queue_positions: n >= 1 host positions; c4_queue_positions_dev: the same from DEVICE memory, boards_dev int64
+ * [n][2] = {color0, color1} per row (the layout of c4_export_buffers.boards_dev; the engine keeps a copy of its own).
+ * Both behave as c4_reset does: counters, game ids and the result table are cleared, slots 0 .. min(G, n) - 1 start on
+ * positions 0 .. with game_id = index, the other slots park, the next index handed out is min(G, n); the evaluation
+ * cache is kept.  The game id of a search is its index: c4_set_tapes rows are indexed by position and row [i][0] is
+ * used (ply 0); the C4_RNG_PHILOX streams are those of (seed, index, 0).  The positions are checked on the device by
+ * the rule of c4_reset: a decided or inconsistent one gives C4_EINVAL with the index of the first in the message,
+ * nothing is queued and the engine stays as it was.  On an engine without reserved[1]: C4_ESTATE.  Synchronous.
+ * c4_reset on a queue engine drops the queue (and its result table). */
+int c4_queue_positions(c4_engine *e, const uint64_t *color0, const uint64_t *color1, int64_t n);
+int c4_queue_positions_dev(c4_engine *e, const int64_t *boards_dev, int64_t n);
+/* rows finished / rows in all.  Synchronous.  No queue: C4_ESTATE (as the three calls below). */
+int c4_queue_progress(c4_engine *e, int64_t *n_done, int64_t *n_total);
+/* rows [first, first + n) into host memory; a range outside the table: C4_EINVAL.  Synchronous. */
+int c4_queue_results(c4_engine *e, c4_search_result *out, int64_t first, int64_t n);
+/* the table itself: engine-owned device memory, valid until the next c4_queue_positions* / c4_reset / destroy */
+int c4_queue_results_dev(c4_engine *e, const c4_search_result **rows_dev, int64_t *n);
+/* The rows as packed float32 device tensors in the layout of the replay window (c4_export_games_dev), one launch on
+ * hip_stream (NULL = the engine's), no host synchronisation; any pointer may be NULL:
+ *   policy_dev [n][7]        values_policy rounded to float32 (tree.get_values_policy(), training_game.py:14)
+ *   visit_policy_dev [n][7]  the children's visit counts over their sum in float64, rounded (tree.py:111-117)
+ *   root_values_dev [n]      root_value_sum / root_visits in float64, rounded
+ *   move_values_dev [n]      value (NaN for None)
+ *   moves_dev uint8 [n]      move
+ * A row that is not finished gives zeros, NaN, NaN and 255. */
+int c4_queue_export_dev(c4_engine *e, void *hip_stream, float *policy_dev, float *visit_policy_dev, float *root_values_dev,
+                        float *move_values_dev, uint8_t *moves_dev);
+
 /* diagnostic build aid: per-phase s_memtime stamps of workgroup 0, [8 waves][16]; needs the
  * environment variable C4_NET_STAMPS=1 when the net is created, else C4_ESTATE. */
 int c4_net_debug_stamps(c4_net *net, unsigned long long *out);
