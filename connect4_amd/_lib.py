@@ -23,6 +23,8 @@ PRIOR_NONE, PRIOR_F32, PRIOR_F64 = 0, 1, 2
 PV_VALUE, PV_VISITS = 0, 1
 NET_F16, NET_F32X3, NET_F32X3_WIDE = 0, 1, 2   # c4_net_desc.precision
 MATCH_MAX_NETS = 16
+SOLVE_MAX_EMPTIES = 24
+SOLVE_SOLVED, SOLVE_TERMINAL, SOLVE_UNKNOWN, SOLVE_TOO_DEEP, SOLVE_INVALID = 0, 1, 2, 3, 4
 
 
 class EngineError(RuntimeError):
@@ -202,6 +204,10 @@ SIGNATURES = {
     "c4_score_reset_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
     "c4_score_update_dev": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_longlong] * 2 + [C.c_void_p] * 2),
     "c4_score_last_error": (C.c_char_p, []),
+    "c4_solve_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 4),
+    "c4_solve": (C.c_int, [C.c_int, _u64p, _u64p, C.c_int64, C.c_int64, C.c_int64, _P(C.c_int8), _P(C.c_int8), _P(C.c_int8), _i64p]),
+    "c4_solve_children_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "c4_solve_last_error": (C.c_char_p, []),
 }
 
 _lib = None

@@ -1,0 +1,575 @@
+// c4_solve.hip -- exact values of late-game positions (at most C4_SOLVE_MAX_EMPTIES empty squares) by
+// alpha-beta on gfx950, behind c4_solve / c4_solve_dev / c4_solve_children_dev of include/c4_engine.h.
+//
+// The answer is the one the reference's GridSearch(plies >= empty squares) computes exhaustively
+// (oinkoink/grid_search.py:38-71: no evaluator is reached, the terminal scoring prefers faster wins and
+// slower losses): the game-theoretic outcome and the age (stone count) at which best play ends the game.
+//
+// Score.  A game that o wins at age a scores 43 - a, one that x wins at age a scores a - 43, a draw 0 --
+// an integer that is strictly monotone in the reference's float64 (1 - a/10000, a/10000, 0.5 + 42/10000).
+// The search keeps it from the side to move (negamax); outcome and final age leave the kernel, the float64
+// is formed from them by the caller as the reference writes it.
+//
+// Search.  One position per lane, iterative depth-first alpha-beta without a transposition table:
+//   * a node is entered only when its mover cannot win at once (the root is checked, below the root the
+//     move list guarantees it), so an immediate win never costs a node;
+//   * the move list holds the non-losing moves only: a forced block if the opponent threatens, no move
+//     under a square the opponent wins on; an empty list is a loss two plies on;
+//   * the window is clipped to what is still possible (no win before age + 3, no loss before age + 4);
+//   * moves are ordered by the number of winning squares they create, ties centre first.
+// Pruning and ordering change the node count, never the value: the root's window is the whole range.
+//
+// Stack.  A frame is two 32-bit words (the ordered rest of the move list with the move played; alpha and
+// beta).  The top frame lives in registers, the frames below in LDS laid out [ply][lane] -- a lane's
+// column, so no lane reads another's and there is no barrier.  Boards are not stacked: the move played
+// is undone on the way back.
+//
+// Termination.  Every loop is bounded: a launch gives each lane a quota of nodes; a lane that has used
+// it stores its registers and frames to global memory and stops.  The host relaunches the unfinished
+// positions, compacted into a dense index list, until all are done or a position's total has reached
+// its budget (status UNKNOWN).  No lane waits for another lane, wave or workgroup; no atomics.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../include/c4_engine.h"
+#include "c4_board.h"
+
+using namespace c4;
+
+namespace {
+
+constexpr int MAX_EMPTIES = C4_SOLVE_MAX_EMPTIES;
+constexpr int MAX_PLY = MAX_EMPTIES;            // frames of one lane (a node with one empty square is a leaf)
+constexpr int BLOCK = 64;                       // one wave per workgroup: 2 x 24 x 64 x 4 B = 12 KiB of LDS
+constexpr uint64_t BOARD = BOTTOM * COLMASK;    // the 42 cells
+constexpr int SCORE_MAX = 42;                   // beyond every score (the fastest win, at age 7, scores 36)
+constexpr int64_t DEFAULT_BUDGET = (int64_t)1 << 26;
+constexpr int64_t DEFAULT_PER_LAUNCH = (int64_t)1 << 14;
+constexpr int64_t CHUNK_ROWS = (int64_t)1 << 20;   // rows searched per pass: bounds the work memory (224 B a row)
+
+// the empty squares on which `p` completes four in a row, given the occupied squares `occ`
+C4_HD uint64_t winning_squares(uint64_t p, uint64_t occ)
+{
+    uint64_t r = (p << 1) & (p << 2) & (p << 3);    // vertical
+    uint64_t q = (p << 7) & (p << 14);              // horizontal
+    r |= q & (p << 21);
+    r |= q & (p >> 7);
+    q = (p >> 7) & (p >> 14);
+    r |= q & (p << 7);
+    r |= q & (p >> 21);
+    q = (p << 6) & (p << 12);                       // diagonal '\'
+    r |= q & (p << 18);
+    r |= q & (p >> 6);
+    q = (p >> 6) & (p >> 12);
+    r |= q & (p << 6);
+    r |= q & (p >> 18);
+    q = (p << 8) & (p << 16);                       // diagonal '/'
+    r |= q & (p << 24);
+    r |= q & (p >> 8);
+    q = (p >> 8) & (p >> 16);
+    r |= q & (p << 8);
+    r |= q & (p >> 24);
+    return r & (BOARD ^ occ);
+}
+
+// Move list: up to 7 columns of 3 bits each, next move lowest; the number left at bits 24..26; the move
+// played from this node (to undo on the way back) at bits 27..29.
+C4_HD int moves_left(uint32_t m) { return (int)((m >> 24) & 7); }
+
+// `cand` has at most one square per column.  More winning squares first, ties centre first (3,2,4,1,5,0,6).
+C4_HD uint32_t order_moves(uint64_t mine, uint64_t occ, uint64_t cand)
+{
+    int key[WIDTH];
+#pragma unroll
+    for (int c = 0; c < WIDTH; ++c) {
+        const uint64_t bit = cand & (COLMASK << (H1 * c));
+        const int prio = c == 3 ? 6 : c == 2 ? 5 : c == 4 ? 4 : c == 1 ? 3 : c == 5 ? 2 : c == 0 ? 1 : 0;
+        key[c] = bit ? popc64(winning_squares(mine | bit, occ | bit)) * 8 + prio + 1 : 0;
+    }
+    uint32_t list = 0;
+    int n = 0;
+#pragma unroll
+    for (int c = 0; c < WIDTH; ++c) {
+        int rank = 0;                  // keys of candidates are distinct: ranks 0..n-1
+#pragma unroll
+        for (int j = 0; j < WIDTH; ++j) rank += (j != c && key[j] > key[c]) ? 1 : 0;
+        if (key[c]) {
+            list |= (uint32_t)c << (3 * rank);
+            ++n;
+        }
+    }
+    return list | ((uint32_t)n << 24);
+}
+
+// A node whose mover (`mine`, `age` stones on the board) cannot win at once.  Returns true for a leaf
+// (`value` is its score for the mover), false for an interior node: alpha and beta are clipped to the
+// scores still possible and `moves` is its ordered move list.
+C4_HD bool enter_node(uint64_t mine, uint64_t theirs, int age, int &alpha, int &beta, uint32_t &moves, int &value)
+{
+    if (age == CELLS - 1) { value = 0; return true; }       // the last square, and it does not win
+    const uint64_t occ = mine | theirs;
+    uint64_t possible = (occ + BOTTOM) & BOARD;
+    const uint64_t opp_win = winning_squares(theirs, occ);
+    const uint64_t forced = possible & opp_win;
+    if (forced) {
+        if (forced & (forced - 1)) { value = age - 41; return true; }   // two threats: lost at age + 2
+        possible = forced;
+    }
+    possible &= ~(opp_win >> 1);
+    if (!possible) { value = age - 41; return true; }
+    const int lo = age + 4 <= CELLS ? age - 39 : 0;     // no loss before age + 4
+    const int hi = age + 3 <= CELLS ? 40 - age : 0;     // no win before age + 3
+    if (beta > hi) {
+        beta = hi;
+        if (alpha >= beta) { value = beta; return true; }
+    }
+    if (alpha < lo) {
+        alpha = lo;
+        if (alpha >= beta) { value = alpha; return true; }
+    }
+    if ((possible & (possible - 1)) == 0)       // one move (a forced block, mostly): nothing to order
+        moves = (uint32_t)(__builtin_ctzll(possible) / H1) | (1u << 24);
+    else
+        moves = order_moves(mine, occ, possible);
+    return false;
+}
+
+struct Lane {
+    uint64_t c0, c1;
+    uint32_t moves;
+    int d, alpha, beta, ret;
+    bool pending;       // the node at depth d has returned `ret`
+    bool done;          // the root has returned
+};
+
+C4_HD uint32_t pack_ab(int alpha, int beta) { return (uint32_t)(alpha + 64) | ((uint32_t)(beta + 64) << 8); }
+
+// The status of a row before any search (c4_engine.h C4_SOLVE_*; SOLVED here means: to be searched).  A
+// finished position carries its own outcome and age.
+C4_HD int classify(uint64_t c0, uint64_t c1, int &outcome, int &final_age)
+{
+    const uint64_t occ = c0 | c1;
+    const int n0 = popc64(c0), n1 = popc64(c1);
+    outcome = -1;
+    final_age = -1;
+    if ((c0 & c1) || (occ & ~BOARD) || (occ & (occ + BOTTOM)) || n0 - n1 < 0 || n0 - n1 > 1 || (wins(c0) && wins(c1)))
+        return C4_SOLVE_INVALID;
+    const uint32_t st = position_status(c0, c1);
+    if (st != ST_FRESH) {
+        outcome = (int)st - (int)ST_XWIN;
+        final_age = n0 + n1;
+        return C4_SOLVE_TERMINAL;
+    }
+    if (CELLS - (n0 + n1) > MAX_EMPTIES) return C4_SOLVE_TOO_DEEP;
+    return C4_SOLVE_SOLVED;
+}
+
+C4_HD void root_answer(int age, int score, int &outcome, int &final_age)
+{
+    const int abs_score = (age & 1) ? -score : score;       // o moves at even ages
+    outcome = abs_score > 0 ? C4_RESULT_OWIN : abs_score < 0 ? C4_RESULT_XWIN : C4_RESULT_DRAW;
+    final_age = abs_score > 0 ? 43 - abs_score : abs_score < 0 ? 43 + abs_score : CELLS;
+}
+
+C4_HD void enter_root(uint64_t c0, uint64_t c1, Lane &L)
+{
+    const uint64_t occ = c0 | c1;
+    const int age = popc64(occ);
+    const uint64_t mine = (age & 1) ? c1 : c0, theirs = (age & 1) ? c0 : c1;
+    L.c0 = c0;
+    L.c1 = c1;
+    L.d = 0;
+    L.moves = 0;
+    L.alpha = -SCORE_MAX;
+    L.beta = SCORE_MAX;
+    L.ret = 0;
+    L.pending = false;
+    L.done = false;
+    if (winning_squares(mine, occ) & (occ + BOTTOM)) {       // the mover wins at once
+        L.ret = 42 - age;
+        L.done = true;
+        return;
+    }
+    int value = 0;
+    if (enter_node(mine, theirs, age, L.alpha, L.beta, L.moves, value)) {
+        L.ret = value;
+        L.done = true;
+    }
+}
+
+// Run lane L for at most `quota` more nodes.  S: the frames below the top one, S.moves(p) / S.ab(p) for ply p.
+// Returns the nodes entered.  Every iteration pops a frame, closes a node or enters one, so 3 * quota + 64
+// iterations cover the quota and the unwinding of a full stack.
+template <class S>
+C4_HD int64_t run_lane(Lane &L, S &stk, int64_t quota)
+{
+    int64_t used = 0;
+    const int64_t max_iter = 3 * quota + 64;
+    for (int64_t it = 0; it < max_iter && !L.done && (L.pending || used < quota); ++it) {
+        if (L.pending) {
+            if (L.d == 0) { L.done = true; break; }
+            --L.d;
+            const uint32_t m = stk.moves(L.d), ab = stk.ab(L.d);
+            const int col = (int)((m >> 27) & 7);
+            // undo: the top stone of `col` belongs to the mover of the node returned to
+            const uint64_t occ = L.c0 | L.c1;
+            const uint64_t bit = 1ULL << (H1 * col + col_count(occ, col) - 1);
+            if ((popc64(occ) - 1) & 1) L.c1 ^= bit; else L.c0 ^= bit;
+            L.moves = m;
+            L.alpha = (int)(ab & 0xff) - 64;
+            L.beta = (int)((ab >> 8) & 0xff) - 64;
+            const int v = -L.ret;
+            if (v >= L.beta) L.ret = v;             // cut-off: this node returns as well
+            else {
+                if (v > L.alpha) L.alpha = v;
+                L.pending = false;
+            }
+        }
+        if (!L.pending && used < quota) {
+            if (moves_left(L.moves) == 0) {
+                L.ret = L.alpha;
+                L.pending = true;
+            } else if (L.d < MAX_PLY) {
+                const int col = (int)(L.moves & 7);
+                const uint32_t rest = ((L.moves & 0xffffffu) >> 3) | ((uint32_t)(moves_left(L.moves) - 1) << 24);
+                stk.moves(L.d) = rest | ((uint32_t)col << 27);
+                stk.ab(L.d) = pack_ab(L.alpha, L.beta);
+                ++L.d;
+                (void)make_move(L.c0, L.c1, col);
+                ++used;
+                const uint64_t occ = L.c0 | L.c1;
+                const int age = popc64(occ);
+                const uint64_t mine = (age & 1) ? L.c1 : L.c0, theirs = (age & 1) ? L.c0 : L.c1;
+                int a = -L.beta, b = -L.alpha, value = 0;
+                uint32_t moves = 0;
+                if (enter_node(mine, theirs, age, a, b, moves, value)) {
+                    L.ret = value;
+                    L.pending = true;
+                } else {
+                    L.alpha = a;
+                    L.beta = b;
+                    L.moves = moves;
+                }
+            } else {
+                L.ret = L.alpha;        // not reachable: a node MAX_PLY deep has no empty square
+                L.pending = true;
+            }
+        }
+    }
+    return used;
+}
+
+thread_local char solve_err[512] = "";
+
+void set_solve_err(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(solve_err, sizeof(solve_err), fmt, ap);
+    va_end(ap);
+}
+
+// work memory of one pass over `n` rows (row-indexed; frames [ply][row])
+struct Work {
+    uint64_t *c0, *c1;          // the position a stopped lane stands at
+    uint32_t *moves, *misc;     // its top frame: move list; alpha | beta << 8 | ret << 16 | d << 24 | pending << 30
+    uint32_t *stk_moves, *stk_ab;
+    int64_t n;
+};
+
+struct LdsStack {
+    uint32_t (*m)[BLOCK];
+    uint32_t (*a)[BLOCK];
+    int lane;
+    __device__ __forceinline__ uint32_t &moves(int p) { return m[p][lane]; }
+    __device__ __forceinline__ uint32_t &ab(int p) { return a[p][lane]; }
+};
+
+__device__ __forceinline__ void store_answer(const int64_t *boards, int64_t row, const Lane &L, int8_t *outcome, int8_t *final_age)
+{
+    const int age = popc64((uint64_t)boards[2 * row] | (uint64_t)boards[2 * row + 1]);
+    int o, fa;
+    root_answer(age, L.ret, o, fa);
+    outcome[row] = (int8_t)o;
+    final_age[row] = (int8_t)fa;
+}
+
+// one lane per row: status, the answers that need no search, the root of the others; unfinished[row] = 1
+// for a row that k_solve_run has to continue
+__global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict__ boards, int64_t n, int64_t node_budget, Work w,
+                                                      int8_t *__restrict__ status, int8_t *__restrict__ outcome,
+                                                      int8_t *__restrict__ final_age, int64_t *__restrict__ nodes,
+                                                      uint8_t *__restrict__ unfinished)
+{
+    const int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (row >= n) return;
+    const uint64_t c0 = (uint64_t)boards[2 * row], c1 = (uint64_t)boards[2 * row + 1];
+    int o, fa;
+    int st = classify(c0, c1, o, fa);
+    int64_t nd = 0;
+    uint8_t more = 0;
+    if (st == C4_SOLVE_SOLVED) {
+        Lane L;
+        enter_root(c0, c1, L);
+        nd = 1;
+        if (L.done) root_answer(popc64(c0 | c1), L.ret, o, fa);
+        else if (nd >= node_budget) st = C4_SOLVE_UNKNOWN;
+        else {
+            more = 1;
+            w.c0[row] = L.c0;
+            w.c1[row] = L.c1;
+            w.moves[row] = L.moves;
+            w.misc[row] = pack_ab(L.alpha, L.beta) | ((uint32_t)(L.ret + 64) << 16);
+        }
+    }
+    status[row] = (int8_t)st;
+    outcome[row] = (int8_t)o;
+    final_age[row] = (int8_t)fa;
+    nodes[row] = nd;
+    unfinished[row] = more;
+}
+
+// one lane per unfinished row, through the dense list `active`: load, search up to the quota, store
+__global__ void __launch_bounds__(BLOCK) k_solve_run(const int64_t *__restrict__ boards, const int32_t *__restrict__ active, int32_t m,
+                                                     int64_t node_budget, int64_t nodes_per_launch, Work w,
+                                                     int8_t *__restrict__ status, int8_t *__restrict__ outcome,
+                                                     int8_t *__restrict__ final_age, int64_t *__restrict__ nodes,
+                                                     uint8_t *__restrict__ unfinished)
+{
+    __shared__ uint32_t s_moves[MAX_PLY][BLOCK];
+    __shared__ uint32_t s_ab[MAX_PLY][BLOCK];
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= m) return;
+    const int64_t row = active[i];
+    if (row < 0 || row >= w.n) return;
+    LdsStack stk{s_moves, s_ab, (int)threadIdx.x};
+    Lane L;
+    L.c0 = w.c0[row];
+    L.c1 = w.c1[row];
+    L.moves = w.moves[row];
+    const uint32_t misc = w.misc[row];
+    L.alpha = (int)(misc & 0xff) - 64;
+    L.beta = (int)((misc >> 8) & 0xff) - 64;
+    L.ret = (int)((misc >> 16) & 0xff) - 64;
+    L.d = (int)((misc >> 24) & 0x3f);
+    L.pending = ((misc >> 30) & 1) != 0;
+    L.done = false;
+    if (L.d > MAX_PLY) L.d = MAX_PLY;
+    for (int p = 0; p < MAX_PLY; ++p) {
+        if (p < L.d) {
+            s_moves[p][threadIdx.x] = w.stk_moves[(int64_t)p * w.n + row];
+            s_ab[p][threadIdx.x] = w.stk_ab[(int64_t)p * w.n + row];
+        }
+    }
+    const int64_t total = nodes[row];
+    const int64_t left = node_budget - total;
+    const int64_t quota = left < nodes_per_launch ? left : nodes_per_launch;
+    const int64_t used = run_lane(L, stk, quota);
+    nodes[row] = total + used;
+    if (L.done) {
+        store_answer(boards, row, L, outcome, final_age);
+        unfinished[i] = 0;
+        return;
+    }
+    if (total + used >= node_budget) {      // it would take a node beyond the budget to go on
+        status[row] = C4_SOLVE_UNKNOWN;
+        unfinished[i] = 0;
+        return;
+    }
+    unfinished[i] = 1;
+    w.c0[row] = L.c0;
+    w.c1[row] = L.c1;
+    w.moves[row] = L.moves;
+    w.misc[row] = pack_ab(L.alpha, L.beta) | ((uint32_t)(L.ret + 64) << 16) | ((uint32_t)L.d << 24) | ((uint32_t)(L.pending ? 1 : 0) << 30);
+    for (int p = 0; p < MAX_PLY; ++p) {
+        if (p < L.d) {
+            w.stk_moves[(int64_t)p * w.n + row] = s_moves[p][threadIdx.x];
+            w.stk_ab[(int64_t)p * w.n + row] = s_ab[p][threadIdx.x];
+        }
+    }
+}
+
+// the children of every row in column order: children[row][col] = the position after `col`, legal[row][col] = 1;
+// an illegal column, or any column of a row that is not a searchable or too deep position: zeros
+__global__ void __launch_bounds__(256) k_solve_children(const int64_t *__restrict__ boards, int64_t n, int64_t *__restrict__ children,
+                                                        int8_t *__restrict__ legal)
+{
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n) return;
+    const uint64_t c0 = (uint64_t)boards[2 * row], c1 = (uint64_t)boards[2 * row + 1];
+    int o, fa;
+    const int st = classify(c0, c1, o, fa);
+    const bool open = st == C4_SOLVE_SOLVED || st == C4_SOLVE_TOO_DEEP;
+    const int mask = open ? legal_mask(c0 | c1) : 0;
+#pragma unroll
+    for (int c = 0; c < WIDTH; ++c) {
+        uint64_t n0 = 0, n1 = 0;
+        const bool ok = ((mask >> c) & 1) != 0;
+        if (ok) {
+            n0 = c0;
+            n1 = c1;
+            (void)make_move(n0, n1, c);
+        }
+        children[(row * WIDTH + c) * 2] = (int64_t)n0;
+        children[(row * WIDTH + c) * 2 + 1] = (int64_t)n1;
+        legal[row * WIDTH + c] = ok ? 1 : 0;
+    }
+}
+
+#define SOLVE_CHECK(expr)                                                                  \
+    do {                                                                                   \
+        hipError_t _r = (expr);                                                            \
+        if (_r != hipSuccess) {                                                            \
+            set_solve_err("%s failed: %s", #expr, hipGetErrorString(_r));                  \
+            return C4_EDEVICE;                                                             \
+        }                                                                                  \
+    } while (0)
+
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t get(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+    template <typename T> T *as() { return (T *)p; }
+};
+
+int pick_device(int device)
+{
+    int count = 0;
+    hipError_t r = hipGetDeviceCount(&count);
+    if (r != hipSuccess || count <= 0) { set_solve_err("no HIP device available: there is no CPU fallback"); return C4_EDEVICE; }
+    if (device < 0 || device >= count) { set_solve_err("device %d out of range (have %d)", device, count); return C4_EDEVICE; }
+    SOLVE_CHECK(hipSetDevice(device));
+    return C4_OK;
+}
+
+// one pass: rows [0, n) of `boards`, n <= CHUNK_ROWS
+int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t node_budget, int64_t per_launch, int8_t *status,
+                int8_t *outcome, int8_t *final_age, int64_t *nodes)
+{
+    DevBuf mem, flags, act;
+    const size_t words = (size_t)n * (4 + 2 + 2 * MAX_PLY);      // 32-bit words a row
+    SOLVE_CHECK(mem.get(words * 4));
+    SOLVE_CHECK(flags.get((size_t)n));
+    SOLVE_CHECK(act.get((size_t)n * 4));
+    Work w;
+    w.n = n;
+    w.c0 = mem.as<uint64_t>();
+    w.c1 = w.c0 + n;
+    w.moves = (uint32_t *)(w.c1 + n);
+    w.misc = w.moves + n;
+    w.stk_moves = w.misc + n;
+    w.stk_ab = w.stk_moves + (size_t)n * MAX_PLY;
+    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(k_solve_init, dim3(grid), dim3(BLOCK), 0, stream, boards, n, node_budget, w, status, outcome, final_age, nodes,
+                       flags.as<uint8_t>());
+    SOLVE_CHECK(hipGetLastError());
+    std::vector<uint8_t> host_flags((size_t)n);
+    std::vector<int32_t> active, next;
+    SOLVE_CHECK(hipMemcpyAsync(host_flags.data(), flags.p, (size_t)n, hipMemcpyDeviceToHost, stream));
+    SOLVE_CHECK(hipStreamSynchronize(stream));
+    for (int64_t i = 0; i < n; ++i)
+        if (host_flags[(size_t)i]) active.push_back((int32_t)i);
+    // every launch adds min(per_launch, budget left) nodes to each row it carries, or finishes the row
+    const int64_t max_launches = node_budget / per_launch + 2;
+    for (int64_t launch = 0; !active.empty(); ++launch) {
+        if (launch >= max_launches) {
+            set_solve_err("internal: %lld rows unfinished after %lld launches", (long long)active.size(), (long long)launch);
+            return C4_ESTATE;
+        }
+        const int32_t m = (int32_t)active.size();
+        SOLVE_CHECK(hipMemcpyAsync(act.p, active.data(), (size_t)m * 4, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_solve_run, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, boards, act.as<int32_t>(), m,
+                           node_budget, per_launch, w, status, outcome, final_age, nodes, flags.as<uint8_t>());
+        SOLVE_CHECK(hipGetLastError());
+        SOLVE_CHECK(hipMemcpyAsync(host_flags.data(), flags.p, (size_t)m, hipMemcpyDeviceToHost, stream));
+        SOLVE_CHECK(hipStreamSynchronize(stream));
+        next.clear();
+        for (int32_t i = 0; i < m; ++i)
+            if (host_flags[(size_t)i]) next.push_back(active[(size_t)i]);
+        active.swap(next);
+    }
+    return C4_OK;
+}
+
+int check_args(const void *boards, int64_t n, int64_t &node_budget, int64_t &per_launch, const void *status, const void *outcome,
+               const void *final_age, const void *nodes)
+{
+    if (n < 0) { set_solve_err("n < 0"); return C4_EINVAL; }
+    if (n > 0 && (!boards || !status || !outcome || !final_age || !nodes)) { set_solve_err("null argument"); return C4_EINVAL; }
+    if (node_budget < 0 || per_launch < 0) { set_solve_err("node_budget and nodes_per_launch must not be negative (0: the default)"); return C4_EINVAL; }
+    if (node_budget == 0) node_budget = DEFAULT_BUDGET;
+    if (per_launch == 0) per_launch = DEFAULT_PER_LAUNCH;
+    if (per_launch > ((int64_t)1 << 40)) per_launch = (int64_t)1 << 40;
+    return C4_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *c4_solve_last_error(void) { return solve_err; }
+
+int c4_solve_dev(int device, void *hip_stream, const int64_t *boards_dev, int64_t n, int64_t node_budget, int64_t nodes_per_launch,
+                 int8_t *status_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev)
+{
+    int rc = check_args(boards_dev, n, node_budget, nodes_per_launch, status_dev, outcome_dev, final_age_dev, nodes_dev);
+    if (rc || n == 0) return rc;
+    rc = pick_device(device);
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    for (int64_t lo = 0; lo < n; lo += CHUNK_ROWS) {
+        const int64_t m = n - lo < CHUNK_ROWS ? n - lo : CHUNK_ROWS;
+        rc = solve_chunk(stream, boards_dev + 2 * lo, m, node_budget, nodes_per_launch, status_dev + lo, outcome_dev + lo,
+                         final_age_dev + lo, nodes_dev + lo);
+        if (rc) return rc;
+    }
+    return C4_OK;
+}
+
+int c4_solve(int device, const uint64_t *color0, const uint64_t *color1, int64_t n, int64_t node_budget, int64_t nodes_per_launch,
+             int8_t *status, int8_t *outcome, int8_t *final_age, int64_t *nodes)
+{
+    if (n > 0 && (!color0 || !color1)) { set_solve_err("null argument"); return C4_EINVAL; }
+    int rc = check_args(color0, n, node_budget, nodes_per_launch, status, outcome, final_age, nodes);
+    if (rc || n == 0) return rc;
+    rc = pick_device(device);
+    if (rc) return rc;
+    std::vector<int64_t> packed((size_t)n * 2);
+    for (int64_t i = 0; i < n; ++i) {
+        packed[(size_t)(2 * i)] = (int64_t)color0[i];
+        packed[(size_t)(2 * i + 1)] = (int64_t)color1[i];
+    }
+    DevBuf b, out;
+    SOLVE_CHECK(b.get((size_t)n * 16));
+    SOLVE_CHECK(out.get((size_t)n * 11));
+    int64_t *nodes_d = out.as<int64_t>();
+    int8_t *status_d = (int8_t *)(nodes_d + n), *outcome_d = status_d + n, *age_d = outcome_d + n;
+    SOLVE_CHECK(hipMemcpy(b.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+    rc = c4_solve_dev(device, nullptr, b.as<int64_t>(), n, node_budget, nodes_per_launch, status_d, outcome_d, age_d, nodes_d);
+    if (rc) return rc;
+    SOLVE_CHECK(hipMemcpy(nodes, nodes_d, (size_t)n * 8, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(status, status_d, (size_t)n, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(outcome, outcome_d, (size_t)n, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(final_age, age_d, (size_t)n, hipMemcpyDeviceToHost));
+    return C4_OK;
+}
+
+int c4_solve_children_dev(int device, void *hip_stream, const int64_t *boards_dev, int64_t n, int64_t *children_dev, int8_t *legal_dev)
+{
+    if (n < 0) { set_solve_err("n < 0"); return C4_EINVAL; }
+    if (n == 0) return C4_OK;
+    if (!boards_dev || !children_dev || !legal_dev) { set_solve_err("null argument"); return C4_EINVAL; }
+    int rc = pick_device(device);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_solve_children, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, boards_dev, n,
+                       children_dev, legal_dev);
+    SOLVE_CHECK(hipGetLastError());
+    return C4_OK;
+}
+
+}  // extern "C"

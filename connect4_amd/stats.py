@@ -307,6 +307,22 @@ class LabelledSet:
         d = torch.load(path, map_location="cpu", weights_only=True)
         return cls.from_tensors(d["boards"], d["values"], d.get("priors"), device=device)
 
+    def save(self, path):
+        """Write the file the reference's Connect4Dataset.save writes (data.py:22-33): a dict of CPU tensors, boards float32
+        [n, 3, 6, 7] (board.py:147-154), values float32 [n], priors float32 [n, 7] (None for a value-only set).  load() and
+        the reference's Connect4Dataset.load read it back.  A set on the GPU builds its planes there; a set on the CPU is
+        converted by the host Board."""
+        import torch
+        if self.device.type == "cuda":
+            planes = self.planes().cpu()
+        else:
+            from .board import Board
+            bits = self.boards.numpy().view(np.uint64)
+            planes = torch.from_numpy(np.stack([Board.from_bits(int(a), int(b)).to_array() for a, b in bits]).astype(np.float32)
+                                      if len(bits) else np.zeros((0, 3, 6, 7), dtype=np.float32))
+        torch.save({"boards": planes, "values": self.values.cpu(), "priors": None if self.priors is None else self.priors.cpu()},
+                   path)
+
     def planes(self):
         """The float32 planes [n, 3, 6, 7] of the boards (board.py:147-154), built on the device (c4_training_tensors_dev)."""
         import torch

@@ -634,6 +634,42 @@ int c4_score_update_dev(int device, void *hip_stream, const float *x_value, cons
                         long long rows, long long valid_rows, c4_score_acc *acc_dev, void *workspace_dev);
 const char *c4_score_last_error(void);
 
+/* -- exact values of late-game positions (c4_solve.hip) ------------------------------------------------------------------ */
+/* What the reference's GridSearch(plies >= empty squares) returns for a position (grid_search.py:38-71: no evaluator is
+ * reached, so it is the game-theoretic result, faster wins and slower losses preferred), found by alpha-beta instead of
+ * exhaustively: the outcome under best play and the age (stone count) at which that play ends the game.  The reference's
+ * float64 follows from the two: an o win 1.0 - age / 10000.0, an x win age / 10000.0, a draw 0.5 + 42 / 10000.0.
+ * One position per lane, depth first, no transposition table, nothing shared between lanes; node counts are deterministic.
+ * Per row:
+ *   status     C4_SOLVE_SOLVED    searched to the end: outcome (C4_RESULT_*) and final_age are the answer
+ *              C4_SOLVE_TERMINAL  already finished: outcome and final_age are its own; not searched
+ *              C4_SOLVE_UNKNOWN   the search would have needed more than node_budget nodes; outcome, final_age -1
+ *              C4_SOLVE_TOO_DEEP  more than C4_SOLVE_MAX_EMPTIES empty squares; not searched; outcome, final_age -1
+ *              C4_SOLVE_INVALID   the colours overlap or leave the 42 cells, a stone floats, the stone counts differ by other
+ *                                 than 0 or 1 with o first, or both sides have four in a row; not searched; -1, -1
+ *   nodes      positions entered by the search (the root is one; a position whose mover wins at once is never entered
+ *              below the root); 0 for a row that was not searched; exactly node_budget for an UNKNOWN row
+ * node_budget: most nodes of one row (0: 2^26).  nodes_per_launch: most nodes a row gets in one kernel launch (0: 2^14); a
+ * row over it parks its stack in device memory and the next launch, which carries only unfinished rows, resumes it -- so
+ * no launch runs longer than nodes_per_launch nodes of one lane, and neither answers nor node counts depend on it.
+ * c4_solve_dev: boards_dev int64 [n][2] packed boards on the device (color0, color1: what c4_export_games_dev writes), the
+ * four outputs device arrays of n.  Launches on hip_stream and waits for it between launches (synchronous).  c4_solve: the
+ * same from and to host memory.  c4_solve_children_dev: children_dev int64 [n][7][2] = the position after each column,
+ * legal_dev int8 [n][7] = 1 where the column is playable; all zero for a finished or invalid row.  One launch, no wait.
+ * A null pointer or a negative count: C4_EINVAL.  Messages: c4_solve_last_error(). */
+#define C4_SOLVE_MAX_EMPTIES 24
+#define C4_SOLVE_SOLVED 0
+#define C4_SOLVE_TERMINAL 1
+#define C4_SOLVE_UNKNOWN 2
+#define C4_SOLVE_TOO_DEEP 3
+#define C4_SOLVE_INVALID 4
+int c4_solve_dev(int device, void *hip_stream, const int64_t *boards_dev, int64_t n, int64_t node_budget, int64_t nodes_per_launch,
+                 int8_t *status_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev);
+int c4_solve(int device, const uint64_t *color0, const uint64_t *color1, int64_t n, int64_t node_budget, int64_t nodes_per_launch,
+             int8_t *status, int8_t *outcome, int8_t *final_age, int64_t *nodes);
+int c4_solve_children_dev(int device, void *hip_stream, const int64_t *boards_dev, int64_t n, int64_t *children_dev, int8_t *legal_dev);
+const char *c4_solve_last_error(void);
+
 int c4_abi_version(void);
 
 #ifdef __cplusplus

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Turn the late positions of self-play generations into an exactly labelled test set, on the GPU.
+
+    python tools/make_test_set.py SAVE_DIR_OR_DATA_PTH... [--min-age 18] [--max-positions N] [--seed S] -o endgame.pth
+
+Each argument is a data.pth, a generation's directory (holding data.pth) or a run's directory (<g>/data.pth, as
+run_generations writes them).  A data.pth holds every position and, in its second half, the mirrored copy of the flip
+augmentation (data.py:78-105): the copies are dropped, and of what remains each distinct position is kept once.  Positions
+with fewer than --min-age stones are dropped (the solver reaches positions with at most 24 empty squares: age 18);
+--max-positions keeps a random subset (--seed).  The rest is solved exactly together with its children
+(connect4_amd/solver.py: label -- value = the game-theoretic outcome, prior = uniform over the moves that keep it) and
+saved in the format of the reference's Connect4Dataset.save, which LabelledSet.load, tools/score_net.py and
+run_generations(test_sets={"endgame": "endgame.pth"}) read.  The labeller's report is printed."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def data_files(path):
+    if os.path.isfile(path):
+        return [path]
+    own = os.path.join(path, "data.pth")
+    if os.path.exists(own):
+        return [own]
+    gens = sorted(int(f.name) for f in os.scandir(path) if f.is_dir() and f.name.isdigit() and os.path.exists(os.path.join(f.path, "data.pth")))
+    if not gens:
+        raise SystemExit("%s is no data.pth and holds neither data.pth nor <generation>/data.pth" % path)
+    return [os.path.join(path, str(g), "data.pth") for g in gens]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("sources", nargs="+", metavar="SAVE_DIR_OR_DATA_PTH")
+    ap.add_argument("--min-age", type=int, default=18)
+    ap.add_argument("--max-positions", type=int, default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("-o", "--output", required=True)
+    a = ap.parse_args(argv)
+    import torch
+    import __graft_entry__ as entry
+    entry.build()
+    from connect4_amd import engine
+    from connect4_amd.solver import label
+    dev = torch.device("cuda", a.device)
+    parts, rows = [], 0
+    for src in a.sources:
+        for path in data_files(src):
+            planes = torch.load(path, map_location="cpu", weights_only=True)["boards"]
+            if planes.shape[0] % 2:
+                raise SystemExit("%s: %d rows -- a data.pth holds every position and its mirror" % (path, planes.shape[0]))
+            planes = planes[:planes.shape[0] // 2].to(dev, torch.float32)
+            rows += int(planes.shape[0])
+            with torch.cuda.device(dev):
+                boards, n_bad = engine.planes_to_boards(planes)
+            if int(n_bad.item()):
+                raise SystemExit("%s: %d rows are not the planes of a board" % (path, int(n_bad.item())))
+            age = planes[:, 1:].sum(dim=(1, 2, 3))
+            parts.append(boards[age >= a.min_age])
+    boards = torch.unique(torch.cat(parts), dim=0)
+    late = int(boards.shape[0])
+    if a.max_positions is not None and late > a.max_positions:
+        g = torch.Generator().manual_seed(a.seed)
+        pick = torch.sort(torch.randperm(late, generator=g)[:a.max_positions]).values
+        boards = boards[pick.to(dev)].contiguous()
+    ls, report = label(boards, device=a.device)
+    ls.save(a.output)
+    report = dict(report, rows_read=rows, distinct_late=late, min_age=a.min_age, output=a.output)
+    print(json.dumps(report))
+    hist = {k: int((ls.values == k).sum().item()) for k in (0.0, 0.5, 1.0)}
+    print("%s: %d positions labelled (x wins %d, draws %d, o wins %d); %d unknown, %.2f s, %d nodes" % (
+        a.output, len(ls), hist[0.0], hist[0.5], hist[1.0], report["unknown"], report["seconds"], report["nodes"]))
+    return report
+
+
+if __name__ == "__main__":
+    main()
