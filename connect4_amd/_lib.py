@@ -24,6 +24,8 @@ PV_VALUE, PV_VISITS = 0, 1
 NET_F16, NET_F32X3, NET_F32X3_WIDE = 0, 1, 2   # c4_net_desc.precision
 MATCH_MAX_NETS = 16
 SOLVE_MAX_EMPTIES = 24
+SOLVE_DEEP_MAX_EMPTIES = 42
+SOLVE_TABLE_MIN_LOG2, SOLVE_TABLE_MAX_LOG2 = 10, 30
 SOLVE_SOLVED, SOLVE_TERMINAL, SOLVE_UNKNOWN, SOLVE_TOO_DEEP, SOLVE_INVALID = 0, 1, 2, 3, 4
 
 
@@ -208,6 +210,12 @@ SIGNATURES = {
     "c4_solve": (C.c_int, [C.c_int, _u64p, _u64p, C.c_int64, C.c_int64, C.c_int64, _P(C.c_int8), _P(C.c_int8), _P(C.c_int8), _i64p]),
     "c4_solve_children_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "c4_solve_last_error": (C.c_char_p, []),
+    "c4_solve_table_create": (C.c_int, [C.c_int, C.c_int, _P(C.c_void_p)]),
+    "c4_solve_table_destroy": (C.c_int, [C.c_void_p]),
+    "c4_solve_table_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "c4_solve_deep_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 5),
+    "c4_solve_deep": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, C.c_int64, C.c_int64, C.c_int64, _P(C.c_int8), _P(C.c_int8),
+                                _P(C.c_int8), _i64p, _i64p]),
 }
 
 _lib = None

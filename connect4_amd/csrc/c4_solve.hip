@@ -28,6 +28,26 @@
 // it stores its registers and frames to global memory and stops.  The host relaunches the unfinished
 // positions, compacted into a dense index list, until all are done or a position's total has reached
 // its budget (status UNKNOWN).  No lane waits for another lane, wave or workgroup; no atomics.
+//
+// Deep search (c4_solve_deep / c4_solve_deep_dev, k_solve_deep).  The same search -- the same enter_node, order_moves,
+// run_lane, frames and park / compact / relaunch loop -- with 42 plies of frames (2 x 42 x 64 x 4 B = 21 KiB of LDS, all
+// frames in LDS: seven one-wave workgroups still fit a CU) and, optionally, a transposition table in device memory that
+// every lane of every launch of every call shares.
+//   * An entry is one aligned 64-bit word: the position's key in bits 0..48 (mover's stones + occupied + BOTTOM, which
+//     is injective), the score + 64 in bits 49..55, the bound's kind in bits 56..57 (lower, upper, exact; 0: empty).
+//     It is read by one relaxed 64-bit atomic load and written by one relaxed 64-bit atomic store: a reader sees a
+//     whole entry, old or new, and a hit compares the whole key, so it is a hit on this very position.
+//   * The score is the mover's 43 - final age form and is a true bound of the position's value whatever window it was
+//     found with, so an entry holds for every row, launch and call; a stale entry does not exist.
+//   * A node probes after enter_node says interior: an entry that closes the window is returned, another narrows
+//     it.  A node stores when it closes (its moves are used up, or one cuts off), against the window its moves were
+//     searched with: the frame keeps that alpha in bits 16..23 of its alpha / beta word.  Always replace.  Nodes with
+//     fewer than TT_MIN_EMPTIES empty squares neither probe nor store.
+//   * Probe and store are straight-line code: the termination argument above holds word for word -- no lane waits for
+//     another, the only atomics are that load and that store.
+//   * Answers are exact and do not depend on the table (alpha-beta returns the same root value for every sound set of
+//     bounds).  NODE COUNTS WITH A TABLE ARE NOT DETERMINISTIC: they depend on what other lanes stored first.  With a
+//     null table they are, and they equal k_solve_run's and solver._Search's.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -45,6 +65,10 @@ namespace {
 
 constexpr int MAX_EMPTIES = C4_SOLVE_MAX_EMPTIES;
 constexpr int MAX_PLY = MAX_EMPTIES;            // frames of one lane (a node with one empty square is a leaf)
+constexpr int DEEP_MAX_EMPTIES = C4_SOLVE_DEEP_MAX_EMPTIES;
+constexpr int DEEP_MAX_PLY = DEEP_MAX_EMPTIES;  // k_solve_deep's frames: 2 x 42 x 64 x 4 B = 21 KiB of LDS
+constexpr int TT_MIN_EMPTIES = 6;               // nodes nearer the end are cheaper to search than to look up
+constexpr int TT_MIN_LOG2 = 10, TT_MAX_LOG2 = 30;
 constexpr int BLOCK = 64;                       // one wave per workgroup: 2 x 24 x 64 x 4 B = 12 KiB of LDS
 constexpr uint64_t BOARD = BOTTOM * COLMASK;    // the 42 cells
 constexpr int SCORE_MAX = 42;                   // beyond every score (the fastest win, at age 7, scores 36)
@@ -143,15 +167,73 @@ struct Lane {
     uint64_t c0, c1;
     uint32_t moves;
     int d, alpha, beta, ret;
+    int alpha0 = 0;     // with a table: the alpha the node's moves were entered with
+    int hits = 0;       // with a table: probes that returned or narrowed
     bool pending;       // the node at depth d has returned `ret`
     bool done;          // the root has returned
 };
 
 C4_HD uint32_t pack_ab(int alpha, int beta) { return (uint32_t)(alpha + 64) | ((uint32_t)(beta + 64) << 8); }
 
+// -- the transposition table ------------------------------------------------------------------------------------------
+constexpr uint64_t TT_KEY_MASK = (1ULL << 49) - 1;
+constexpr int TT_LOWER = 1, TT_UPPER = 2, TT_EXACT = 3;
+
+struct NoTable {        // k_solve_run: no table code is compiled
+    static constexpr bool compiled = false;
+};
+
+struct TableRef {       // k_solve_deep: e == nullptr is the table-free search
+    static constexpr bool compiled = true;
+    uint64_t *e;
+    int shift;          // 64 - log2(entries)
+};
+
+C4_HD uint64_t tt_key(uint64_t mine, uint64_t occ) { return mine + occ + BOTTOM; }
+C4_HD bool tt_covers(const TableRef t, int age) { return t.e != nullptr && CELLS - age >= TT_MIN_EMPTIES; }
+C4_HD size_t tt_slot(const TableRef t, uint64_t key) { return (size_t)((key * 0x9E3779B97F4A7C15ULL) >> t.shift); }
+
+// hit 0: nothing known; 1: the entry narrowed alpha or beta; 2: the entry closes the window, `value` is what the node
+// returns.  By value and branch-free: a store through a selected reference would put the window into scratch.
+struct Probe {
+    int hit, alpha, beta, value;
+};
+
+__device__ __forceinline__ Probe tt_probe(const TableRef t, uint64_t key, int alpha, int beta)
+{
+    const uint64_t w = __hip_atomic_load(t.e + tt_slot(t, key), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool match = (w & TT_KEY_MASK) == key;
+    const int s = (int)((w >> 49) & 0x7f) - 64, kind = (int)((w >> 56) & 3);
+    const bool closes = kind == TT_EXACT || (kind == TT_LOWER && s >= beta) || (kind == TT_UPPER && s <= alpha);
+    const bool up = kind == TT_LOWER && s > alpha, down = kind == TT_UPPER && s < beta;
+    Probe p;
+    p.hit = !match ? 0 : closes ? 2 : (up || down) ? 1 : 0;
+    p.alpha = p.hit == 1 && up ? s : alpha;
+    p.beta = p.hit == 1 && down ? s : beta;
+    p.value = s;
+    return p;
+}
+
+__device__ __forceinline__ void tt_store(const TableRef t, uint64_t key, int score, int kind)
+{
+    const uint64_t w = key | ((uint64_t)(score + 64) << 49) | ((uint64_t)kind << 56);
+    __hip_atomic_store(t.e + tt_slot(t, key), w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the node the lane stands at closes with L.ret
+template <class T>
+__device__ __forceinline__ void tt_close(const T tt, const Lane &L, int kind)
+{
+    if constexpr (T::compiled) {
+        const uint64_t occ = L.c0 | L.c1;
+        const int age = popc64(occ);
+        if (tt_covers(tt, age)) tt_store(tt, tt_key((age & 1) ? L.c1 : L.c0, occ), L.ret, kind);
+    }
+}
+
 // The status of a row before any search (c4_engine.h C4_SOLVE_*; SOLVED here means: to be searched).  A
 // finished position carries its own outcome and age.
-C4_HD int classify(uint64_t c0, uint64_t c1, int &outcome, int &final_age)
+C4_HD int classify(uint64_t c0, uint64_t c1, int &outcome, int &final_age, int max_empties = MAX_EMPTIES)
 {
     const uint64_t occ = c0 | c1;
     const int n0 = popc64(c0), n1 = popc64(c1);
@@ -165,7 +247,7 @@ C4_HD int classify(uint64_t c0, uint64_t c1, int &outcome, int &final_age)
         final_age = n0 + n1;
         return C4_SOLVE_TERMINAL;
     }
-    if (CELLS - (n0 + n1) > MAX_EMPTIES) return C4_SOLVE_TOO_DEEP;
+    if (CELLS - (n0 + n1) > max_empties) return C4_SOLVE_TOO_DEEP;
     return C4_SOLVE_SOLVED;
 }
 
@@ -204,9 +286,10 @@ C4_HD void enter_root(uint64_t c0, uint64_t c1, Lane &L)
 
 // Run lane L for at most `quota` more nodes.  S: the frames below the top one, S.moves(p) / S.ab(p) for ply p.
 // Returns the nodes entered.  Every iteration pops a frame, closes a node or enters one, so 3 * quota + 64
-// iterations cover the quota and the unwinding of a full stack.
-template <class S>
-C4_HD int64_t run_lane(Lane &L, S &stk, int64_t quota)
+// iterations cover the quota and the unwinding of a full stack.  MAXP: the frames S holds.  tt: NoTable, or a TableRef
+// (probe on entering an interior node, store on closing one; neither adds an iteration).
+template <int MAXP, class S, class T>
+C4_HD int64_t run_lane(Lane &L, S &stk, const T tt, int64_t quota)
 {
     int64_t used = 0;
     const int64_t max_iter = 3 * quota + 64;
@@ -223,9 +306,12 @@ C4_HD int64_t run_lane(Lane &L, S &stk, int64_t quota)
             L.moves = m;
             L.alpha = (int)(ab & 0xff) - 64;
             L.beta = (int)((ab >> 8) & 0xff) - 64;
+            if constexpr (T::compiled) L.alpha0 = (int)((ab >> 16) & 0xff) - 64;
             const int v = -L.ret;
-            if (v >= L.beta) L.ret = v;             // cut-off: this node returns as well
-            else {
+            if (v >= L.beta) {                      // cut-off: this node returns as well
+                L.ret = v;
+                tt_close(tt, L, TT_LOWER);
+            } else {
                 if (v > L.alpha) L.alpha = v;
                 L.pending = false;
             }
@@ -234,11 +320,13 @@ C4_HD int64_t run_lane(Lane &L, S &stk, int64_t quota)
             if (moves_left(L.moves) == 0) {
                 L.ret = L.alpha;
                 L.pending = true;
-            } else if (L.d < MAX_PLY) {
+                tt_close(tt, L, L.alpha > L.alpha0 ? TT_EXACT : TT_UPPER);
+            } else if (L.d < MAXP) {
                 const int col = (int)(L.moves & 7);
                 const uint32_t rest = ((L.moves & 0xffffffu) >> 3) | ((uint32_t)(moves_left(L.moves) - 1) << 24);
                 stk.moves(L.d) = rest | ((uint32_t)col << 27);
-                stk.ab(L.d) = pack_ab(L.alpha, L.beta);
+                if constexpr (T::compiled) stk.ab(L.d) = pack_ab(L.alpha, L.beta) | ((uint32_t)(L.alpha0 + 64) << 16);
+                else stk.ab(L.d) = pack_ab(L.alpha, L.beta);
                 ++L.d;
                 (void)make_move(L.c0, L.c1, col);
                 ++used;
@@ -254,9 +342,22 @@ C4_HD int64_t run_lane(Lane &L, S &stk, int64_t quota)
                     L.alpha = a;
                     L.beta = b;
                     L.moves = moves;
+                    if constexpr (T::compiled) {
+                        if (tt_covers(tt, age)) {
+                            const Probe p = tt_probe(tt, tt_key(mine, occ), a, b);
+                            L.hits += p.hit ? 1 : 0;
+                            L.alpha = p.alpha;
+                            L.beta = p.beta;
+                            if (p.hit == 2) {
+                                L.ret = p.value;
+                                L.pending = true;
+                            }
+                        }
+                        L.alpha0 = L.alpha;
+                    }
                 }
             } else {
-                L.ret = L.alpha;        // not reachable: a node MAX_PLY deep has no empty square
+                L.ret = L.alpha;        // not reachable: a node MAXP deep has no empty square
                 L.pending = true;
             }
         }
@@ -301,22 +402,41 @@ __device__ __forceinline__ void store_answer(const int64_t *boards, int64_t row,
 
 // one lane per row: status, the answers that need no search, the root of the others; unfinished[row] = 1
 // for a row that k_solve_run has to continue
+// for the deep search (`deep`): every depth is searchable, the root probes the table `tt` like any interior node, and the
+// parked word carries alpha0 where k_solve_run's carries ret (neither is read: the root is not pending); hits: or null
 __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict__ boards, int64_t n, int64_t node_budget, Work w,
                                                       int8_t *__restrict__ status, int8_t *__restrict__ outcome,
                                                       int8_t *__restrict__ final_age, int64_t *__restrict__ nodes,
-                                                      uint8_t *__restrict__ unfinished)
+                                                      uint8_t *__restrict__ unfinished, bool deep, TableRef tt,
+                                                      int64_t *__restrict__ hits)
 {
     const int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (row >= n) return;
     const uint64_t c0 = (uint64_t)boards[2 * row], c1 = (uint64_t)boards[2 * row + 1];
     int o, fa;
-    int st = classify(c0, c1, o, fa);
+    int st = classify(c0, c1, o, fa, deep ? DEEP_MAX_EMPTIES : MAX_EMPTIES);
     int64_t nd = 0;
     uint8_t more = 0;
+    int hit = 0;
     if (st == C4_SOLVE_SOLVED) {
         Lane L;
         enter_root(c0, c1, L);
         nd = 1;
+        if (deep && !L.done) {
+            const uint64_t occ = c0 | c1;
+            const int age = popc64(occ);
+            if (tt_covers(tt, age)) {
+                const Probe p = tt_probe(tt, tt_key((age & 1) ? c1 : c0, occ), L.alpha, L.beta);
+                hit = p.hit;
+                L.alpha = p.alpha;
+                L.beta = p.beta;
+                if (hit == 2) {
+                    L.ret = p.value;
+                    L.done = true;
+                }
+            }
+            L.ret = L.done ? L.ret : L.alpha;       // the parked word's third field: alpha0
+        }
         if (L.done) root_answer(popc64(c0 | c1), L.ret, o, fa);
         else if (nd >= node_budget) st = C4_SOLVE_UNKNOWN;
         else {
@@ -332,6 +452,7 @@ __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict_
     final_age[row] = (int8_t)fa;
     nodes[row] = nd;
     unfinished[row] = more;
+    if (hits) hits[row] = hit ? 1 : 0;
 }
 
 // one lane per unfinished row, through the dense list `active`: load, search up to the quota, store
@@ -369,7 +490,7 @@ __global__ void __launch_bounds__(BLOCK) k_solve_run(const int64_t *__restrict__
     const int64_t total = nodes[row];
     const int64_t left = node_budget - total;
     const int64_t quota = left < nodes_per_launch ? left : nodes_per_launch;
-    const int64_t used = run_lane(L, stk, quota);
+    const int64_t used = run_lane<MAX_PLY>(L, stk, NoTable{}, quota);
     nodes[row] = total + used;
     if (L.done) {
         store_answer(boards, row, L, outcome, final_age);
@@ -387,6 +508,70 @@ __global__ void __launch_bounds__(BLOCK) k_solve_run(const int64_t *__restrict__
     w.moves[row] = L.moves;
     w.misc[row] = pack_ab(L.alpha, L.beta) | ((uint32_t)(L.ret + 64) << 16) | ((uint32_t)L.d << 24) | ((uint32_t)(L.pending ? 1 : 0) << 30);
     for (int p = 0; p < MAX_PLY; ++p) {
+        if (p < L.d) {
+            w.stk_moves[(int64_t)p * w.n + row] = s_moves[p][threadIdx.x];
+            w.stk_ab[(int64_t)p * w.n + row] = s_ab[p][threadIdx.x];
+        }
+    }
+}
+
+// k_solve_run for positions of any depth, with or without a table (tt.e == nullptr).  The frames are DEEP_MAX_PLY deep, in
+// LDS and in `w`; the third field of the parked word is ret for a pending lane, else the top frame's alpha0.
+__global__ void __launch_bounds__(BLOCK) k_solve_deep(const int64_t *__restrict__ boards, const int32_t *__restrict__ active, int32_t m,
+                                                      int64_t node_budget, int64_t nodes_per_launch, Work w, TableRef tt,
+                                                      int8_t *__restrict__ status, int8_t *__restrict__ outcome,
+                                                      int8_t *__restrict__ final_age, int64_t *__restrict__ nodes,
+                                                      int64_t *__restrict__ hits, uint8_t *__restrict__ unfinished)
+{
+    __shared__ uint32_t s_moves[DEEP_MAX_PLY][BLOCK];
+    __shared__ uint32_t s_ab[DEEP_MAX_PLY][BLOCK];
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= m) return;
+    const int64_t row = active[i];
+    if (row < 0 || row >= w.n) return;
+    LdsStack stk{s_moves, s_ab, (int)threadIdx.x};
+    Lane L;
+    L.c0 = w.c0[row];
+    L.c1 = w.c1[row];
+    L.moves = w.moves[row];
+    const uint32_t misc = w.misc[row];
+    L.alpha = (int)(misc & 0xff) - 64;
+    L.beta = (int)((misc >> 8) & 0xff) - 64;
+    L.d = (int)((misc >> 24) & 0x3f);
+    L.pending = ((misc >> 30) & 1) != 0;
+    L.ret = L.pending ? (int)((misc >> 16) & 0xff) - 64 : 0;
+    L.alpha0 = L.pending ? L.alpha : (int)((misc >> 16) & 0xff) - 64;
+    L.done = false;
+    if (L.d > DEEP_MAX_PLY) L.d = DEEP_MAX_PLY;
+    for (int p = 0; p < DEEP_MAX_PLY; ++p) {
+        if (p < L.d) {
+            s_moves[p][threadIdx.x] = w.stk_moves[(int64_t)p * w.n + row];
+            s_ab[p][threadIdx.x] = w.stk_ab[(int64_t)p * w.n + row];
+        }
+    }
+    const int64_t total = nodes[row];
+    const int64_t left = node_budget - total;
+    const int64_t quota = left < nodes_per_launch ? left : nodes_per_launch;
+    const int64_t used = run_lane<DEEP_MAX_PLY>(L, stk, tt, quota);
+    nodes[row] = total + used;
+    if (hits) hits[row] += L.hits;
+    if (L.done) {
+        store_answer(boards, row, L, outcome, final_age);
+        unfinished[i] = 0;
+        return;
+    }
+    if (total + used >= node_budget) {      // it would take a node beyond the budget to go on
+        status[row] = C4_SOLVE_UNKNOWN;
+        unfinished[i] = 0;
+        return;
+    }
+    unfinished[i] = 1;
+    w.c0[row] = L.c0;
+    w.c1[row] = L.c1;
+    w.moves[row] = L.moves;
+    w.misc[row] = pack_ab(L.alpha, L.beta) | ((uint32_t)((L.pending ? L.ret : L.alpha0) + 64) << 16) | ((uint32_t)L.d << 24) |
+                  ((uint32_t)(L.pending ? 1 : 0) << 30);
+    for (int p = 0; p < DEEP_MAX_PLY; ++p) {
         if (p < L.d) {
             w.stk_moves[(int64_t)p * w.n + row] = s_moves[p][threadIdx.x];
             w.stk_ab[(int64_t)p * w.n + row] = s_ab[p][threadIdx.x];
@@ -447,12 +632,15 @@ int pick_device(int device)
     return C4_OK;
 }
 
-// one pass: rows [0, n) of `boards`, n <= CHUNK_ROWS
+// one pass: rows [0, n) of `boards`, n <= CHUNK_ROWS.  deep: k_solve_deep with the table `tt` (or none) and 42 plies of
+// parked frames (360 B a row), hits: table_hits or null; else k_solve_run
 int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t node_budget, int64_t per_launch, int8_t *status,
-                int8_t *outcome, int8_t *final_age, int64_t *nodes)
+                int8_t *outcome, int8_t *final_age, int64_t *nodes, bool deep = false, TableRef tt = TableRef{nullptr, 0},
+                int64_t *hits = nullptr)
 {
     DevBuf mem, flags, act;
-    const size_t words = (size_t)n * (4 + 2 + 2 * MAX_PLY);      // 32-bit words a row
+    const int max_ply = deep ? DEEP_MAX_PLY : MAX_PLY;
+    const size_t words = (size_t)n * (4 + 2 + 2 * max_ply);      // 32-bit words a row
     SOLVE_CHECK(mem.get(words * 4));
     SOLVE_CHECK(flags.get((size_t)n));
     SOLVE_CHECK(act.get((size_t)n * 4));
@@ -463,10 +651,10 @@ int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t no
     w.moves = (uint32_t *)(w.c1 + n);
     w.misc = w.moves + n;
     w.stk_moves = w.misc + n;
-    w.stk_ab = w.stk_moves + (size_t)n * MAX_PLY;
+    w.stk_ab = w.stk_moves + (size_t)n * max_ply;
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
     hipLaunchKernelGGL(k_solve_init, dim3(grid), dim3(BLOCK), 0, stream, boards, n, node_budget, w, status, outcome, final_age, nodes,
-                       flags.as<uint8_t>());
+                       flags.as<uint8_t>(), deep, tt, hits);
     SOLVE_CHECK(hipGetLastError());
     std::vector<uint8_t> host_flags((size_t)n);
     std::vector<int32_t> active, next;
@@ -483,8 +671,12 @@ int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t no
         }
         const int32_t m = (int32_t)active.size();
         SOLVE_CHECK(hipMemcpyAsync(act.p, active.data(), (size_t)m * 4, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(k_solve_run, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, boards, act.as<int32_t>(), m,
-                           node_budget, per_launch, w, status, outcome, final_age, nodes, flags.as<uint8_t>());
+        if (deep)
+            hipLaunchKernelGGL(k_solve_deep, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, boards, act.as<int32_t>(),
+                               m, node_budget, per_launch, w, tt, status, outcome, final_age, nodes, hits, flags.as<uint8_t>());
+        else
+            hipLaunchKernelGGL(k_solve_run, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, boards, act.as<int32_t>(), m,
+                               node_budget, per_launch, w, status, outcome, final_age, nodes, flags.as<uint8_t>());
         SOLVE_CHECK(hipGetLastError());
         SOLVE_CHECK(hipMemcpyAsync(host_flags.data(), flags.p, (size_t)m, hipMemcpyDeviceToHost, stream));
         SOLVE_CHECK(hipStreamSynchronize(stream));
@@ -505,6 +697,33 @@ int check_args(const void *boards, int64_t n, int64_t &node_budget, int64_t &per
     if (node_budget == 0) node_budget = DEFAULT_BUDGET;
     if (per_launch == 0) per_launch = DEFAULT_PER_LAUNCH;
     if (per_launch > ((int64_t)1 << 40)) per_launch = (int64_t)1 << 40;
+    return C4_OK;
+}
+
+}  // namespace
+
+struct c4_solve_table {
+    int device;
+    int log2_entries;
+    uint64_t *entries;
+};
+
+namespace {
+
+// the table's reference for a call on `device`: C4_EINVAL for a table of another device
+int table_ref(const c4_solve_table *table, int device, TableRef &tt)
+{
+    tt = TableRef{nullptr, 0};
+    if (!table) return C4_OK;
+    if (!table->entries || table->log2_entries < TT_MIN_LOG2 || table->log2_entries > TT_MAX_LOG2) {
+        set_solve_err("not a table of c4_solve_table_create");
+        return C4_EINVAL;
+    }
+    if (table->device != device) {
+        set_solve_err("the table lives on device %d, the call is for device %d", table->device, device);
+        return C4_EINVAL;
+    }
+    tt = TableRef{table->entries, 64 - table->log2_entries};
     return C4_OK;
 }
 
@@ -553,6 +772,106 @@ int c4_solve(int device, const uint64_t *color0, const uint64_t *color1, int64_t
     rc = c4_solve_dev(device, nullptr, b.as<int64_t>(), n, node_budget, nodes_per_launch, status_d, outcome_d, age_d, nodes_d);
     if (rc) return rc;
     SOLVE_CHECK(hipMemcpy(nodes, nodes_d, (size_t)n * 8, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(status, status_d, (size_t)n, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(outcome, outcome_d, (size_t)n, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(final_age, age_d, (size_t)n, hipMemcpyDeviceToHost));
+    return C4_OK;
+}
+
+int c4_solve_table_create(int device, int log2_entries, c4_solve_table **out)
+{
+    if (!out) { set_solve_err("null argument"); return C4_EINVAL; }
+    *out = nullptr;
+    if (log2_entries < TT_MIN_LOG2 || log2_entries > TT_MAX_LOG2) {
+        set_solve_err("log2_entries %d outside %d..%d", log2_entries, TT_MIN_LOG2, TT_MAX_LOG2);
+        return C4_EINVAL;
+    }
+    int rc = pick_device(device);
+    if (rc) return rc;
+    const size_t bytes = (size_t)8 << log2_entries;
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_solve_err("no device memory for a table of 2^%d entries (%zu bytes)", log2_entries, bytes);
+        return C4_ENOMEM;
+    }
+    hipError_t r = hipMemset(p, 0, bytes);
+    if (r == hipSuccess) r = hipDeviceSynchronize();
+    if (r != hipSuccess) {
+        (void)hipFree(p);
+        set_solve_err("clearing the table failed: %s", hipGetErrorString(r));
+        return C4_EDEVICE;
+    }
+    *out = new c4_solve_table{device, log2_entries, (uint64_t *)p};
+    return C4_OK;
+}
+
+int c4_solve_table_destroy(c4_solve_table *table)
+{
+    if (!table) return C4_OK;
+    if (pick_device(table->device) == C4_OK && table->entries) (void)hipFree(table->entries);
+    delete table;
+    return C4_OK;
+}
+
+int c4_solve_table_clear(c4_solve_table *table, void *hip_stream)
+{
+    if (!table || !table->entries) { set_solve_err("null argument"); return C4_EINVAL; }
+    int rc = pick_device(table->device);
+    if (rc) return rc;
+    SOLVE_CHECK(hipMemsetAsync(table->entries, 0, (size_t)8 << table->log2_entries, (hipStream_t)hip_stream));
+    SOLVE_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
+    return C4_OK;
+}
+
+int c4_solve_deep_dev(int device, void *hip_stream, c4_solve_table *table, const int64_t *boards_dev, int64_t n, int64_t node_budget,
+                      int64_t nodes_per_launch, int8_t *status_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev,
+                      int64_t *table_hits_dev)
+{
+    int rc = check_args(boards_dev, n, node_budget, nodes_per_launch, status_dev, outcome_dev, final_age_dev, nodes_dev);
+    if (rc) return rc;
+    TableRef tt;
+    rc = table_ref(table, device, tt);
+    if (rc || n == 0) return rc;
+    rc = pick_device(device);
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    for (int64_t lo = 0; lo < n; lo += CHUNK_ROWS) {
+        const int64_t m = n - lo < CHUNK_ROWS ? n - lo : CHUNK_ROWS;
+        rc = solve_chunk(stream, boards_dev + 2 * lo, m, node_budget, nodes_per_launch, status_dev + lo, outcome_dev + lo,
+                         final_age_dev + lo, nodes_dev + lo, true, tt, table_hits_dev ? table_hits_dev + lo : nullptr);
+        if (rc) return rc;
+    }
+    return C4_OK;
+}
+
+int c4_solve_deep(int device, c4_solve_table *table, const uint64_t *color0, const uint64_t *color1, int64_t n, int64_t node_budget,
+                  int64_t nodes_per_launch, int8_t *status, int8_t *outcome, int8_t *final_age, int64_t *nodes, int64_t *table_hits)
+{
+    if (n > 0 && (!color0 || !color1)) { set_solve_err("null argument"); return C4_EINVAL; }
+    int rc = check_args(color0, n, node_budget, nodes_per_launch, status, outcome, final_age, nodes);
+    if (rc) return rc;
+    TableRef tt;
+    rc = table_ref(table, device, tt);
+    if (rc || n == 0) return rc;
+    rc = pick_device(device);
+    if (rc) return rc;
+    std::vector<int64_t> packed((size_t)n * 2);
+    for (int64_t i = 0; i < n; ++i) {
+        packed[(size_t)(2 * i)] = (int64_t)color0[i];
+        packed[(size_t)(2 * i + 1)] = (int64_t)color1[i];
+    }
+    DevBuf b, out;
+    SOLVE_CHECK(b.get((size_t)n * 16));
+    SOLVE_CHECK(out.get((size_t)n * 19));
+    int64_t *nodes_d = out.as<int64_t>(), *hits_d = nodes_d + n;
+    int8_t *status_d = (int8_t *)(hits_d + n), *outcome_d = status_d + n, *age_d = outcome_d + n;
+    SOLVE_CHECK(hipMemcpy(b.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+    rc = c4_solve_deep_dev(device, nullptr, table, b.as<int64_t>(), n, node_budget, nodes_per_launch, status_d, outcome_d, age_d,
+                           nodes_d, hits_d);
+    if (rc) return rc;
+    SOLVE_CHECK(hipMemcpy(nodes, nodes_d, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (table_hits) SOLVE_CHECK(hipMemcpy(table_hits, hits_d, (size_t)n * 8, hipMemcpyDeviceToHost));
     SOLVE_CHECK(hipMemcpy(status, status_d, (size_t)n, hipMemcpyDeviceToHost));
     SOLVE_CHECK(hipMemcpy(outcome, outcome_d, (size_t)n, hipMemcpyDeviceToHost));
     SOLVE_CHECK(hipMemcpy(final_age, age_d, (size_t)n, hipMemcpyDeviceToHost));

@@ -4,14 +4,17 @@ The reference defines a position's exact value through ``GridSearch(plies >= emp
 (oinkoink/grid_search.py:38-71), so the search returns the game-theoretic result with its terminal scoring -- an o win that
 ends at age ``a`` is ``1 - a/10000``, an x win ``a/10000``, a draw ``0.5 + 42/10000``.  That search is exhaustive; the kernel
 behind this module (connect4_amd/csrc/c4_solve.hip) finds the same number by alpha-beta, for positions with at most
-``MAX_EMPTIES`` = 24 empty squares.
+``MAX_EMPTIES`` = 24 empty squares -- and, asked for with ``deep=True``, a ``Table`` or ``split_plies``, for every position
+(``DEEP_MAX_EMPTIES`` = 42): the same search with 42 plies of stack, a transposition table in device memory that all rows of
+all calls share, and a split that spreads one hard position over many lanes.  Neither changes an answer.
 
-``solve``       status, outcome, final age, the reference's float64 value and the node count of every row
+``solve``       status, outcome, final age, the reference's float64 value, the node count and the table hits of every row
+``Table``       the owner of a device transposition table
 ``grid_triple`` ``(move, value, tree)`` per board, what ``grid_search(boards, plies=empties, evaluate_centre)`` returns
 ``label``       a ``LabelledSet`` (value = outcome, prior = uniform over the moves that keep it: the rule of
                 oinkoink/scripts/generate_7ply.py:83-91) and a report
 ``solve_host``  a plain-Python mirror of the kernel's search -- same integer score, same pruning and move order, same node
-                counts -- for tests and for machines without a GPU
+                counts -- for tests and for machines without a GPU; with ``table={}`` also of its probe / store logic
 
 The integer score: a game o wins at age ``a`` scores ``43 - a``, one x wins ``a - 43``, a draw 0, taken from the side to
 move inside the search.  It is strictly monotone in the reference's float, so max / min over it pick what the reference's
@@ -28,15 +31,16 @@ from .board import BOTTOM, H1, HEIGHT, SIZE, WIDTH, Board, _wins
 from .grid_search import GridTree, _terminal_value
 from .utils import Side
 
-__all__ = ["MAX_EMPTIES", "DEFAULT_NODE_BUDGET", "STATUS_NAMES", "Solved", "HostAnswer", "solve", "solve_host", "grid_triple",
-           "label", "prior_from_children", "value_from_answer", "random_playout"]
+__all__ = ["MAX_EMPTIES", "DEEP_MAX_EMPTIES", "DEFAULT_NODE_BUDGET", "STATUS_NAMES", "Solved", "HostAnswer", "Table", "solve", "solve_host",
+           "grid_triple", "label", "prior_from_children", "value_from_answer", "random_playout", "random_openings"]
 
 MAX_EMPTIES = L.SOLVE_MAX_EMPTIES
+DEEP_MAX_EMPTIES = L.SOLVE_DEEP_MAX_EMPTIES     # every position: c4_solve_deep and solve(deep=True / table=)
 DEFAULT_NODE_BUDGET = 1 << 26          # the kernel's default (c4_engine.h)
 STATUS_NAMES = {L.SOLVE_SOLVED: "solved", L.SOLVE_TERMINAL: "terminal", L.SOLVE_UNKNOWN: "unknown",
                 L.SOLVE_TOO_DEEP: "too_deep", L.SOLVE_INVALID: "invalid"}
 
-Solved = namedtuple("Solved", "status outcome final_age value nodes")
+Solved = namedtuple("Solved", "status outcome final_age value nodes table_hits")
 HostAnswer = namedtuple("HostAnswer", "status outcome final_age value nodes")
 
 _BOARD = BOTTOM * ((1 << HEIGHT) - 1)
@@ -64,6 +68,22 @@ def random_playout(rng, n_stones):
             return b
 
 
+def random_openings(plies, count, seed=0, max_draws=None):
+    """`count` distinct undecided positions after `plies` uniformly random legal moves (``random_playout`` from
+    ``RandomState(seed)``), in the order drawn: a sample of the set the reference's ``make_random_ips(plies)`` enumerates
+    (oinkoink/board.py:225-243).  Fewer than `count` if `max_draws` (default 64 * count + 64) playouts do not yield them."""
+    rng = np.random.RandomState(seed)
+    seen, out = set(), []
+    for _ in range(64 * count + 64 if max_draws is None else max_draws):
+        if len(out) >= count:
+            break
+        b = random_playout(rng, plies)
+        if tuple(b.color) not in seen:
+            seen.add(tuple(b.color))
+            out.append(b)
+    return out
+
+
 # -- the host mirror ------------------------------------------------------------------------------------------------------
 def _winning_squares(p, occ):
     r = (p << 1) & (p << 2) & (p << 3)
@@ -81,10 +101,18 @@ class _OverBudget(Exception):
     pass
 
 
+_LOWER, _UPPER, _EXACT = 1, 2, 3        # the bound kinds of a table entry (c4_solve.hip TT_*)
+_TT_MIN_EMPTIES = 6                     # nodes with fewer empty squares neither probe nor store (c4_solve.hip)
+
+
 class _Search:
-    def __init__(self, budget):
+    """`table`: None, or a dict ``key -> (kind, score)`` -- the kernel's transposition table without its replacement."""
+
+    def __init__(self, budget, table=None):
         self.nodes = 0
         self.budget = budget
+        self.table = table
+        self.hits = 0
 
     def enter(self):
         if self.nodes >= self.budget:
@@ -117,6 +145,29 @@ class _Search:
             alpha = lo
             if alpha >= beta:
                 return alpha
+        if self.table is not None and SIZE - age >= _TT_MIN_EMPTIES:
+            # probe (c4_solve.hip tt_probe): the key is the position, the score its mover's, so an entry is a true bound
+            # wherever and whenever it was written
+            key = mine + occ + BOTTOM
+            hit = self.table.get(key)
+            if hit is not None:
+                kind, s = hit
+                if kind == _EXACT or (kind == _LOWER and s >= beta) or (kind == _UPPER and s <= alpha):
+                    self.hits += 1
+                    return s
+                if kind == _LOWER and s > alpha:
+                    alpha = s
+                    self.hits += 1
+                elif kind == _UPPER and s < beta:
+                    beta = s
+                    self.hits += 1
+            ret = self._moves(mine, theirs, occ, possible, age, alpha, beta)
+            # store (tt_store): against the window the moves were searched with
+            self.table[key] = (_UPPER if ret <= alpha else _LOWER if ret >= beta else _EXACT, ret)
+            return ret
+        return self._moves(mine, theirs, occ, possible, age, alpha, beta)
+
+    def _moves(self, mine, theirs, occ, possible, age, alpha, beta):
         keyed = []
         for c in range(WIDTH):
             bit = possible & (_COL << (H1 * c))
@@ -132,25 +183,30 @@ class _Search:
         return alpha
 
 
-def _classify(c0, c1):
+def _classify(c0, c1, max_empties=None):
+    max_empties = MAX_EMPTIES if max_empties is None else max_empties
     occ = c0 | c1
     n0, n1 = bin(c0).count("1"), bin(c1).count("1")
     if (c0 & c1) or (occ & ~_BOARD) or (occ & (occ + BOTTOM)) or not 0 <= n0 - n1 <= 1 or (_wins(c0) and _wins(c1)):
         return L.SOLVE_INVALID
     if _wins(c0) or _wins(c1) or n0 + n1 == SIZE:
         return L.SOLVE_TERMINAL
-    if SIZE - (n0 + n1) > MAX_EMPTIES:
+    if SIZE - (n0 + n1) > max_empties:
         return L.SOLVE_TOO_DEEP
     return L.SOLVE_SOLVED
 
 
-def solve_host(board, node_budget=None):
+def solve_host(board, node_budget=None, table=None, deep=False):
     """The kernel's answer for one position, computed in plain Python: ``HostAnswer(status, outcome, final_age, value,
-    nodes)``.  `board`: a Board or a ``(color0, color1)`` pair.  outcome / value are None where the status has none."""
+    nodes)``.  `board`: a Board or a ``(color0, color1)`` pair.  outcome / value are None where the status has none.
+
+    deep=True is c4_solve_deep's table-free search (any number of empty squares, never TOO_DEEP).  table: a ``dict``, which
+    implies deep -- the kernel's probe / store / bound logic on ``key -> (kind, score)`` entries; the dict may be shared by
+    any number of calls, the answer does not depend on what it holds, the node count does."""
     c0, c1 = (board.color if isinstance(board, Board) else board)
     c0, c1 = int(c0), int(c1)
     budget = DEFAULT_NODE_BUDGET if node_budget is None else int(node_budget)
-    st = _classify(c0, c1)
+    st = _classify(c0, c1, DEEP_MAX_EMPTIES if deep or table is not None else MAX_EMPTIES)
     if st == L.SOLVE_TERMINAL:
         outcome = 1.0 if _wins(c0) else 0.0 if _wins(c1) else 0.5
         age = bin(c0 | c1).count("1")
@@ -160,7 +216,7 @@ def solve_host(board, node_budget=None):
     occ = c0 | c1
     age = bin(occ).count("1")
     mine, theirs = (c1, c0) if age & 1 else (c0, c1)
-    s = _Search(budget)
+    s = _Search(budget, table)
     if _winning_squares(mine, occ) & (occ + BOTTOM):
         score, nodes = 42 - age, 1
     else:
@@ -212,8 +268,55 @@ def _packed_on_device(boards, device):
     return t.contiguous()
 
 
-def _solve_dev(packed, node_budget=None, nodes_per_launch=None):
-    """c4_solve_dev on a packed cuda tensor: (status int8, outcome int8, final_age int8, nodes int64) device tensors."""
+class Table:
+    """A transposition table in device memory (c4_solve_table_create): ``2 ** log2_entries`` entries of 8 bytes, zero-filled.
+    Pass it to ``solve`` / ``grid_triple`` / ``label`` as ``table=``; any number of calls may share it, and what it holds
+    never changes an answer, only how many nodes the answer costs.  ``clear()`` empties it (for measurements); ``close()``
+    frees it (also on garbage collection and at the end of a ``with`` block)."""
+
+    def __init__(self, log2_entries=24, device=0):
+        import ctypes as C
+        self._h = None
+        h = C.c_void_p()
+        _check(L.load().c4_solve_table_create(int(device), int(log2_entries), C.byref(h)))
+        self._h = h
+        self.log2_entries = int(log2_entries)
+        self.device = int(device)
+
+    @property
+    def entries(self):
+        return 1 << self.log2_entries
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("the table is closed")
+        return self._h
+
+    def clear(self):
+        _check(L.load().c4_solve_table_clear(self.handle, None))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L.load().c4_solve_table_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _solve_dev(packed, node_budget=None, nodes_per_launch=None, table=None, deep=False):
+    """c4_solve_dev -- or, with `deep` or a `table`, c4_solve_deep_dev -- on a packed cuda tensor: (status int8, outcome int8,
+    final_age int8, nodes int64, table_hits int64) device tensors."""
     import ctypes as C
     import torch
     n = int(packed.shape[0])
@@ -222,14 +325,20 @@ def _solve_dev(packed, node_budget=None, nodes_per_launch=None):
     outcome = torch.empty(n, dtype=torch.int8, device=dev)
     age = torch.empty(n, dtype=torch.int8, device=dev)
     nodes = torch.empty(n, dtype=torch.int64, device=dev)
+    hits = torch.zeros(n, dtype=torch.int64, device=dev)
     if n:
         idx = dev.index if dev.index is not None else torch.cuda.current_device()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-            _check(L.load().c4_solve_dev(idx, C.c_void_p(stream), ptr(packed), n, int(node_budget or 0), int(nodes_per_launch or 0),
-                                         ptr(status), ptr(outcome), ptr(age), ptr(nodes)))
-    return status, outcome, age, nodes
+            if deep or table is not None:
+                _check(L.load().c4_solve_deep_dev(idx, C.c_void_p(stream), table.handle if table is not None else None, ptr(packed), n,
+                                                  int(node_budget or 0), int(nodes_per_launch or 0), ptr(status), ptr(outcome),
+                                                  ptr(age), ptr(nodes), ptr(hits)))
+            else:
+                _check(L.load().c4_solve_dev(idx, C.c_void_p(stream), ptr(packed), n, int(node_budget or 0),
+                                             int(nodes_per_launch or 0), ptr(status), ptr(outcome), ptr(age), ptr(nodes)))
+    return status, outcome, age, nodes, hits
 
 
 def _children_dev(packed):
@@ -249,16 +358,173 @@ def _children_dev(packed):
     return children, legal
 
 
-def _finish(status, outcome, age, nodes):
+def _finish(status, outcome, age, nodes, hits=None):
     status = np.asarray(status, dtype=np.int8)
     age = np.asarray(age, dtype=np.int8)
     known = np.asarray(outcome) >= 0
     out = np.where(known, np.asarray(outcome, dtype=np.float64) * 0.5, np.nan)
     value = np.where(known, value_from_answer(np.where(known, out, 0.0), np.where(known, age, 0)), np.nan)
-    return Solved(status, out, age, value, np.asarray(nodes, dtype=np.int64))
+    nodes = np.asarray(nodes, dtype=np.int64)
+    return Solved(status, out, age, value, nodes, np.zeros_like(nodes) if hits is None else np.asarray(hits, dtype=np.int64))
 
 
-def solve(boards, node_budget=None, nodes_per_launch=None, device=0):
+# -- the split: one hard position over many lanes -------------------------------------------------------------------------
+def _mirror_bits(x):
+    """The left-right mirror image of uint64 bitboards (any shape)."""
+    out = np.zeros_like(x)
+    for c in range(WIDTH):
+        out |= ((x >> np.uint64(H1 * c)) & np.uint64((1 << H1) - 1)) << np.uint64(H1 * (WIDTH - 1 - c))
+    return out
+
+
+def _canonical(rows):
+    """uint64 [m, 2] rows, each replaced by the smaller of itself and its mirror image (by color0, then color1): the value
+    of a position is its mirror image's, so the two are solved once."""
+    m = _mirror_bits(rows)
+    swap = (m[:, 0] < rows[:, 0]) | ((m[:, 0] == rows[:, 0]) & (m[:, 1] < rows[:, 1]))
+    return np.where(swap[:, None], m, rows)
+
+
+def _unique_rows(rows):
+    """(unique uint64 [u, 2], inverse int64 [m]) of uint64 [m, 2]."""
+    if len(rows) == 0:
+        return rows.reshape(0, 2), np.zeros(0, dtype=np.int64)
+    uniq, inv = np.unique(rows, axis=0, return_inverse=True)
+    return uniq, np.asarray(inv, dtype=np.int64).reshape(-1)
+
+
+def _abs_score(outcome_code, age):
+    """The integer score from o's side (43 - age, age - 43, 0) of answers given as C4_RESULT_* and final age."""
+    outcome_code = np.asarray(outcome_code, dtype=np.int64)
+    age = np.asarray(age, dtype=np.int64)
+    return np.where(outcome_code == L.RESULT_OWIN, 43 - age, np.where(outcome_code == L.RESULT_XWIN, age - 43, 0))
+
+
+def _fold_level(rows, link, child_score, child_known):
+    """One ply of the fold (the rule of grid_search.py:21-32 on the integer score): for each open row of `rows` (uint64
+    [m, 2]) the max (o to move) or min (x to move) of its children's scores; link int64 [m, 7] = the child's index or -1.
+    Returns (score int64 [m], known bool [m]): known where every child is."""
+    has = link >= 0
+    at = np.where(has, link, 0)
+    s = child_score[at] if len(child_score) else np.zeros(link.shape, dtype=np.int64)
+    k = child_known[at] if len(child_known) else np.zeros(link.shape, dtype=bool)
+    ages = np.array([bin(int(a | b)).count("1") for a, b in rows], dtype=np.int64)
+    o_moves = (ages & 1) == 0
+    best_o = np.where(has, s, -99).max(axis=1) if link.shape[0] else np.zeros(0, dtype=np.int64)
+    best_x = np.where(has, s, 99).min(axis=1) if link.shape[0] else np.zeros(0, dtype=np.int64)
+    return np.where(o_moves, best_o, best_x), (k | ~has).all(axis=1)
+
+
+def _leaf_pairs(link, p_row, p_leaf, n_next):
+    """(row, leaf) pairs of a level from its links and the next level's pairs (sorted by row): each row's distinct leaves."""
+    r, c = np.nonzero(link >= 0)
+    ch = link[r, c]
+    start = np.searchsorted(p_row, np.arange(n_next))
+    count = np.bincount(p_row, minlength=n_next)
+    reps = count[ch]
+    offs = np.arange(int(reps.sum())) - np.repeat(np.cumsum(reps) - reps, reps)
+    pairs = np.stack([np.repeat(r, reps), p_leaf[np.repeat(start[ch], reps) + offs]], axis=1)
+    pairs = np.unique(pairs, axis=0) if len(pairs) else pairs.reshape(0, 2)
+    return pairs[:, 0], pairs[:, 1]
+
+
+def _fold_split(levels, links, leaf, own):
+    """The host half of ``split_plies``.  levels[j]: the distinct positions j plies below the rows (uint64 [n_j, 2]);
+    links[j]: int64 [n_j, 7], the index in levels[j + 1] of the child in each column, -1 where there is none; leaf: the
+    answers (status, outcome code, final age, nodes, hits arrays) of levels[-1]; own[j]: the same for levels[j], read only
+    where a row has no child at all (a finished or invalid position answers for itself).  Returns the answers of levels[0]:
+    a row with children is SOLVED with the folded score if every child has an answer, else UNKNOWN; its nodes and hits are
+    the sums over its distinct leaves."""
+    status, outcome, age, nodes, hits = (np.asarray(a) for a in leaf)
+    score = _abs_score(outcome, age)
+    known = (status == L.SOLVE_SOLVED) | (status == L.SOLVE_TERMINAL)
+    n_leaf = len(status)
+    p_row, p_leaf = np.arange(n_leaf), np.arange(n_leaf)
+    leaf_nodes, leaf_hits = nodes.astype(np.int64), hits.astype(np.int64)
+    for j in range(len(links) - 1, -1, -1):
+        link = links[j]
+        o_status, o_outcome, o_age = (np.asarray(a) for a in own[j][:3])
+        is_open = (link >= 0).any(axis=1)
+        f_score, f_known = _fold_level(levels[j], link, score, known)
+        score = np.where(is_open, f_score, _abs_score(o_outcome, o_age))
+        known = np.where(is_open, f_known, (o_status == L.SOLVE_SOLVED) | (o_status == L.SOLVE_TERMINAL))
+        status = np.where(is_open, np.where(f_known, L.SOLVE_SOLVED, L.SOLVE_UNKNOWN), o_status).astype(np.int8)
+        p_row, p_leaf = _leaf_pairs(link, p_row, p_leaf, len(levels[j + 1]))
+    n = len(levels[0])
+    answered = known & (status != L.SOLVE_INVALID)
+    out_code = np.where(answered, np.where(score > 0, L.RESULT_OWIN, np.where(score < 0, L.RESULT_XWIN, L.RESULT_DRAW)), -1).astype(np.int8)
+    out_age = np.where(answered, np.where(score != 0, 43 - np.abs(score), SIZE), -1).astype(np.int8)
+    if links:
+        out_nodes = np.bincount(p_row, weights=leaf_nodes[p_leaf], minlength=n).astype(np.int64)
+        out_hits = np.bincount(p_row, weights=leaf_hits[p_leaf], minlength=n).astype(np.int64)
+    else:
+        out_nodes, out_hits = leaf_nodes, leaf_hits
+    return status, out_code, out_age, out_nodes, out_hits
+
+
+def _children_host(rows):
+    """c4_solve_children_dev in Python: (children uint64 [m, 7, 2], legal bool [m, 7]) of uint64 [m, 2] rows."""
+    children = np.zeros((len(rows), WIDTH, 2), dtype=np.uint64)
+    legal = np.zeros((len(rows), WIDTH), dtype=bool)
+    for i, (c0, c1) in enumerate(rows):
+        c0, c1 = int(c0), int(c1)
+        if _classify(c0, c1, DEEP_MAX_EMPTIES) != L.SOLVE_SOLVED:
+            continue
+        occ = c0 | c1
+        o_moves = bin(occ).count("1") % 2 == 0
+        for c in range(WIDTH):
+            bit = (occ + BOTTOM) & (_COL << (H1 * c))
+            if bit:
+                children[i, c] = (c0 | bit, c1) if o_moves else (c0, c1 | bit)
+                legal[i, c] = True
+    return children, legal
+
+
+def _split_levels(rows, split_plies, children_of):
+    """The positions 0..split_plies plies below uint64 [n, 2] `rows`, each level's distinct ones with mirror images merged
+    below the rows themselves: (levels, links, childless, inverse) -- see _fold_split; childless[j]: the rows of levels[j]
+    without a child; levels[0][inverse] = rows.  children_of: _children_host, or c4_solve_children_dev's wrapper."""
+    level, inverse = _unique_rows(rows)
+    levels, links, childless = [level], [], []
+    for _ in range(split_plies):
+        ch, lg = children_of(levels[-1])
+        nxt, inv = _unique_rows(_canonical(ch[lg]))
+        link = np.full(lg.shape, -1, dtype=np.int64)
+        link[lg] = inv
+        levels.append(nxt)
+        links.append(link)
+        childless.append(~lg.any(axis=1))
+    return levels, links, childless, inverse
+
+
+def _solve_split(packed, split_plies, node_budget, nodes_per_launch, table):
+    import torch
+    dev = packed.device
+
+    def children_of(rows):
+        children, legal = _children_dev(torch.from_numpy(np.ascontiguousarray(rows).view(np.int64)).to(dev).contiguous())
+        return children.cpu().numpy().view(np.uint64).reshape(-1, WIDTH, 2), legal.cpu().numpy() != 0
+
+    levels, links, childless, inv0 = _split_levels(packed.cpu().numpy().view(np.uint64).reshape(-1, 2), split_plies, children_of)
+    # one batch: the last level, and above it the rows without children (they answer for themselves and cost no node)
+    parts = [lv[cl] for lv, cl in zip(levels, childless)] + [levels[-1]]
+    batch = torch.from_numpy(np.ascontiguousarray(np.concatenate(parts)).view(np.int64)).to(dev).contiguous()
+    res = [t.cpu().numpy() for t in _solve_dev(batch, node_budget, nodes_per_launch, table, deep=True)]
+    own, at = [], 0
+    for lv, cl in zip(levels, childless):
+        m = int(cl.sum())
+        filled = []
+        for a in res[:3]:
+            full = np.full(len(lv), -1, dtype=a.dtype)
+            full[cl] = a[at:at + m]
+            filled.append(full)
+        own.append(filled)
+        at += m
+    status, outcome, age, nodes, hits = _fold_split(levels, links, [a[at:] for a in res], own)
+    return _finish(status[inv0], outcome[inv0], age[inv0], nodes[inv0], hits[inv0])
+
+
+def solve(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, deep=False, split_plies=0):
     """Solve every row on the GPU.  `boards`: a sequence of Boards (host arrays through c4_solve) or a packed int64 [n, 2]
     tensor (c4_solve_dev; a CPU tensor is moved to cuda:`device`).  Returns ``Solved`` of NumPy arrays:
 
@@ -267,32 +533,57 @@ def solve(boards, node_budget=None, nodes_per_launch=None, device=0):
       final_age  int8, the age at which best play ends the game; -1 where unknown
       value      float64, what ``GridSearch(plies=empties)`` computes for the node (grid_search.py:43-71); NaN where unknown
       nodes      int64, positions the search entered
+      table_hits int64, table probes that returned a stored score or narrowed the window (zeros without a table)
 
     node_budget: most nodes of one row, beyond it the row is UNKNOWN (default 2^26); nodes_per_launch: the quota of one
-    kernel launch (default 2^14) -- it changes neither answers nor node counts."""
+    kernel launch (default 2^14) -- it changes neither answers nor, without a table, node counts.
+
+    deep=True: c4_solve_deep's search, which reaches every position (no TOO_DEEP); table-free it enters the nodes the
+    default search enters.  table: a ``Table`` (implies deep, and the table's device) shared by all rows and by every other
+    call it is passed to; the answers stay exact and the same, the node counts fall and are no longer deterministic.
+    split_plies=k (implies deep): every row is expanded k plies (c4_solve_children_dev), the distinct descendants -- mirror
+    images merged -- are solved as rows of one batch, so one hard position occupies many lanes and they share the table,
+    and the answers are folded back by max / min over the integer score; a row is UNKNOWN if any of its descendants is, and
+    its nodes and table_hits are the sums over its distinct descendants (so node_budget bounds each descendant)."""
+    deep = bool(deep or table is not None or split_plies)
+    if table is not None:
+        device = table.device
+    if split_plies:
+        if not 0 < int(split_plies) <= 8:
+            raise ValueError("split_plies must be 0..8")
+        if not _is_tensor(boards) and len(boards) == 0:
+            return _finish(*(np.zeros(0, dtype=np.int8),) * 3, np.zeros(0, dtype=np.int64))
+        return _solve_split(_packed_on_device(boards, device), int(split_plies), node_budget, nodes_per_launch, table)
     if _is_tensor(boards):
-        st, out, age, nodes = _solve_dev(_packed_on_device(boards, device), node_budget, nodes_per_launch)
-        return _finish(st.cpu().numpy(), out.cpu().numpy(), age.cpu().numpy(), nodes.cpu().numpy())
+        res = _solve_dev(_packed_on_device(boards, device), node_budget, nodes_per_launch, table, deep)
+        return _finish(*(t.cpu().numpy() for t in res))
     import ctypes as C
     n = len(boards)
     status = np.zeros(n, dtype=np.int8)
     outcome = np.zeros(n, dtype=np.int8)
     age = np.zeros(n, dtype=np.int8)
     nodes = np.zeros(n, dtype=np.int64)
+    hits = np.zeros(n, dtype=np.int64)
     if n:
         c0, c1 = _bits(boards)
         i8 = C.POINTER(C.c_int8)
-        _check(L.load().c4_solve(device, c0.ctypes.data_as(L._u64p), c1.ctypes.data_as(L._u64p), n, int(node_budget or 0),
-                                 int(nodes_per_launch or 0), status.ctypes.data_as(i8), outcome.ctypes.data_as(i8),
-                                 age.ctypes.data_as(i8), nodes.ctypes.data_as(L._i64p)))
-    return _finish(status, outcome, age, nodes)
+        if deep:
+            _check(L.load().c4_solve_deep(device, table.handle if table is not None else None, c0.ctypes.data_as(L._u64p),
+                                          c1.ctypes.data_as(L._u64p), n, int(node_budget or 0), int(nodes_per_launch or 0),
+                                          status.ctypes.data_as(i8), outcome.ctypes.data_as(i8), age.ctypes.data_as(i8),
+                                          nodes.ctypes.data_as(L._i64p), hits.ctypes.data_as(L._i64p)))
+        else:
+            _check(L.load().c4_solve(device, c0.ctypes.data_as(L._u64p), c1.ctypes.data_as(L._u64p), n, int(node_budget or 0),
+                                     int(nodes_per_launch or 0), status.ctypes.data_as(i8), outcome.ctypes.data_as(i8),
+                                     age.ctypes.data_as(i8), nodes.ctypes.data_as(L._i64p)))
+    return _finish(status, outcome, age, nodes, hits)
 
 
 # -- grid_search's triple --------------------------------------------------------------------------------------------------
-def _check_root(board):
+def _check_root(board, deep=False):
     if board.result is not None:
         raise ValueError("cannot search a finished position")
-    if SIZE - board.age > MAX_EMPTIES:
+    if not deep and SIZE - board.age > MAX_EMPTIES:
         raise ValueError("grid_triple solves positions with at most %d empty squares; this one has %d" % (
             MAX_EMPTIES, SIZE - board.age))
 
@@ -323,21 +614,23 @@ def _child_boards(board):
     return out
 
 
-def grid_triple(boards: Sequence[Board], device=0, node_budget=None, nodes_per_launch=None, host=False):
+def grid_triple(boards: Sequence[Board], device=0, node_budget=None, nodes_per_launch=None, host=False, table=None, split_plies=0):
     """``[(move, value, tree)]``, what ``grid_search.grid_search(boards, plies=empties, evaluate_centre)`` returns for
     undecided boards with at most MAX_EMPTIES empty squares: GridTree's root and children with their ``absolute_value``s,
     Tree.best_move's tie to the higher column.  Every child of every root is solved as a row of its own in one batch;
-    host=True solves them with ``solve_host`` instead (no GPU).  A child the budget leaves UNKNOWN raises RuntimeError."""
+    host=True solves them with ``solve_host`` instead (no GPU).  A child the budget leaves UNKNOWN raises RuntimeError.
+    table (a ``Table``; with host=True a dict) and split_plies are ``solve``'s: with either, boards of any depth are taken."""
+    deep = table is not None or bool(split_plies)
     for b in boards:
-        _check_root(b)
+        _check_root(b, deep)
     kids = [_child_boards(b) for b in boards]
     flat = [cb for ks in kids for _, cb in ks if cb.result is None]
     if host:
-        answers = [solve_host(cb, node_budget) for cb in flat]
+        answers = [solve_host(cb, node_budget, table=table, deep=deep) for cb in flat]
         status = [a.status for a in answers]
         values = [a.value for a in answers]
     elif flat:
-        res = solve(flat, node_budget, nodes_per_launch, device)
+        res = solve(flat, node_budget, nodes_per_launch, device, table=table, split_plies=split_plies)
         status, values = res.status.tolist(), res.value.tolist()
     else:
         status, values = [], []
@@ -367,14 +660,17 @@ def prior_from_children(outcome, child_outcomes, legal):
     return np.where(s > 0, p / np.maximum(s, 1.0), 0.0)
 
 
-def label(boards, node_budget=None, nodes_per_launch=None, device=0):
+def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, split_plies=0):
     """Label positions with their exact outcome: returns ``(LabelledSet, report)``.
 
     Each distinct position is solved once, together with its up-to-seven children (c4_solve_children_dev lists them) in one
     batch.  value = the outcome (0.0 / 0.5 / 1.0); prior = ``prior_from_children``.  Rows that are unknown, too deep,
     terminal or invalid are dropped, as is a row one of whose children stayed unknown (counted as unknown); the kept rows
     stay in the order of their first occurrence.  report: positions, distinct, labelled, the count per status
-    (STATUS_NAMES), nodes (parents and children) and seconds."""
+    (STATUS_NAMES), nodes (parents and children) and seconds.
+
+    table (a ``Table``) and split_plies are ``solve``'s; with either, positions of any depth are labelled (none is too deep)
+    and only the children that exist are solved.  The report then also says table_log2_entries and table_hits."""
     import torch
     from .stats import LabelledSet
     t0 = time.perf_counter()
@@ -387,11 +683,26 @@ def label(boards, node_budget=None, nodes_per_launch=None, device=0):
         uniq = uniq[torch.argsort(first)].contiguous()
         n = int(uniq.shape[0])
         children, legal = _children_dev(uniq)
-        batch = torch.cat([uniq, children.reshape(n * WIDTH, 2)]).contiguous()
-        status, outcome, _, nodes = _solve_dev(batch, node_budget, nodes_per_launch)
-        p_status, p_out = status[:n], outcome[:n]
-        c_status, c_out = status[n:].reshape(n, WIDTH), outcome[n:].reshape(n, WIDTH)
         is_legal = legal != 0
+        total_hits = 0
+        if table is None and not split_plies:
+            batch = torch.cat([uniq, children.reshape(n * WIDTH, 2)]).contiguous()
+            status, outcome, _, nodes, _ = _solve_dev(batch, node_budget, nodes_per_launch)
+            p_status, p_out = status[:n], outcome[:n]
+            c_status, c_out = status[n:].reshape(n, WIDTH), outcome[n:].reshape(n, WIDTH)
+        else:
+            # the deep search reaches the empty board, so the zero rows of the illegal slots stay out of the batch
+            res = solve(torch.cat([uniq, children[is_legal]]).contiguous(), node_budget, nodes_per_launch, device, table=table,
+                        split_plies=split_plies)
+            status = torch.from_numpy(res.status).to(packed.device)
+            outcome = torch.from_numpy(np.where(np.isnan(res.outcome), -1, res.outcome * 2).astype(np.int8)).to(packed.device)
+            nodes = torch.from_numpy(res.nodes)
+            total_hits = int(res.table_hits.sum())
+            p_status, p_out = status[:n], outcome[:n]
+            c_status = torch.full((n, WIDTH), L.SOLVE_INVALID, dtype=torch.int8, device=packed.device)
+            c_out = torch.full((n, WIDTH), -1, dtype=torch.int8, device=packed.device)
+            c_status[is_legal] = status[n:]
+            c_out[is_legal] = outcome[n:]
         child_known = (~is_legal | (c_status == L.SOLVE_SOLVED) | (c_status == L.SOLVE_TERMINAL)).all(dim=1)
         keep = (p_status == L.SOLVE_SOLVED) & child_known
         p_status = torch.where((p_status == L.SOLVE_SOLVED) & ~child_known, torch.full_like(p_status, L.SOLVE_UNKNOWN), p_status)
@@ -402,6 +713,9 @@ def label(boards, node_budget=None, nodes_per_launch=None, device=0):
         # illegal child slots are zero rows (the empty board: too deep, never searched, 0 nodes)
         total_nodes = int(nodes.sum().item())
     report = {"positions": n_in, "distinct": n, "labelled": len(ls), "nodes": total_nodes}
+    if table is not None or split_plies:
+        report.update(table_log2_entries=table.log2_entries if table is not None else None, table_hits=total_hits,
+                      split_plies=int(split_plies))
     report.update({name: int(counts[code]) for code, name in STATUS_NAMES.items()})
     report["seconds"] = time.perf_counter() - t0
     return ls, report

@@ -670,6 +670,36 @@ int c4_solve(int device, const uint64_t *color0, const uint64_t *color1, int64_t
 int c4_solve_children_dev(int device, void *hip_stream, const int64_t *boards_dev, int64_t n, int64_t *children_dev, int8_t *legal_dev);
 const char *c4_solve_last_error(void);
 
+/* -- positions of any depth: the same search with 42 plies of stack and a shared transposition table (c4_solve.hip) ------ */
+/* c4_solve_deep_dev / c4_solve_deep answer like c4_solve_dev / c4_solve for positions with up to
+ * C4_SOLVE_DEEP_MAX_EMPTIES = 42 empty squares -- every position: they never answer C4_SOLVE_TOO_DEEP.  Statuses, nodes,
+ * node_budget and nodes_per_launch mean what they mean above.
+ * table: a handle from c4_solve_table_create, or NULL.  With NULL this is the table-free search: node counts are
+ * deterministic and the ones c4_solve_dev has where both answer.  With a table, every lane of every launch of every call
+ * probes and stores in the same 2^log2_entries entries of device memory.  An entry is one aligned 64-bit word = the
+ * position's full 49-bit key (mover's stones + occupied squares + bottom row: injective), a 7-bit score and whether that
+ * score is a lower bound, an upper bound or exact; it is read and written by one 64-bit access, so a reader sees a whole
+ * entry, and a hit is a hit on the position itself, never on a hash.  The score is the mover's and depends on the position
+ * alone, so an entry holds for every row, launch and call, and the table never has to be cleared for correctness.
+ * Answers (status other than UNKNOWN, outcome, final_age) are exact and do not depend on the table's size or contents,
+ * on nodes_per_launch or on what else is in the batch.  NODE COUNTS WITH A TABLE ARE NOT DETERMINISTIC: they depend on
+ * what other lanes stored first, and so does which rows a tight node_budget leaves UNKNOWN.  Replacement: always.
+ * table_hits_dev / table_hits: int64 [n] or NULL -- per row, the probes that returned the stored score or narrowed the
+ * window (0 without a table).
+ * c4_solve_table_create: log2_entries in 10..30 (8 bytes an entry), else C4_EINVAL; zero-filled, on `device`; the table
+ * must be used on the device it was created on (else C4_EINVAL).  c4_solve_table_clear zero-fills on hip_stream and waits for it (a
+ * matter of measurement, not of correctness).  Two calls that share a table may run concurrently. */
+#define C4_SOLVE_DEEP_MAX_EMPTIES  42
+typedef struct c4_solve_table c4_solve_table;
+int c4_solve_table_create(int device, int log2_entries, c4_solve_table **out);
+int c4_solve_table_destroy(c4_solve_table *table);
+int c4_solve_table_clear(c4_solve_table *table, void *hip_stream);
+int c4_solve_deep_dev(int device, void *hip_stream, c4_solve_table *table, const int64_t *boards_dev, int64_t n, int64_t node_budget,
+                      int64_t nodes_per_launch, int8_t *status_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev,
+                      int64_t *table_hits_dev);
+int c4_solve_deep(int device, c4_solve_table *table, const uint64_t *color0, const uint64_t *color1, int64_t n, int64_t node_budget,
+                  int64_t nodes_per_launch, int8_t *status, int8_t *outcome, int8_t *final_age, int64_t *nodes, int64_t *table_hits);
+
 int c4_abi_version(void);
 
 #ifdef __cplusplus

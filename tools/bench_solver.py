@@ -7,7 +7,11 @@
   kernel_rate        65,536 positions with 20 empty squares (1,024 waves) in one solve(): nodes per second of wall time
   solve_host         the Python mirror's nodes per second on 64 rows of tests/golden/solver_deep.npz, for scale
   generation         4,096 self-play games of a random 32-filter net at 100 simulations; every distinct position with
-                     age >= 18 labelled (solver.label): seconds, share unknown, label histogram"""
+                     age >= 18 labelled (solver.label): seconds, share unknown, label histogram
+
+    python tools/bench_solver.py --table [--budget-log2 20] [--out profiles/solver_table.json]
+
+  the deep search, its transposition table and the split instead: see bench_table below"""
 import argparse
 import json
 import os
@@ -25,9 +29,14 @@ from connect4_amd import _lib as L  # noqa: E402
 from connect4_amd.solver import label, random_playout, solve, solve_host  # noqa: E402
 
 ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "solver.json"))
+ap.add_argument("--out", default=None)
+ap.add_argument("--table", action="store_true", help="measure the deep search and its transposition table instead (below)")
+ap.add_argument("--budget-log2", type=int, default=20, help="--table: the node budget of one row in the budgeted parts")
 args = ap.parse_args()
-out = {"command": "python tools/bench_solver.py --out profiles/solver.json", "device": torch.cuda.get_device_name(0)}
+if args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "solver_table.json" if args.table else "solver.json")
+out = {"command": "python tools/bench_solver.py%s --out profiles/%s" % (" --table" if args.table else "", os.path.basename(args.out)),
+       "device": torch.cuda.get_device_name(0)}
 
 
 def dump():
@@ -38,6 +47,101 @@ def dump():
 def packed(boards):
     return torch.from_numpy(np.array([b.color for b in boards], dtype=np.uint64).reshape(len(boards), 2).view(np.int64)).cuda()
 
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    return r, time.perf_counter() - t0
+
+
+def summary(r, dt):
+    known = (r.status == L.SOLVE_SOLVED) | (r.status == L.SOLVE_TERMINAL)
+    return {"positions": int(len(r.status)), "share_solved": float(known.mean()), "unknown": int((r.status == L.SOLVE_UNKNOWN).sum()),
+            "mean_nodes": float(r.nodes.mean()), "max_nodes": int(r.nodes.max()), "nodes": int(r.nodes.sum()),
+            "table_hits": int(r.table_hits.sum()), "seconds": dt}
+
+
+def bench_table():
+    """--table: writes profiles/solver_table.json (nothing is gated on these figures)
+
+      late          the 512 positions per depth of profiles/solver.json at 20..24 empty squares (same seed, same draws) with
+                    Table(24), cleared per depth, default budget; the table-free baseline is that file's
+      deep          64 random playouts per depth 25..35 under 2^budget-log2 nodes a row, tables of 2^20 / 2^24 / 2^27
+                    entries (cleared per depth) and table-free: share solved, nodes, hits, seconds
+      split         64 positions with 30 empty squares, split_plies 0..3, Table(24) cleared per run, the same budget per
+                    descendant
+      seven_ply     4,096 random 7-ply positions through label(), Table(27), split_plies 0 and 1: seconds, share unknown
+      empty_board   the empty board at split_plies 4, 2^22 nodes a descendant: its answer (published: o wins with the 41st
+                    stone) or UNKNOWN with the nodes spent"""
+    from connect4_amd.solver import Table, random_openings
+    budget = 1 << args.budget_log2
+    out["budget"] = budget
+    rng = np.random.RandomState(2024)
+    solve(packed([random_playout(rng, 30)]))        # warm; the draw keeps the sequence of profiles/solver.json
+    base = json.load(open(os.path.join(ROOT, "profiles", "solver.json")))["nodes_per_empties"]
+    late = {}
+    with Table(24) as table:
+        for e in range(12, 25):
+            boards = [random_playout(rng, 42 - e) for _ in range(512)]
+            if e < 20:
+                continue
+            table.clear()
+            r, dt = timed(lambda: solve(packed(boards), table=table))
+            late[e] = dict(summary(r, dt), table_free_mean_nodes=base[str(e)]["mean_nodes"], table_free_max_nodes=base[str(e)]["max_nodes"],
+                           table_free_seconds=base[str(e)]["seconds"])
+            print(e, late[e], flush=True)
+    out["late"] = late
+    dump()
+
+    rng = np.random.RandomState(2025)
+    samples = {e: packed([random_playout(rng, 42 - e) for _ in range(64)]) for e in range(25, 36)}
+    deep = {}
+    for log2 in (None, 20, 24, 27):
+        table = Table(log2) if log2 is not None else None
+        for e, t in samples.items():
+            if table is not None:
+                table.clear()
+            r, dt = timed(lambda: solve(t, node_budget=budget, table=table, deep=True))
+            deep.setdefault(e, {})["table_free" if log2 is None else "2^%d" % log2] = summary(r, dt)
+            print(e, log2, deep[e]["table_free" if log2 is None else "2^%d" % log2], flush=True)
+        if table is not None:
+            table.close()
+    out["deep"] = deep
+    dump()
+
+    split = {}
+    with Table(24) as table:
+        for k in range(4):
+            table.clear()
+            r, dt = timed(lambda: solve(samples[30], node_budget=budget, table=table, split_plies=k))
+            split[k] = summary(r, dt)
+            print("split", k, split[k], flush=True)
+    out["split"] = split
+    dump()
+
+    openings = packed(random_openings(7, 4096, seed=7))
+    seven = {}
+    with Table(27) as table:
+        for k in (0, 1):
+            table.clear()
+            (ls, report), dt = timed(lambda: label(openings, node_budget=budget, table=table, split_plies=k))
+            seven[k] = {"report": report, "share_unknown": report["unknown"] / max(1, report["distinct"]), "seconds": dt}
+            print("7-ply", k, seven[k], flush=True)
+    out["seven_ply"] = seven
+    dump()
+
+    with Table(27) as table:
+        r, dt = timed(lambda: solve(torch.zeros((1, 2), dtype=torch.int64).cuda(), node_budget=1 << 22, table=table, split_plies=4))
+    out["empty_board"] = dict(summary(r, dt), status=int(r.status[0]), outcome=None if np.isnan(r.outcome[0]) else float(r.outcome[0]),
+                              final_age=int(r.final_age[0]), split_plies=4, budget_per_descendant=1 << 22)
+    print("empty board", out["empty_board"], flush=True)
+    dump()
+
+
+if args.table:
+    bench_table()
+    sys.exit(0)
 
 # 1. nodes per empty-square count: 512 seeded random playouts each, default budget
 rng = np.random.RandomState(2024)

@@ -10,11 +10,21 @@ with fewer than --min-age stones are dropped (the solver reaches positions with 
 --max-positions keeps a random subset (--seed).  The rest is solved exactly together with its children
 (connect4_amd/solver.py: label -- value = the game-theoretic outcome, prior = uniform over the moves that keep it) and
 saved in the format of the reference's Connect4Dataset.save, which LabelledSet.load, tools/score_net.py and
-run_generations(test_sets={"endgame": "endgame.pth"}) read.  The labeller's report is printed."""
+run_generations(test_sets={"endgame": "endgame.pth"}) read.  The labeller's report is printed.
+
+    python tools/make_test_set.py --openings 7 --count 4096 --seed 0 --table-log2 27 --split-plies 2 -o 7ply.pth
+
+--openings PLIES draws --count distinct undecided positions after PLIES uniformly random legal moves (--seed) instead of
+reading self-play data: the reference's make_random_ips (scripts/generate_7ply.py), labelled by the same rule.  Positions
+with more than 24 empty squares need --table-log2 N (a shared transposition table of 2^N entries; solver.Table) and may
+use --split-plies K (solver.solve); --node-budget bounds the nodes of one row.  Positions the budget leaves unknown are
+dropped and counted."""
 import argparse
 import json
 import os
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -34,20 +44,37 @@ def data_files(path):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("sources", nargs="+", metavar="SAVE_DIR_OR_DATA_PTH")
+    ap.add_argument("sources", nargs="*", metavar="SAVE_DIR_OR_DATA_PTH")
+    ap.add_argument("--openings", type=int, default=None, metavar="PLIES", help="random positions after PLIES moves, not self-play data")
+    ap.add_argument("--count", type=int, default=4096, help="with --openings: how many distinct positions")
+    ap.add_argument("--table-log2", type=int, default=None, metavar="N", help="solve with a transposition table of 2^N entries")
+    ap.add_argument("--split-plies", type=int, default=0, metavar="K")
+    ap.add_argument("--node-budget", type=int, default=None)
     ap.add_argument("--min-age", type=int, default=18)
     ap.add_argument("--max-positions", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-o", "--output", required=True)
     a = ap.parse_args(argv)
+    if (a.openings is None) == (not a.sources):
+        ap.error("give either sources or --openings")
+    if a.openings is not None and not 0 <= a.openings <= 41:
+        ap.error("--openings takes 0..41 plies")
+    if a.openings is not None and 42 - a.openings > 24 and a.table_log2 is None and not a.split_plies:
+        ap.error("positions with more than 24 empty squares need --table-log2 (or --split-plies)")
     import torch
     import __graft_entry__ as entry
     entry.build()
     from connect4_amd import engine
-    from connect4_amd.solver import label
+    from connect4_amd.solver import Table, label, random_openings
     dev = torch.device("cuda", a.device)
+    table = Table(a.table_log2, a.device) if a.table_log2 is not None else None
     parts, rows = [], 0
+    if a.openings is not None:
+        boards = random_openings(a.openings, a.count, a.seed)
+        rows = len(boards)
+        bits = np.array([b.color for b in boards], dtype=np.uint64).reshape(rows, 2)
+        parts.append(torch.from_numpy(bits.view(np.int64)).to(dev))
     for src in a.sources:
         for path in data_files(src):
             planes = torch.load(path, map_location="cpu", weights_only=True)["boards"]
@@ -67,9 +94,11 @@ def main(argv=None):
         g = torch.Generator().manual_seed(a.seed)
         pick = torch.sort(torch.randperm(late, generator=g)[:a.max_positions]).values
         boards = boards[pick.to(dev)].contiguous()
-    ls, report = label(boards, device=a.device)
+    ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, split_plies=a.split_plies)
+    if table is not None:
+        table.close()
     ls.save(a.output)
-    report = dict(report, rows_read=rows, distinct_late=late, min_age=a.min_age, output=a.output)
+    report = dict(report, rows_read=rows, distinct_late=late, min_age=a.min_age, output=a.output, openings=a.openings)
     print(json.dumps(report))
     hist = {k: int((ls.values == k).sum().item()) for k in (0.0, 0.5, 1.0)}
     print("%s: %d positions labelled (x wins %d, draws %d, o wins %d); %d unknown, %.2f s, %d nodes" % (
