@@ -14,12 +14,15 @@
 //   * score arithmetic reproduces the reference bit-for-bit: float64 everywhere, or NumPy>=2's
 //     float32 path when the prior is a float32 net output (see ucb_score below); log() comes from a
 //     host-built table so device libm never enters the comparison.  Build with -ffp-contract=off;
-//   * three drivers share tree_step(): c4_step_kernel (one rollout step per launch, evaluator outside),
-//     c4_selfplay_kernel (workgroup-synchronous tree / network phases in one persistent kernel) and
-//     c4_selfplay_wave_kernel (the default: every wave alternates the tree walk of its own slots with
-//     the network on their leaves, no barrier; slot state lives in LDS for the whole launch).
+//   * five kernels share tree_step(): c4_step_kernel (one rollout step per launch, evaluator outside),
+//     c4_selfplay_kernel (workgroup-synchronous tree / network phases in one persistent kernel),
+//     c4_selfplay_wave_kernel (every wave alternates the tree walk of its own slots with the network on
+//     their leaves, no barrier; slot state lives in LDS for the whole launch), c4_match_wave_kernel (the
+//     same with one net per launch: net-vs-net matches) and c4_selfplay_split_kernel (the default: tree
+//     waves and network waves of one workgroup hand leaves and answers over through LDS).
 //
-// No CUDA-compat headers, no dual code paths, no CPU fallback: every entry point needs a HIP device.
+// No CUDA-compat headers, no CPU fallback: every entry point needs a HIP device.  One code path: the only
+// build switches are the diagnostic ones below, both off in the library anyone ships.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <hip/hip_bfloat16.h>
@@ -37,72 +40,12 @@
 #include "c4_board.h"
 #include "c4_net_dev.h"
 
-#ifndef C4_DEADLINE_EVERY
-#define C4_DEADLINE_EVERY 1   // a tree call looks at the clock every this many simulations (power of two; 4 measured no faster)
-#endif
-#ifndef C4_TERMQ
-#define C4_TERMQ 1            // q of a terminal node holds its exact result from creation on
-#endif
 #ifndef C4_FUSED_NET_STAMPS
 #define C4_FUSED_NET_STAMPS 0 // diagnostic build only (-DC4_FUSED_NET_STAMPS=1, tools/wave_stamps.py): stamps of the network pass
                               // inside the fused kernel; the extra pointer costs the production kernel 3 %
 #endif
-#ifndef C4_ASM_PICK
-#define C4_ASM_PICK 1         // butterfly step written out in assembly (compare, select and DPP moves in one block)
-#endif
-#ifndef C4_SPECULATE
-#define C4_SPECULATE 1         // split kernel: a network wave with nothing else to do evaluates the best-prior child of the position it just answered (tuning aid: 0 = off)
-#endif
 #ifndef C4_SPLIT_PHASES
 #define C4_SPLIT_PHASES 0       // diagnostic build only: per-slot cycles per phase of the split kernel's tree walk (tools/split_stamps.py)
-#endif
-#ifndef C4_DIV_NORMAL
-#define C4_DIV_NORMAL 1
-#endif
-#ifndef C4_SCORE_ALL
-#define C4_SCORE_ALL 1          // level loop: all eight lanes score, a select instead of a branch around the division (+1.6 %)
-#endif
-#ifndef C4_PATH_ALL_LANES
-#define C4_PATH_ALL_LANES 1      // the descent's path entries are stored by all eight lanes of the group (same words, same address): no
-                                // exec-mask region per level (+0.5 %; the same for the parent's record in the apply: nothing)
-#endif
-#ifndef C4_PEEL_BACKUP
-#define C4_PEEL_BACKUP 1
-#endif
-#ifndef C4_NO_SUSPEND
-#define C4_NO_SUSPEND 1
-#endif
-#ifndef C4_NET_SANITISES
-#define C4_NET_SANITISES 1
-#endif
-#ifndef C4_WAIT_CLOCK_LAZY
-#define C4_WAIT_CLOCK_LAZY 1
-#endif
-#ifndef C4_SPLIT_PAIRS
-#define C4_SPLIT_PAIRS 1      // split kernel: a network wave takes two waiting requests into one pass (tuning aid: 0 = one position per pass)
-#endif
-#ifndef C4_SORT_SLOTS
-#define C4_SORT_SLOTS 1       // split kernel: at launch start the workgroup's slots are sorted by ply and neighbours in that order share a tree
-                              // wave (games at a similar stage spend their iterations in similar phases: +1.6 % with the fp16 net, +0.3 % with the
-                              // reference-precision net; sorting by simulations done or by the measured leaf depth: nothing); 0 = slot p -> wave p % TW
-#endif
-#ifndef C4_FILLERS
-#define C4_FILLERS (C4_ORIENTED_Q && C4_SCORE_ALL)   // a sibling block's unused records are written too, with q = -inf: they score -inf by arithmetic, the level loop needs no "is this lane a child" logic
-#endif
-#ifndef C4_VGPR_BASES
-#define C4_VGPR_BASES 1
-#endif
-#ifndef C4_ORIENTED_Q
-#define C4_ORIENTED_Q 1      // a record's q is stored from the point of view of the player who chooses AT ITS PARENT: the level loop reads the value it scores
-#endif
-#ifndef C4_COOP_LEGAL
-#define C4_COOP_LEGAL 1      // the legal-move mask of a group's position by one lane per column + a ballot; the prior sum's seven fetches issued together
-#endif
-#ifndef C4_PICK_BPERM
-#define C4_PICK_BPERM 1      // the level loop's argmax: butterfly on the score alone + one fetch of the winner's record through the LDS crossbar
-#endif
-#ifndef C4_EARLY_REQUEST
-#define C4_EARLY_REQUEST 1   // software-pipelined level loop (tuning aid: -DC4_EARLY_REQUEST=0 restores the plain loop)
 #endif
 
 namespace {
@@ -361,34 +304,17 @@ __device__ inline double rng_gamma(uint64_t seed, long long gid, uint32_t ply, u
     return boost * dd;
 }
 
-// tree.py:27-44 + utils.py:33-34: value of a child from `side`'s point of view (branch-free).
+// A record's q is stored from the point of view of the player who chooses AT ITS PARENT: tree.py:27-44's value of a node "for
+// the side to move at its parent" (+ utils.py:33-34) is what the field holds, and the level loop reads the value it scores.
 // terminal: the exact result, not a running mean -- it is what q holds for a terminal node from its creation on
 // (every visit adds that same value, so w / n reproduces it exactly); visited: q = value_sum / visit_count
-// (refreshed by every backup); unknown: 0.0 for either side ("assume lost")
-__device__ __forceinline__ double child_value_for(uint32_t status, uint32_t n, double q, int side)
-{
-    const bool term = status >= ST_XWIN;
-#if C4_TERMQ
-    const double v = q;
-#else
-    const double v = term ? 0.5 * (double)(status - ST_XWIN) : q;
-#endif
-    const double sv = side == 0 ? v : 1.0 - v;
-    return (term || n > 0) ? sv : 0.0;
-}
-
-// C4_ORIENTED_Q: tree.py:27-44's value of a node "for the side to move at its parent" is what a record's q field holds -- the flip
-// 1 - v for an x-to-move parent is done once by whoever writes q (expansion, backup: same operation on the same float64, so the
-// same bits), an unvisited child's q is 0 and a terminal child's its exact result, flipped likewise: the level loop's
-// child_value_for (select by side, select by visited / terminal: eight instructions per level) becomes a plain read.
+// (refreshed by every backup); unknown: 0.0 for either side ("assume lost").
+// The flip 1 - v for an x-to-move parent is done once by whoever writes q (expansion, backup: same operation on the same float64,
+// so the same bits), and a terminal child's exact result is flipped likewise: what would be a select by side and a select by
+// visited / terminal in the level loop (eight instructions per level) is a plain read.
 __device__ __forceinline__ double orient_q(double v, int parent_side)
 {
-#if C4_ORIENTED_Q
     return (parent_side & 1) ? 1.0 - v : v;
-#else
-    (void)parent_side;
-    return v;
-#endif
 }
 
 // mcts.py:147-161 ucb_score.  A = log(..)+pb_c_init and B = sqrt(Np) come from the host table.
@@ -400,11 +326,10 @@ __device__ __forceinline__ double orient_q(double v, int parent_side)
 // division (v_rcp_f64, two Newton steps, one residual correction) without its v_div_scale / v_div_fmas / v_div_fixup
 // instructions, which change something only for denormal, infinite, NaN or huge-ratio operands (a zero numerator
 // comes out as +0 either way).  For 0 <= a < 2^32 and an integer 1 <= b < 2^32 the quotient is bit-identical to a / b
-// (#if C4_DIV_NORMAL == 0 restores the plain division for A/B runs: same games); three dependent instructions less on
-// the level loop's critical chain.
+// (k_debug_div counts mismatches against the plain division); three dependent instructions less on the level loop's
+// critical chain.
 __device__ __forceinline__ double div_normal(double a, double b)
 {
-#if C4_DIV_NORMAL
     double r = __builtin_amdgcn_rcp(b);
     double e = __builtin_fma(-b, r, 1.0);
     r = __builtin_fma(r, e, r);
@@ -413,9 +338,6 @@ __device__ __forceinline__ double div_normal(double a, double b)
     const double q = a * r;
     const double rem = __builtin_fma(-b, q, a);
     return __builtin_fma(rem, r, q);
-#else
-    return a / b;
-#endif
 }
 
 __device__ __forceinline__ double ucb_score(double A, double B, uint32_t nc, double p, double V, uint32_t pf64)
@@ -433,14 +355,10 @@ __device__ __forceinline__ double ucb_score(double A, double B, uint32_t nc, dou
 // lanes all active.
 __device__ __forceinline__ int legal_mask_group(uint64_t occ)
 {
-#if C4_COOP_LEGAL
     const int lane = (int)(threadIdx.x & (GROUP - 1));
     const bool legal = lane < WIDTH && col_count(occ, lane < WIDTH ? lane : 0) < HEIGHT;
     const unsigned long long b = __builtin_amdgcn_ballot_w64(legal);
     return (int)((b >> (threadIdx.x & 63u & ~(uint32_t)(GROUP - 1))) & 0x7fu);
-#else
-    return legal_mask(occ);
-#endif
 }
 
 // argmax over the group on (score, k); ties -> larger k == higher column (tree.py:11-15).
@@ -479,74 +397,6 @@ struct Pick {      // a candidate child with its record riding along
     uint32_t n, info;
     double w;
 };
-// One butterfly step.  Score and index are exchanged with v_mov_b32_dpp and compared; the record
-// fields that only ride along are selected with v_cndmask_b32_dpp (own value where VCC, else the
-// partner's, permuted inside the select), one instruction per field instead of mov_dpp + cndmask.
-// keep-own = (s > os) | (s == os & k >= ok): ties go to the higher column (tree.py:11-15).
-// DPP hazard: 2 wait states between the VALU write of a source and its DPP read -- s_mov + s_nop.
-#define C4_DPP_SELECT(CTRL)                                                                              \
-    asm volatile("s_mov_b64 vcc, %[m]\n"                                                                 \
-                 "s_nop 0\n"                                                                             \
-                 "v_cndmask_b32_dpp %[n], %[n], %[n], vcc " CTRL " row_mask:0xf bank_mask:0xf\n"         \
-                 "v_cndmask_b32_dpp %[i], %[i], %[i], vcc " CTRL " row_mask:0xf bank_mask:0xf\n"         \
-                 "v_cndmask_b32_dpp %[wl], %[wl], %[wl], vcc " CTRL " row_mask:0xf bank_mask:0xf\n"      \
-                 "v_cndmask_b32_dpp %[wh], %[wh], %[wh], vcc " CTRL " row_mask:0xf bank_mask:0xf\n"      \
-                 : [n] "+v"(n), [i] "+v"(info), [wl] "+v"(wl), [wh] "+v"(wh)                              \
-                 : [m] "s"(m)                                                                             \
-                 : "vcc")
-#if C4_ASM_PICK
-// keep-own = (s > os) | (s == os & own index > partner's index).  In a butterfly over lanes that start with k == lane,
-// the candidates a lane holds at a step all lie on its side of the exchanged bit (step 1: the lane itself; step 2: its
-// pair; step 3: its quad), so "own index > partner's index" is a constant of the lane: the exchanged bit of its lane id.
-// The tie-break therefore needs no index compare and the index itself need not travel through the compares: keep-own =
-// gt | (ge & LANES_WITH_THE_BIT) as wave masks (two v_cmp into SGPR pairs + two scalar ops), to VCC once; the selects of
-// the score and the v_cndmask_b32_dpp selects of the fields that ride along (the index rides in the top bits of n) then
-// all read VCC in one block.
-#define C4_PICK_SELECT(CTRL)                                                                             \
-    asm volatile("s_mov_b64 vcc, %[m]\n"                                                                 \
-                 "s_nop 0\n"                                                                             \
-                 "v_cndmask_b32 %[sl], %[ol], %[sl], vcc\n"                                               \
-                 "v_cndmask_b32 %[sh], %[oh], %[sh], vcc\n"                                               \
-                 "v_cndmask_b32_dpp %[n], %[n], %[n], vcc " CTRL " row_mask:0xf bank_mask:0xf\n"          \
-                 "v_cndmask_b32_dpp %[i], %[i], %[i], vcc " CTRL " row_mask:0xf bank_mask:0xf\n"          \
-                 "v_cndmask_b32_dpp %[wl], %[wl], %[wl], vcc " CTRL " row_mask:0xf bank_mask:0xf\n"       \
-                 "v_cndmask_b32_dpp %[wh], %[wh], %[wh], vcc " CTRL " row_mask:0xf bank_mask:0xf\n"       \
-                 : [sl] "+v"(sl), [sh] "+v"(sh), [n] "+v"(n), [i] "+v"(info), [wl] "+v"(wl), [wh] "+v"(wh) \
-                 : [m] "s"(m), [ol] "v"(ol), [oh] "v"(oh)                                                   \
-                 : "vcc")
-template <int CTRL>
-__device__ __forceinline__ void pick_step(double &s, uint32_t &n, uint32_t &info, uint32_t &wl, uint32_t &wh)
-{
-    const uint64_t sb = (uint64_t)__double_as_longlong(s);
-    uint32_t sl = (uint32_t)sb, sh = (uint32_t)(sb >> 32);
-    const uint32_t ol = dpp_u32<CTRL>(sl), oh = dpp_u32<CTRL>(sh);
-    const double os = __longlong_as_double((long long)(((uint64_t)oh << 32) | ol));
-    // lanes whose id has the bit this step exchanges: they hold the higher indices
-    constexpr unsigned long long HIGH = CTRL == 0xB1 ? 0xAAAAAAAAAAAAAAAAull : (CTRL == 0x4E ? 0xCCCCCCCCCCCCCCCCull : 0xF0F0F0F0F0F0F0F0ull);
-    const unsigned long long m = __builtin_amdgcn_fcmp(s, os, 2 /* ogt */) | (__builtin_amdgcn_fcmp(s, os, 3 /* oge */) & HIGH);
-    if (CTRL == 0xB1) C4_PICK_SELECT("quad_perm:[1,0,3,2]");
-    else if (CTRL == 0x4E) C4_PICK_SELECT("quad_perm:[2,3,0,1]");
-    else C4_PICK_SELECT("row_half_mirror");
-    s = __longlong_as_double((long long)(((uint64_t)sh << 32) | sl));
-}
-#undef C4_PICK_SELECT
-#else
-template <int CTRL>
-__device__ __forceinline__ void pick_step(double &s, int &k, uint32_t &n, uint32_t &info, uint32_t &wl, uint32_t &wh)
-{
-    const double os = dpp_f64<CTRL>(s);
-    const int ok = (int)dpp_u32<CTRL>((uint32_t)k);
-    const bool keep = (s > os) | ((s == os) & (k >= ok));
-    s = keep ? s : os;
-    k = keep ? k : ok;
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
-    if (CTRL == 0xB1) C4_DPP_SELECT("quad_perm:[1,0,3,2]");
-    else if (CTRL == 0x4E) C4_DPP_SELECT("quad_perm:[2,3,0,1]");
-    else C4_DPP_SELECT("row_half_mirror");
-}
-#endif
-#undef C4_DPP_SELECT
-#if C4_PICK_BPERM
 // The argmax with the record moved ONCE: three butterfly steps on the score alone (v_max_f64 returns one of its operands: the
 // maximum is exact), the lanes that hold it found by one compare, the highest of them (ties -> higher column, tree.py:11-15)
 // by a count of leading zeros on the group's byte of the wave mask, and the winner's record fetched from its lane through the
@@ -573,27 +423,6 @@ __device__ __forceinline__ void group_pick(Pick &a)
     a.k = k;
     a.s = m;
 }
-#else
-__device__ __forceinline__ void group_pick(Pick &a)
-{
-    const uint64_t wb = (uint64_t)__double_as_longlong(a.w);
-    uint32_t wl = (uint32_t)wb, wh = (uint32_t)(wb >> 32);
-#if C4_ASM_PICK
-    // the index rides in the top three bits of the visit count (a search has fewer than 2^19 simulations, c4_engine_create)
-    uint32_t nk = a.n | ((uint32_t)(threadIdx.x & (GROUP - 1)) << 29);
-    pick_step<0xB1>(a.s, nk, a.info, wl, wh);    // quad_perm [1,0,3,2]
-    pick_step<0x4E>(a.s, nk, a.info, wl, wh);    // quad_perm [2,3,0,1]
-    pick_step<0x141>(a.s, nk, a.info, wl, wh);   // row_half_mirror
-    a.k = (int)(nk >> 29);
-    a.n = nk & 0x1fffffffu;
-#else
-    pick_step<0xB1>(a.s, a.k, a.n, a.info, wl, wh);    // quad_perm [1,0,3,2]
-    pick_step<0x4E>(a.s, a.k, a.n, a.info, wl, wh);    // quad_perm [2,3,0,1]
-    pick_step<0x141>(a.s, a.k, a.n, a.info, wl, wh);   // row_half_mirror
-#endif
-    a.w = __longlong_as_double((long long)(((uint64_t)wh << 32) | wl));
-}
-#endif
 
 // mcts.py:175-178: noise = Gamma(alpha, 1, size=7), zeroed on illegal columns and normalised (mcts.py:197-202)
 // with NumPy's sequential sum: a Dirichlet draw over the legal moves.  Lane k holds column k's raw draw.
@@ -730,12 +559,11 @@ template <> __device__ __forceinline__ void store_plane<hip_bfloat16>(void *p, s
 // expand_node call is the first descent THROUGH an evaluated node (tree_step: cN == 1), after which its visit count is >= 2,
 // and no other record has status ST_EVALUATED -- so it is the number of evaluated records with n >= 2 (NOT the number of
 // sibling blocks: a block is allocated when a node is evaluated, and most evaluated leaves are never visited again).
-// Blocks 1 .. nalloc - 1 were written whole by this search (C4_FILLERS); of block 0 only the root record exists.
+// Blocks 1 .. nalloc - 1 were written whole by this search (children and fillers); of block 0 only the root record exists.
 // `state` is stored last, behind a fence: a row is untouched or whole.
 __device__ __noinline__ void queue_write_row(c4_search_result *row, const uint8_t *pool_base, uint32_t nalloc, uint64_t root0,
                                              uint64_t root1, int mv, double absv, double pol_col, uint32_t sims, int lane)
 {
-    static_assert(C4_FILLERS, "the expansion count reads all eight records of every allocated block");
     const Rec *rec = reinterpret_cast<const Rec *>(pool_base);
     const uint32_t rinfo = rec[0].info, rn = rec[0].n;
     const uint32_t cb = info_base(rinfo), nc = info_nchild(rinfo);
@@ -890,7 +718,7 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
     // shader cycles, so cheap (shallow / terminal / cached) simulations are not rationed by count and
     // every wave of a launch ends at about the same time
     const unsigned long long t_begin = (!WAVE_SYNC && d.time_budget > 0) ? __builtin_amdgcn_s_memtime() : 0;
-    bool resume = !(WAVE_SYNC && C4_NO_SUSPEND) && (pend == -2);   // the wave-autonomous kernels have no level budget: no descent is ever suspended there
+    bool resume = !WAVE_SYNC && (pend == -2);   // the wave-autonomous kernels have no level budget: no descent is ever suspended there
     // Hot subtree in LDS: once a launch has loaded the root's sibling block it stays in s_l1 for all
     // further simulations of the launch (write-through on every backup), so level 1 of every later
     // descent is an LDS read instead of an HBM round trip.
@@ -909,7 +737,6 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
         if (SPLIT) { const unsigned long long tn = __builtin_amdgcn_s_memtime(); if (ph_t0) { (ph_was_waiting ? ph_wait : ph_iter) += tn - ph_t0; ph_n += ph_was_waiting ? 0 : 1; } ph_t0 = tn; ph_was_waiting = waiting; }
 #endif
         if (SPLIT) {
-#if C4_WAIT_CLOCK_LAZY
             // Nobody in this wave can walk (every lane still in the loop waits): sleep, and look at the clock HERE only -- while
             // some slot walks, the walking lanes' deadline check ends their part of the call and the waiting lanes arrive here.
             if (__builtin_amdgcn_ballot_w64(!waiting) == 0) {
@@ -917,11 +744,6 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
                 if ((long long)(__builtin_amdgcn_s_memtime() - deadline) > 0) { has_leaf = 1; break; }
             }
             if (waiting) {
-#else
-            if (__builtin_amdgcn_ballot_w64(!waiting) == 0) __builtin_amdgcn_s_sleep(4);   // nobody in this wave can walk
-            if (waiting) {
-                if ((long long)(__builtin_amdgcn_s_memtime() - deadline) > 0) { has_leaf = 1; break; }
-#endif
                 if (lds_ld(req) != REQ_ANSWERED) continue;
 #if C4_SPLIT_PHASES
                 if (lane == 0) {   // diagnostic: answered -> picked up, in units of 64 cycles
@@ -948,7 +770,7 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
             // the walk must not depend on the evaluator (counted in stats as bad_evals).  Only finite answers reach the
             // evaluation cache, so a cache hit needs no check; in the split kernel the network wave has looked at a fresh
             // answer before it published it (sanitise_answer), and the tree waves carry no check at all.
-            if (!(SPLIT && C4_NET_SANITISES) && !cached_answer) {   // (an answer of any evaluator: the device net, a host callable, the centre heuristic)
+            if (!SPLIT && !cached_answer) {   // (an answer of any evaluator: the device net, a host callable, the centre heuristic)
                 const bool bad = !(ev_value >= 0.0 && ev_value <= 1.0) || !(ev_prior >= 0.0 && ev_prior <= 3.0e38);
                 if (__ballot(bad) >> (((threadIdx.x & 63) / GROUP) * GROUP) & 0xffull) {
                     if (!(ev_value >= 0.0 && ev_value <= 1.0)) ev_value = 0.5;
@@ -971,16 +793,11 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
             if (SCORE_F32) {
                 const float pf = legal ? (float)ev_prior : 0.0f;
                 float s = 0.0f;
-#if C4_COOP_LEGAL
                 float pall[7];   // (all seven fetches in flight before the first add: the sum keeps NumPy's order)
 #pragma unroll
                 for (int i = 0; i < 7; ++i) pall[i] = gshfl(pf, i);
 #pragma unroll
                 for (int i = 0; i < 7; ++i) s = s + pall[i];
-#else
-#pragma unroll
-                for (int i = 0; i < 7; ++i) s = s + gshfl(pf, i);
-#endif
                 prn = s > 0.0f ? (double)(pf / s) : (legal ? 1.0 / (double)__popc(mask) : 0.0);
                 pf64 = 0;
             } else {
@@ -1009,9 +826,9 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
             const uint32_t nchild = (uint32_t)__popc(mask);
             const uint32_t base = nalloc * GROUP;
             nalloc += 1;
-#if C4_FILLERS
             {   // all eight records of the block are written: the children in column order, then fillers nobody can choose -- their q
-                // is -inf, so their score (prior term + value, either form) is -inf by arithmetic
+                // is -inf, so their score (prior term + value, either form) is -inf by arithmetic: the level loop needs no "is this
+                // lane a child" logic
                 const int below = (1 << lane) - 1;
                 Rec nr{0.0, -std::numeric_limits<double>::infinity(), 0.0, 0u, pack_info(0, 0, ST_FRESH, 0, 0)};
                 uint32_t k = nchild + (uint32_t)__popc(~mask & 0x7f & below);
@@ -1020,22 +837,11 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
                     uint64_t c0 = leaf0, c1 = leaf1;
                     const uint32_t bit = (uint32_t)(H1 * lane + col_count(occ, lane));
                     const uint32_t cst = make_move(c0, c1, lane);
-                    // q of a terminal child = its exact result (utils.py:19-22), see child_value_for
+                    // q of a terminal child = its exact result (utils.py:19-22), see orient_q
                     nr = Rec{0.0, cst >= ST_XWIN ? orient_q(0.5 * (double)(cst - ST_XWIN), age) : 0.0, prn, 0u, pack_info(0, 0, cst, bit, 0)};
                 }
                 *pool.rec(base + k) = nr;
             }
-#else
-            if (legal) {
-                const uint32_t k = (uint32_t)__popc(mask & ((1 << lane) - 1));
-                uint64_t c0 = leaf0, c1 = leaf1;
-                const uint32_t bit = (uint32_t)(H1 * lane + col_count(occ, lane));
-                const uint32_t cst = make_move(c0, c1, lane);
-                const uint32_t idx = base + k;
-                // q of a terminal child = its exact result (utils.py:19-22), see child_value_for
-                *pool.rec(idx) = Rec{0.0, cst >= ST_XWIN ? orient_q(0.5 * (double)(cst - ST_XWIN), age) : 0.0, prn, 0u, pack_info(0, 0, cst, bit, 0)};
-            }
-#endif
             if (lane == 0) {   // mcts.py:132-134: position_value / search_value.add(value)
                 if (l1_valid && pdepth == 1) {   // the leaf is a child of the root: keep the LDS copy current
                     Rec &c = s_l1[gl][pend & 7];
@@ -1059,19 +865,14 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
                     pool.q(e.node) = nq;
                     if (l1_valid && i == 1) { Rec &c = s_l1[gl][e.node & 7]; c.n = e.n + 1; c.w = nw; c.q = nq; }
                 };
-#if C4_PEEL_BACKUP
                 if ((uint32_t)lane < pdepth) back_up((uint32_t)lane);
                 for (uint32_t i = lane + GROUP; i < pdepth; i += GROUP) back_up(i);
-#else
-                for (uint32_t i = lane; i < pdepth; i += GROUP) back_up(i);
-#endif
             }
             root_w = pdepth == 0 ? ev_value : root_w + ev_value;
             if (pdepth == 0) l1_valid = false;   // a new sibling block under the root
             st.leaf_evals += 1;
             st.children += nchild;
             if (pdepth > 0) sims += 1;
-            (void)age;
             pend = -1;
             group_fence();
             stamp(2);
@@ -1134,8 +935,7 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
             const double cq = act ? pool.q(cb + lane) : 0.0;
             const uint32_t ci = act ? pool.info(cb + lane) : 0;
             const int root_age = popc64(root0 | root1);
-            const int side = root_age & 1;
-            const double V = act ? (C4_ORIENTED_Q ? cq : child_value_for(info_status(ci), cn, cq, side)) : 0.0;
+            const double V = act ? cq : 0.0;
             // tree.py:104-109 + :139-147 values policy
             double vs = 0.0;
 #pragma unroll
@@ -1152,14 +952,10 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
             if (kb < 0) kb = group_argmax(act ? V : -1.0, act ? lane : -1);   // tree.py:69-73 best_move
             const uint32_t bi = gshfl(ci, kb);
             const uint32_t bn = gshfl(cn, kb);
-#if C4_ORIENTED_Q
             // (the record's q is the value for the root's mover; the absolute value is value_sum / visit_count: the very division the
             //  backups do, on the record's own w and n)
             const double cw = act ? pool.w(cb + lane) : 0.0;
             const double bq = div_normal(gshfl(cw, kb), (double)(bn > 0 ? bn : 1u));
-#else
-            const double bq = gshfl(cq, kb);
-#endif
             const int mv = (int)info_move(bi);
             const uint32_t bst = info_status(bi);
             double absv;   // child.data.absolute_value (mcts.py:88)
@@ -1237,7 +1033,7 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
         if (SPLIT) {
             if ((long long)(__builtin_amdgcn_s_memtime() - deadline) > 0) break;
         } else if (WAVE_SYNC && !resume && (__builtin_amdgcn_ballot_w64(true) != wave_mask0 ||
-                                     ((inner & (C4_DEADLINE_EVERY - 1)) == 0 && (long long)(__builtin_amdgcn_s_memtime() - deadline) > 0))) break;
+                                     (long long)(__builtin_amdgcn_s_memtime() - deadline) > 0)) break;   // (the clock every simulation: every fourth measured no faster)
         if (!SPLIT && !resume && (inner >= d.max_inner || levels_left <= 0 ||
                         (!WAVE_SYNC && d.time_budget > 0 && inner > 0 && (long long)(__builtin_amdgcn_s_memtime() - t_begin) > d.time_budget))) {
             st.capped += 1;
@@ -1276,23 +1072,18 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
             }
             b0 = root0;
             b1 = root1;
-#if C4_PATH_ALL_LANES
-            s_path[gl][0] = PathEntry{0u, cN, cW};
-#else
-            if (lane == 0) s_path[gl][0] = PathEntry{0u, cN, cW};
-#endif
+            s_path[gl][0] = PathEntry{0u, cN, cW};   // (stored by all eight lanes, as in the level loop)
         }
         int age = popc64(b0 | b1);
 #if C4_SPLIT_PHASES
         const unsigned long long ph_tl = __builtin_amdgcn_s_memtime();
 #endif
         unsigned long long lvl_t0 = (STAMPS && d.has_stamps) ? __builtin_amdgcn_s_memtime() : 0, lvl_wait = 0, lvl_alu = 0, lvl_cnt = 0;
-#if C4_EARLY_REQUEST
         // Software-pipelined level loop: the sibling block (and score-table entry) of the NEXT level is requested
         // the moment the argmax is known, in front of this level's bookkeeping (board replay, path entry,
         // counters), so that bookkeeping runs under the load instead of in front of it.
         // All 8 lanes of the group load "their" record of the 8-record sibling block, also the lanes beyond the node's
-        // children (their records exist in the pool and are never scored): no predicate, no zero fill on the loads.
+        // children (their records exist in the pool: fillers that score -inf): no predicate, no zero fill on the loads.
         // The level budget is a feature of c4_step; the wave-autonomous kernel (WAVE_SYNC) bounds its calls by time.
         constexpr bool BUDGET = !WAVE_SYNC;
         Rec r;
@@ -1314,16 +1105,12 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
             r = Rec{};
             ab = double2{0.0, 0.0};
         }
-#if C4_VGPR_BASES
         // the two bases of the level loop's requests in vector registers (the kernel has ~130 scalars spilled to lanes: four
         // v_readlane per level otherwise)
         const double2 *tab_v = d.tabAB;
         const Rec *rec_v = pool.rec((uint32_t)lane);
         asm volatile("" : "+v"(tab_v), "+v"(rec_v));
-#endif
-#if C4_FILLERS
         b1 ^= b0;   // inside the loop b1 is the occupancy: every stone goes in, only o's stones need a select
-#endif
         while (go) {
             if (BUDGET) levels_left -= 1;
             const uint32_t cb = info_base(cinfo), nc = info_nchild(cinfo), pf64 = info_pf64(cinfo);
@@ -1338,20 +1125,9 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
                 lvl_wait += t1 - lvl_t0;
                 lvl_t0 = t1;
             }
-            const double V = C4_ORIENTED_Q ? q : child_value_for(info_status(inf), n, q, age & 1);
-#if C4_SCORE_ALL
-            // all eight lanes score (the lanes beyond the node's children hold records nobody reads otherwise): a select
-            // instead of a branch around the division
-#if C4_FILLERS
-            (void)act;
+            const double V = q;   // oriented for this node's mover by whoever wrote it (orient_q)
+            // all eight lanes score (the lanes beyond the node's children hold fillers): no branch around the division (+1.6 %)
             const double s = ucb_score(A, B, n, p, V, pf64);   // (a filler's q is -inf: so is its score)
-#else
-            const double sc = ucb_score(A, B, act ? n : 0u, p, V, pf64);
-            const double s = act ? sc : -std::numeric_limits<double>::infinity();
-#endif
-#else
-            const double s = act ? ucb_score(A, B, n, p, V, pf64) : -std::numeric_limits<double>::infinity();
-#endif
             Pick best{s, act ? lane : -1, n, inf, w};
             group_pick(best);                                   // mcts.py:141-142 max((score, child))
             // ---- next level's request
@@ -1359,15 +1135,9 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
             Rec rn = r;
             double2 abn = ab;
             if (go) {
-#if C4_VGPR_BASES
                 abn = tab_v[best.n];
                 asm volatile("" ::: "memory");
                 rn = rec_v[info_base(best.info)];
-#else
-                abn = d.tabAB[best.n];
-                asm volatile("" ::: "memory");
-                rn = *pool.rec(info_base(best.info) + lane);
-#endif
             }
             // ---- this level's bookkeeping
             cN = best.n;
@@ -1377,19 +1147,11 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
             {   // board.py:160-163 replayed: xor the recorded stone into the mover's colour (b1 is kept as occupancy ^ b0 inside the loop)
                 const uint64_t stone = 1ULL << info_bit(cinfo);
                 b0 ^= (age & 1) ? 0ULL : stone;
-#if C4_FILLERS
                 b1 ^= stone;
-#else
-                b1 ^= (age & 1) ? stone : 0ULL;
-#endif
             }
             age += 1;
             depth += 1;
-#if C4_PATH_ALL_LANES
-            s_path[gl][depth] = PathEntry{cur, cN, cW};   // all eight lanes store the same entry: no exec-mask region in the level loop
-#else
-            if (lane == 0) s_path[gl][depth] = PathEntry{cur, cN, cW};
-#endif
+            s_path[gl][depth] = PathEntry{cur, cN, cW};   // all eight lanes store the same entry (same words, same address): no exec-mask region in the level loop (+0.5 %)
             r = rn;
             ab = abn;
             if (STAMPS && d.has_stamps) {
@@ -1399,68 +1161,12 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
                 lvl_cnt += 1;
             }
         }
-#if C4_FILLERS
         b1 ^= b0;
-#endif
-#else
-        while (info_status(cinfo) == ST_EVALUATED && levels_left > 0) {
-            levels_left -= 1;
-            const uint32_t cb = info_base(cinfo), nc = info_nchild(cinfo), pf64 = info_pf64(cinfo);
-            if (cN == 1) st.expansions += 1;   // first descent through an evaluated node == expand_node
-            const bool act = lane < (int)nc;
-            const uint32_t idx = cb + lane;
-            // the score-table entry is requested FIRST so that its (L1/L2) latency hides under the
-            // sibling-block loads instead of being paid after them; the barrier keeps the order
-            const double2 ab = d.tabAB[cN];
-            asm volatile("" ::: "memory");
-            Rec r = {};
-            if (depth == 0 && l1_valid) {
-                if (act) r = s_l1[gl][lane];                  // hot subtree: LDS
-            } else {
-                if (act) r = *pool.rec(idx);                  // two 16-byte loads per lane
-                if (depth == 0) {                             // first descent of the launch: stage the block
-                    if (act) s_l1[gl][lane] = r;
-                    l1_valid = true;
-                }
-            }
-            const uint32_t n = r.n, inf = r.info;
-            const double w = r.w, q = r.q, p = r.p;
-            const double A = ab.x, B = ab.y;
-            if (STAMPS && d.has_stamps) {   // diagnostic: cycles spent waiting for this level's loads
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-                lvl_wait += t1 - lvl_t0;
-                lvl_t0 = t1;
-            }
-            const double V = C4_ORIENTED_Q ? q : child_value_for(info_status(inf), n, q, age & 1);
-            const double s = act ? ucb_score(A, B, n, p, V, pf64) : -std::numeric_limits<double>::infinity();
-            Pick best{s, act ? lane : -1, n, inf, w};
-            group_pick(best);                                   // mcts.py:141-142 max((score, child))
-            cN = best.n;
-            cW = best.w;
-            cinfo = best.info;
-            cur = cb + (uint32_t)best.k;
-            {   // board.py:160-163 replayed: xor the recorded stone into the mover's colour
-                const uint64_t stone = 1ULL << info_bit(cinfo);
-                b0 ^= (age & 1) ? 0ULL : stone;
-                b1 ^= (age & 1) ? stone : 0ULL;
-            }
-            age += 1;
-            depth += 1;
-            if (lane == 0) s_path[gl][depth] = PathEntry{cur, cN, cW};
-            if (STAMPS && d.has_stamps) {
-                const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-                lvl_alu += t2 - lvl_t0;
-                lvl_t0 = t2;
-                lvl_cnt += 1;
-            }
-        }
-#endif
         if (STAMPS && d.has_stamps && blockIdx.x < 256 && threadIdx.x == 0) {
             d.cold->stamps[blockIdx.x * 8 + 7] = (lvl_wait << 32) | (lvl_alu & 0xffffffffu);
             d.cold->stamps[blockIdx.x * 8 + 6] = ((unsigned long long)lvl_cnt << 32) | depth;
         }
-        if (!(WAVE_SYNC && C4_NO_SUSPEND) && info_status(cinfo) == ST_EVALUATED) {   // level budget exhausted mid-descent: suspend
+        if (!WAVE_SYNC && info_status(cinfo) == ST_EVALUATED) {   // level budget exhausted mid-descent: suspend
             lds_fence();
             for (uint32_t i = lane; i <= depth; i += GROUP) gpath[i] = s_path[gl][i];
             if (lane == 0) {
@@ -1497,12 +1203,8 @@ __device__ __forceinline__ void tree_step(DevT &d, const int g, const int lane, 
                     pool.q(e.node) = nq;
                     if (l1_valid && i == 1) { Rec &c = s_l1[gl][e.node & 7]; c.n = e.n + 1; c.w = nw; c.q = nq; }
                 };
-#if C4_PEEL_BACKUP
                 if ((uint32_t)lane <= depth) back_up((uint32_t)lane);
                 for (uint32_t i = lane + GROUP; i <= depth; i += GROUP) back_up(i);
-#else
-                for (uint32_t i = lane; i <= depth; i += GROUP) back_up(i);
-#endif
             }
             root_w = root_w + value;
             sims += 1;
@@ -2137,7 +1839,7 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
     static_assert(TW >= 1 && NW >= 1 && SPW >= 1 && SPW <= 8 && TS <= 64, "slots per workgroup");
     // two positions per pass when two requests wait: pays once the network waves are the busier half (32 slots per CU: +1.5 %;
     // 16 slots: -1.5 %)
-    constexpr bool PAIRS = MODE == NETMODE_F32_F16 && TS == 32 && C4_SPLIT_PAIRS;
+    constexpr bool PAIRS = MODE == NETMODE_F32_F16 && TS == 32;
     constexpr int WBUF = WaveBuf<MODE>::HALVES * (PAIRS ? 2 : 1);
     // speculative evaluation by network waves that have nothing else to do (4096 games: +4.3 %, f32x3 +1.2 %, 8192 games +0.2 %;
     // 64 filters -1.5 %: its network waves are never idle and the check is not free)
@@ -2146,7 +1848,7 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
     // net (34 k cycles per pass, network waves busy 80 % with real requests alone) it COSTS 3.5 % (r03 A/B, profiles/r03_ab_speculation.json:
     // always 235 M, only while one / two / three other network waves are idle 236 / 239 / 241 M, never 244 M): off there, as for
     // 64 filters.
-    constexpr bool SPECULATE = C4_SPECULATE && MODE == NETMODE_F32_F16;
+    constexpr bool SPECULATE = MODE == NETMODE_F32_F16;
     // (two network waves per position -- the forward split by cout tile, shared planes, a flag handshake per layer -- was built,
     // bit-identical, and measured: latency -28 %, but 43 k instead of 31 k wave-cycles per evaluation; -17 %.  profiles/r03_ab_pair_split_and_roles.json)
     __shared__ __attribute__((aligned(16))) _Float16 act[NW][WBUF];   // planes of the network waves
@@ -2212,10 +1914,11 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
     __syncthreads();
     // Which slots a tree wave walks: the workgroup's ACTIVE slots, sorted by ply, dealt out in TW contiguous chunks of equal size
     // (+-1).  Games at a similar stage end their simulations in similar ways, so a wave's lock-step iterations spend less time in
-    // phases only one of its slots needs (+1.6 % fp16 net, +0.3 % reference precision); and a workgroup that is not full -- a
+    // phases only one of its slots needs (+1.6 % fp16 net, +0.3 % reference precision; sorting by simulations done or by the
+    // measured leaf depth instead: nothing); and a workgroup that is not full -- a
     // small batch spread over the CUs, the tail of a generation when slots have parked -- keeps ALL its tree waves busy with
     // one or two slots each instead of filling wave 0 first.  (All writers are threads of wave 0: LDS executes them in order.)
-    if (C4_SORT_SLOTS && threadIdx.x < 64) {
+    if (threadIdx.x < 64) {
         const int p = threadIdx.x;
         if (p < TW * SPW) s_perm[p] = 0xff;
         const bool act = p < TS && smem[p < TS ? p : 0].state() == SLOT_ACTIVE;
@@ -2233,7 +1936,7 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
     // Answers carried over from the previous launch were written by whatever ran last -- a network wave of this kernel (already
     // finite) or c4_net_forward / a host evaluator between c4_step launches (include/c4_engine.h: the launches are
     // interchangeable) -- and the tree waves below apply answers without a check of their own: make them finite here.
-    if (C4_NET_SANITISES && threadIdx.x < TS && smem[threadIdx.x].has_leaf()) {
+    if (threadIdx.x < TS && smem[threadIdx.x].has_leaf()) {
         const int p = threadIdx.x;
         bool bad = false;
         const float v = s_val[p];
@@ -2273,7 +1976,7 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
             const int lane = tid & (GROUP - 1);
             const int grp = (tid & 63) / GROUP;
             const int sl0 = tw + TW * grp;        // slot of this 8-lane group inside the workgroup
-            const int sl = (C4_SORT_SLOTS && grp < SPW) ? (int)s_perm[tw * SPW + grp] : sl0;   // (0xff = no slot: >= TS)
+            const int sl = grp < SPW ? (int)s_perm[tw * SPW + grp] : sl0;   // (0xff = no slot: >= TS)
             bool runnable = false;
             if (grp < SPW && sl < TS) {
                 const uint32_t fl = smem[sl].flags;
@@ -2360,11 +2063,10 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
                     net_forward_wave1_mode<MODE>(nd, &act[nw][0], mlp, s_bias, s_tab16, b0, b1, s_val, s_pri, row, s_w0, nstamps);
                 }
                 lds_fence();   // the answer is in LDS before the request word says so
-                if (C4_NET_SANITISES) {   // see tree_step's apply: answers leave this server finite
-                    sanitise_answer(s_val, s_pri, row, lw, s_stats);
-                    if (PAIRS && c2 >= 0) sanitise_answer(s_val, s_pri, c2, lw, s_stats);
-                    lds_fence();
-                }
+                // see tree_step's apply: answers leave this server finite
+                sanitise_answer(s_val, s_pri, row, lw, s_stats);
+                if (PAIRS && c2 >= 0) sanitise_answer(s_val, s_pri, c2, lw, s_stats);
+                lds_fence();
                 if (is_spec) {
                     if (lw < GROUP) cache_insert(d, b0, b1, lw, s_val[row], lw < 7 ? s_pri[row * 7 + lw] : 0.0f);
                     if (lw == 0) atomicAdd(&s_stats[offsetof(SlotStats, spec_evals) / sizeof(uint64_t)], 1u);

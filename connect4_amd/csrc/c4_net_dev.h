@@ -520,9 +520,7 @@ __device__ __forceinline__ void store16(const floatx4 &acc, _Float16 *dst, int o
 #ifndef C4_NET_STAMP_LAYER
 #define C4_NET_STAMP_LAYER 2   // diagnostic stamps 12..14 split this layer of the tower into k-loop / skip / epilogue
 #endif
-#ifndef C4_NET_BDEPTH
-#define C4_NET_BDEPTH 2   // operand ring of the tower's k-loop: reads run this many taps minus one ahead (3 and 4 measured the same)
-#endif
+constexpr int NET_BDEPTH = 2;   // operand ring of the tower's k-loop: reads run this many taps minus one ahead (3 and 4 measured the same)
 template <int NP>
 __device__ __forceinline__ void net_forward_wave16n(const NetDev &nd, _Float16 *buf, const float4 *mlp, const float *bias_lds,
                                                     const uint16_t *tab, const uint64_t (&b0)[NP], const uint64_t (&b1)[NP],
@@ -536,7 +534,7 @@ __device__ __forceinline__ void net_forward_wave16n(const NetDev &nd, _Float16 *
     auto stamp = [&](int i) { if (stamps && lane == 0) stamps[i] = __builtin_amdgcn_s_memtime(); };
     stamp(0);
     const int n_layers = 2 * nd.n_res;
-    constexpr int BDEPTH = NP == 1 ? C4_NET_BDEPTH : 2;   // ring of operand fragments
+    constexpr int BDEPTH = NP == 1 ? NET_BDEPTH : 2;   // ring of operand fragments
     // position i: ping plane at buf + 2 i PLANE16, pong plane behind it
 #define P0(i) (buf + (2 * (i)) * PLANE16)
 #define P1(i) (buf + (2 * (i) + 1) * PLANE16)
@@ -788,22 +786,6 @@ __device__ __forceinline__ void net_forward_wave16(const NetDev &nd, _Float16 *b
 // ------------------------------------------------------------------------------------------------
 constexpr int WTAPS = 3;   // taps of weights in flight (divides 9: a tap's window slot is t % 3 in every layer)
 
-__device__ __forceinline__ void store16p(const floatx4 &hi, const floatx4 &lo, _Float16 *dh, _Float16 *dl, int off, bool real)
-{
-    half4 oh, ol;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float y = lrelu(hi[i] + lo[i] * LO_INV);
-        const _Float16 yh = (_Float16)y;
-        oh[i] = yh;
-        ol[i] = (_Float16)((y - (float)yh) * LO_SCALE);
-    }
-    if (real) {
-        *reinterpret_cast<half4 *>(dh + off) = oh;
-        *reinterpret_cast<half4 *>(dl + off) = ol;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // net_forward_wave16q: the one-position reference-precision forward, with an instruction stream lean enough for ONE wave to
 // keep its SIMD's MFMA pipe fed -- a wave cannot issue its MFMAs back to back when ~30 other instructions per tap stand
@@ -816,20 +798,11 @@ __device__ __forceinline__ void store16p(const floatx4 &hi, const floatx4 &lo, _
 //   * what a pass needs FIRST -- the stem's and the heads' fragments, the tower's first two taps -- lives in LDS for the whole
 //     launch (18 KB per workgroup, stage_w0_lds): a pass no longer starts with an L2 round trip in front of its first MFMA;
 //   * group barriers spread the next tap's operand reads and the weight requests between the MFMAs instead of in
-//     clusters in front of them (C4_F32X3_SGB; with buffer loads but WITHOUT them the compiler's order is 30 % slower
+//     clusters in front of them (with buffer loads but WITHOUT them the compiler's order is 30 % slower
 //     than round 2's);
 //   * the epilogue runs on packed float32 instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: two values per
 //     instruction; hi + lo * 2^-11 as ONE fma -- the product is exact, so the rounding is the add's).
 // ------------------------------------------------------------------------------------------------
-#ifndef C4_F32X3_SGB
-#define C4_F32X3_SGB 1
-#endif
-#ifndef C4_F32X3_PKEPI
-#define C4_F32X3_PKEPI 1
-#endif
-#ifndef C4_F32X3_MIXEPI
-#define C4_F32X3_MIXEPI 1
-#endif
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
@@ -853,9 +826,9 @@ __device__ __forceinline__ void stage_w0_lds(const NetDev &nd, half8 *w0)
     for (int i = threadIdx.x; i < W0_FRAGS * 64; i += blockDim.x) w0[i] = nd.w0[i];
 }
 
+// y = lrelu(hi + lo * LO_INV), stored as yh = RN16(y) and yl = RN16((y - yh) * LO_SCALE), two values per packed instruction
 __device__ __forceinline__ void store16q(const floatx4 &hi, const floatx4 &lo, _Float16 *dh, _Float16 *dl, int off, bool real)
 {
-#if C4_F32X3_PKEPI
     half4 oh, ol;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -866,7 +839,6 @@ __device__ __forceinline__ void store16q(const floatx4 &hi, const floatx4 &lo, _
         asm("v_max_f32 %0, %1, %2" : "=v"(y.x) : "v"(y.x), "v"(ly.x));
         asm("v_max_f32 %0, %1, %2" : "=v"(y.y) : "v"(y.y), "v"(ly.y));
         const half2v yh = __builtin_convertvector(y, half2v);
-#if C4_F32X3_MIXEPI
         // lo = RN16((y - yh) * 2^11) as ONE mixed-precision fma per value: fma(yh [fp16 operand], -2^11, y * 2^11) is exact in
         // float32 (y - yh has at most 13 significant bits), so the only rounding is the conversion -- the same value as the
         // convert / subtract / scale / convert sequence, in 3 instructions per pair instead of 5
@@ -877,11 +849,6 @@ __device__ __forceinline__ void store16q(const floatx4 &hi, const floatx4 &lo, _
         asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(ylb) : "v"(yhb), "s"(nsc), "v"(ysc.x));
         asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(ylb) : "v"(yhb), "s"(nsc), "v"(ysc.y));
         const half2v yl = __builtin_bit_cast(half2v, ylb);
-#else
-        const float2v back = __builtin_convertvector(yh, float2v);
-        const float2v rl = (y - back) * sc;
-        const half2v yl = __builtin_convertvector(rl, half2v);
-#endif
         oh[2 * i] = yh.x; oh[2 * i + 1] = yh.y;
         ol[2 * i] = yl.x; ol[2 * i + 1] = yl.y;
     }
@@ -889,9 +856,6 @@ __device__ __forceinline__ void store16q(const floatx4 &hi, const floatx4 &lo, _
         *reinterpret_cast<half4 *>(dh + off) = oh;
         *reinterpret_cast<half4 *>(dl + off) = ol;
     }
-#else
-    store16p(hi, lo, dh, dl, off, real);
-#endif
 }
 
 __device__ __forceinline__ void net_forward_wave16q(const NetDev &nd, _Float16 *buf, const float4 *mlp, const float *bias_lds,
@@ -1007,9 +971,7 @@ __device__ __forceinline__ void net_forward_wave16q(const NetDev &nd, _Float16 *
             bh[rt] = *reinterpret_cast<const half8 *>(sh + tof(rt * 9));
             bl[rt] = *reinterpret_cast<const half8 *>(sl + tof(rt * 9));
         }
-#if C4_F32X3_SGB
         __builtin_amdgcn_sched_barrier(0);   // the group barriers below order the k-loop's own reads: the first tap's stay in front of it
-#endif
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             {   // refill: the slot the PREVIOUS tap used gets the tap two ahead of this one
@@ -1039,7 +1001,6 @@ __device__ __forceinline__ void net_forward_wave16q(const NetDev &nd, _Float16 *
             }
 #pragma unroll
             for (int rt = 0; rt < RT16; ++rt) { bh[rt] = nh[rt]; bl[rt] = nl[rt]; }
-#if C4_F32X3_SGB
             // this tap's instruction order: the four weight requests behind the first MFMAs, then one operand read of the
             // next tap per two MFMAs
 #pragma unroll
@@ -1051,11 +1012,8 @@ __device__ __forceinline__ void net_forward_wave16q(const NetDev &nd, _Float16 *
             } else {
                 __builtin_amdgcn_sched_group_barrier(0x008, 14, 0);
             }
-#endif
         }
-#if C4_F32X3_SGB
         __builtin_amdgcn_sched_barrier(0);
-#endif
         if (L == C4_NET_STAMP_LAYER) stamp(12);
         if (second) {   // + block input (lives in dh/dl): identity MFMAs keep it exact in both accumulators
 #pragma unroll
@@ -1517,9 +1475,7 @@ __device__ __forceinline__ void net_forward_wave16x(const NetDev &nd, _Float16 *
                 bh[rt] = *reinterpret_cast<const half8 *>(sh + tof(rt * 9));
                 bl[rt] = *reinterpret_cast<const half8 *>(sl + tof(rt * 9));
             }
-#if C4_F32X3_SGB
             __builtin_amdgcn_sched_barrier(0);   // the group barriers below order the k-loop's own reads: the first unit's stay in front of it
-#endif
 #pragma unroll
             for (int u = 0; u < 18; ++u) {   // unit u = (tap u / 2, k-step u % 2)
                 {   // refill: the slot the PREVIOUS unit used gets the unit two ahead of this one
@@ -1549,7 +1505,6 @@ __device__ __forceinline__ void net_forward_wave16x(const NetDev &nd, _Float16 *
                 }
 #pragma unroll
                 for (int rt = 0; rt < RT16; ++rt) { bh[rt] = nh[rt]; bl[rt] = nl[rt]; }
-#if C4_F32X3_SGB
                 // this unit's instruction order (as net_forward_wave16q's tap): the four weight requests behind the first
                 // MFMAs, then one operand read of the next unit per two MFMAs
 #pragma unroll
@@ -1561,11 +1516,8 @@ __device__ __forceinline__ void net_forward_wave16x(const NetDev &nd, _Float16 *
                 } else {
                     __builtin_amdgcn_sched_group_barrier(0x008, 14, 0);
                 }
-#endif
             }
-#if C4_F32X3_SGB
             __builtin_amdgcn_sched_barrier(0);
-#endif
             if (second) {   // + block input (lives in dh/dl): the half's 32 channels are k-step ch of the destination rows; identity
                             // MFMAs add hi into the first accumulator and lo into the second, exactly
 #pragma unroll
