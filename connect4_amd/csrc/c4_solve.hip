@@ -824,6 +824,26 @@ int c4_solve_table_clear(c4_solve_table *table, void *hip_stream)
     return C4_OK;
 }
 
+// Every solver call waits for its last launch before it returns, so after the device-wide wait the copy sees all its stores.
+int c4_solve_table_read(c4_solve_table *table, uint64_t *entries_host, int64_t n)
+{
+    if (!table || !table->entries || !entries_host) { set_solve_err("null argument"); return C4_EINVAL; }
+    if (table->log2_entries < TT_MIN_LOG2 || table->log2_entries > TT_MAX_LOG2) {
+        set_solve_err("not a table of c4_solve_table_create");
+        return C4_EINVAL;
+    }
+    const int64_t entries = (int64_t)1 << table->log2_entries;
+    if (n != entries) {
+        set_solve_err("n = %lld, the table has 2^%d = %lld entries", (long long)n, table->log2_entries, (long long)entries);
+        return C4_EINVAL;
+    }
+    int rc = pick_device(table->device);
+    if (rc) return rc;
+    SOLVE_CHECK(hipDeviceSynchronize());
+    SOLVE_CHECK(hipMemcpy(entries_host, table->entries, (size_t)entries * 8, hipMemcpyDeviceToHost));
+    return C4_OK;
+}
+
 int c4_solve_deep_dev(int device, void *hip_stream, c4_solve_table *table, const int64_t *boards_dev, int64_t n, int64_t node_budget,
                       int64_t nodes_per_launch, int8_t *status_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev,
                       int64_t *table_hits_dev)

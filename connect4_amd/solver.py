@@ -15,6 +15,8 @@ all calls share, and a split that spreads one hard position over many lanes.  Ne
                 oinkoink/scripts/generate_7ply.py:83-91) and a report
 ``solve_host``  a plain-Python mirror of the kernel's search -- same integer score, same pruning and move order, same node
                 counts -- for tests and for machines without a GPU; with ``table={}`` also of its probe / store logic
+``HostTable``   the kernel's table (layout, slot function, always-replace) behind ``solve_host(table=...)``;
+                ``entry_fields`` takes a table image (``Table.read()``, ``HostTable.words``) apart
 
 The integer score: a game o wins at age ``a`` scores ``43 - a``, one x wins ``a - 43``, a draw 0, taken from the side to
 move inside the search.  It is strictly monotone in the reference's float, so max / min over it pick what the reference's
@@ -31,8 +33,8 @@ from .board import BOTTOM, H1, HEIGHT, SIZE, WIDTH, Board, _wins
 from .grid_search import GridTree, _terminal_value
 from .utils import Side
 
-__all__ = ["MAX_EMPTIES", "DEEP_MAX_EMPTIES", "DEFAULT_NODE_BUDGET", "STATUS_NAMES", "Solved", "HostAnswer", "Table", "solve", "solve_host",
-           "grid_triple", "label", "prior_from_children", "value_from_answer", "random_playout", "random_openings"]
+__all__ = ["MAX_EMPTIES", "DEEP_MAX_EMPTIES", "DEFAULT_NODE_BUDGET", "STATUS_NAMES", "Solved", "HostAnswer", "Table", "HostTable",
+           "EntryFields", "entry_fields", "solve", "solve_host", "grid_triple", "label", "prior_from_children", "value_from_answer", "random_playout", "random_openings"]
 
 MAX_EMPTIES = L.SOLVE_MAX_EMPTIES
 DEEP_MAX_EMPTIES = L.SOLVE_DEEP_MAX_EMPTIES     # every position: c4_solve_deep and solve(deep=True / table=)
@@ -105,8 +107,89 @@ _LOWER, _UPPER, _EXACT = 1, 2, 3        # the bound kinds of a table entry (c4_s
 _TT_MIN_EMPTIES = 6                     # nodes with fewer empty squares neither probe nor store (c4_solve.hip)
 
 
+_TT_KEY_BITS, _TT_SCORE_SHIFT, _TT_KIND_SHIFT = 49, 49, 56      # the entry word (c4_solve.hip tt_store)
+_TT_KEY_MASK = (1 << _TT_KEY_BITS) - 1
+_TT_HASH = 0x9E3779B97F4A7C15                                   # tt_slot
+
+EntryFields = namedtuple("EntryFields", "index key score kind mine occ color0 color1 age")
+
+
+class HostTable:
+    """The kernel's table on the host: ``2 ** log2_entries`` words of its layout (key in bits 0..48, score + 64 in bits
+    49..55, kind in bits 56..57), its slot function (the top `log2_entries` bits of ``key * 0x9E3779B97F4A7C15 mod 2^64``),
+    always-replace, and a hit only on the whole key.  It is what ``solve_host(table=...)`` takes in place of a dict;
+    ``words`` is the image ``Table.read()`` returns for the same stores in the same order.  ``stores`` counts the stores,
+    ``replaced`` those that overwrote an entry of another key, ``hits`` what ``table_hits`` counts, summed over the
+    ``solve_host`` calls the table was given to."""
+
+    def __init__(self, log2_entries):
+        if not L.SOLVE_TABLE_MIN_LOG2 <= int(log2_entries) <= L.SOLVE_TABLE_MAX_LOG2:
+            raise ValueError("log2_entries %r outside %d..%d" % (log2_entries, L.SOLVE_TABLE_MIN_LOG2, L.SOLVE_TABLE_MAX_LOG2))
+        self.log2_entries = int(log2_entries)
+        self.words = np.zeros(1 << self.log2_entries, dtype=np.uint64)
+        self.stores = 0
+        self.replaced = 0
+        self.hits = 0
+
+    def slot(self, key):
+        return ((key * _TT_HASH) & 0xFFFFFFFFFFFFFFFF) >> (64 - self.log2_entries)
+
+    def get(self, key, default=None):
+        w = int(self.words[self.slot(key)])
+        if w & _TT_KEY_MASK != key:
+            return default
+        return (w >> _TT_KIND_SHIFT) & 3, ((w >> _TT_SCORE_SHIFT) & 0x7f) - 64
+
+    def __setitem__(self, key, entry):
+        kind, score = entry
+        at = self.slot(key)
+        old = int(self.words[at])
+        self.stores += 1
+        self.replaced += 1 if old and old & _TT_KEY_MASK != key else 0
+        self.words[at] = np.uint64(key | ((score + 64) << _TT_SCORE_SHIFT) | (kind << _TT_KIND_SHIFT))
+
+
+def _popcount64(x):
+    x = np.asarray(x, dtype=np.uint64)
+    if hasattr(np, "bitwise_count"):
+        return np.bitwise_count(x).astype(np.int64)
+    x = x - ((x >> np.uint64(1)) & np.uint64(0x5555555555555555))
+    x = (x & np.uint64(0x3333333333333333)) + ((x >> np.uint64(2)) & np.uint64(0x3333333333333333))
+    x = (x + (x >> np.uint64(4))) & np.uint64(0x0F0F0F0F0F0F0F0F)
+    return ((x * np.uint64(0x0101010101010101)) >> np.uint64(56)).astype(np.int64)
+
+
+def entry_fields(words):
+    """Every non-zero word of a table image (``Table.read()``, ``HostTable.words``) taken apart, as ``EntryFields`` of
+    arrays: index (the word's slot), key, score, kind, the mover's stones, the occupied squares, color0, color1 and age.
+
+    The key is mover's stones + occupied squares + bottom row, so the 7-bit field of a column of height h is
+    ``f = 2^h + (the mover's stones in it)``: h = floor(log2 f), the mover's stones are f - 2^h, the occupied cells 2^h - 1.
+    The mover is x (color1) at odd ages.  A field of 0 belongs to no position: it decodes as an empty column, and
+    ``mine + occ + BOTTOM`` then differs from the key."""
+    words = np.asarray(words, dtype=np.uint64)
+    index = np.nonzero(words)[0]
+    w = words[index]
+    key = w & np.uint64(_TT_KEY_MASK)
+    score = ((w >> np.uint64(_TT_SCORE_SHIFT)) & np.uint64(0x7f)).astype(np.int64) - 64
+    kind = ((w >> np.uint64(_TT_KIND_SHIFT)) & np.uint64(3)).astype(np.int64)
+    top = np.array([0] + [1 << (f.bit_length() - 1) for f in range(1, 1 << H1)], dtype=np.uint64)    # 2^floor(log2 f)
+    mine = np.zeros_like(key)
+    occ = np.zeros_like(key)
+    for c in range(WIDTH):
+        f = (key >> np.uint64(H1 * c)) & np.uint64((1 << H1) - 1)
+        t = top[f.astype(np.int64)]
+        mine |= (f - t) << np.uint64(H1 * c)
+        occ |= (np.maximum(t, np.uint64(1)) - np.uint64(1)) << np.uint64(H1 * c)
+    age = _popcount64(occ)
+    odd = (age & 1) == 1
+    theirs = occ ^ (mine & occ)
+    return EntryFields(index, key, score, kind, mine, occ, np.where(odd, theirs, mine), np.where(odd, mine, theirs), age)
+
+
 class _Search:
-    """`table`: None, or a dict ``key -> (kind, score)`` -- the kernel's transposition table without its replacement."""
+    """`table`: None, a dict ``key -> (kind, score)`` -- the kernel's transposition table without its replacement -- or a
+    ``HostTable``, the kernel's table with it."""
 
     def __init__(self, budget, table=None):
         self.nodes = 0
@@ -202,7 +285,8 @@ def solve_host(board, node_budget=None, table=None, deep=False):
 
     deep=True is c4_solve_deep's table-free search (any number of empty squares, never TOO_DEEP).  table: a ``dict``, which
     implies deep -- the kernel's probe / store / bound logic on ``key -> (kind, score)`` entries; the dict may be shared by
-    any number of calls, the answer does not depend on what it holds, the node count does."""
+    any number of calls, the answer does not depend on what it holds, the node count does.  A ``HostTable`` in its place
+    adds the kernel's slots and replacement: one row at a time it holds, word for word, what one lane leaves in a ``Table``."""
     c0, c1 = (board.color if isinstance(board, Board) else board)
     c0, c1 = int(c0), int(c1)
     budget = DEFAULT_NODE_BUDGET if node_budget is None else int(node_budget)
@@ -224,6 +308,9 @@ def solve_host(board, node_budget=None, table=None, deep=False):
             score = s.node(mine, theirs, age, -42, 42)
         except _OverBudget:
             return HostAnswer(L.SOLVE_UNKNOWN, None, -1, None, s.nodes)
+        finally:
+            if isinstance(table, HostTable):
+                table.hits += s.hits
         nodes = s.nodes
     abs_score = -score if age & 1 else score
     outcome = 1.0 if abs_score > 0 else 0.0 if abs_score < 0 else 0.5
@@ -295,6 +382,13 @@ class Table:
 
     def clear(self):
         _check(L.load().c4_solve_table_clear(self.handle, None))
+
+    def read(self):
+        """The table's ``2 ** log2_entries`` words as a ``numpy.uint64`` array (c4_solve_table_read): every store of every
+        call that has returned is in it.  ``entry_fields`` takes it apart; ``HostTable.words`` has the same layout."""
+        out = np.empty(self.entries, dtype=np.uint64)
+        _check(L.load().c4_solve_table_read(self.handle, out.ctypes.data_as(L._u64p), out.size))
+        return out
 
     def close(self):
         if self._h is not None:

@@ -688,12 +688,16 @@ const char *c4_solve_last_error(void);
  * window (0 without a table).
  * c4_solve_table_create: log2_entries in 10..30 (8 bytes an entry), else C4_EINVAL; zero-filled, on `device`; the table
  * must be used on the device it was created on (else C4_EINVAL).  c4_solve_table_clear zero-fills on hip_stream and waits for it (a
- * matter of measurement, not of correctness).  Two calls that share a table may run concurrently. */
+ * matter of measurement, not of correctness).  Two calls that share a table may run concurrently.
+ * c4_solve_table_read copies all 2^log2_entries words to entries_host (n must be that count, else C4_EINVAL; a null argument
+ * likewise): it waits for the device first, so it sees every store of every solver call that has returned.  For audits of the
+ * table (an entry must be a true bound of its position); no search needs it. */
 #define C4_SOLVE_DEEP_MAX_EMPTIES  42
 typedef struct c4_solve_table c4_solve_table;
 int c4_solve_table_create(int device, int log2_entries, c4_solve_table **out);
 int c4_solve_table_destroy(c4_solve_table *table);
 int c4_solve_table_clear(c4_solve_table *table, void *hip_stream);
+int c4_solve_table_read(c4_solve_table *table, uint64_t *entries_host, int64_t n);
 int c4_solve_deep_dev(int device, void *hip_stream, c4_solve_table *table, const int64_t *boards_dev, int64_t n, int64_t node_budget,
                       int64_t nodes_per_launch, int8_t *status_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev,
                       int64_t *table_hits_dev);

@@ -135,8 +135,12 @@ def test_symbols_and_constants():
     assert (int(lo), int(hi)) == (L.SOLVE_TABLE_MIN_LOG2, L.SOLVE_TABLE_MAX_LOG2) == (10, 30)
     assert [int(x) for x in re.search(r"TT_LOWER = (\d), TT_UPPER = (\d), TT_EXACT = (\d);", src).groups()] == [
         solver._LOWER, solver._UPPER, solver._EXACT]
+    # the entry word and the slot function HostTable and entry_fields restate
+    assert "key * 0x%XULL) >> t.shift" % solver._TT_HASH in src and "TT_KEY_MASK = (1ULL << %d) - 1;" % solver._TT_KEY_BITS in src
+    assert "(uint64_t)(score + 64) << %d) | ((uint64_t)kind << %d)" % (solver._TT_SCORE_SHIFT, solver._TT_KIND_SHIFT) in src
     lib = L.load()
-    for name in ("c4_solve_table_create", "c4_solve_table_destroy", "c4_solve_table_clear", "c4_solve_deep_dev", "c4_solve_deep"):
+    for name in ("c4_solve_table_create", "c4_solve_table_destroy", "c4_solve_table_clear", "c4_solve_table_read", "c4_solve_deep_dev",
+                 "c4_solve_deep"):
         assert name in L.SIGNATURES and hasattr(lib, name) and re.search(r"\bint %s\(" % name, text)
     assert len(L.SIGNATURES["c4_solve_deep_dev"][1]) == 12 and len(L.SIGNATURES["c4_solve_deep"][1]) == 12
 
