@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/c4_engine.h"
@@ -217,6 +218,81 @@ struct Dev {
     double alpha, frac;
     uint64_t seed;
 };
+
+// ------------------------------------------------------------------------------------------
+// How a launch of the block and the split kernel starts and ends: slot states, the network's answers and the launch's counters
+// move between the Dev arrays and the workgroup's LDS.  (The wave and match kernels keep their own text, see there.)  DevT as in
+// tree_step, but handed over as a POINTER: a reference parameter is dereferenceable by type, the compiler then loads d->G ... ahead
+// of their guards and every split kernel has 3 more scalar spills.  Run by the whole workgroup; the caller synchronises.
+// ------------------------------------------------------------------------------------------
+struct SlotMap {   // slot p of the workgroup is engine slot first + p * stride (dense: {blockIdx.x * TS, 1})
+    int first, stride;
+    __device__ __forceinline__ int operator()(int p) const { return first + p * stride; }
+};
+
+template <class DevT>
+__device__ __forceinline__ SlotMem load_slot(DevT *d, int g)   // a slot past the engine's last is parked
+{
+    SlotMem m = {};
+    m.flags = SlotMem::pack(SLOT_PARKED, 0, 0);
+    if (g < d->G) {
+        m.root0 = d->root_c0[g]; m.root1 = d->root_c1[g]; m.leaf0 = d->leaf_c0[g]; m.leaf1 = d->leaf_c1[g];
+        m.gid = d->game_id[g]; m.sims = d->sims_done[g]; m.nalloc = d->n_alloc[g]; m.pend = d->pending[g];
+        m.pdepth = d->pending_depth[g]; m.pinfo = d->pending_info[g];
+        m.ply = d->ply[g]; m.flags = SlotMem::pack(d->state[g], d->has_leaf[g], d->need_root[g]);
+        m.root_w = *(const double *)(d->pool + (size_t)g * d->cap * (BLOCK_BYTES / 8));   // Rec::w of node 0
+    }
+    return m;
+}
+
+// (root_w needs no store: tree_step keeps node 0 of the pool current)
+template <int TS, class DevT>
+__device__ __forceinline__ void store_slots(DevT *d, const SlotMap slots, const SlotMem *smem)
+{
+    if (threadIdx.x < TS && slots(threadIdx.x) < d->G) {
+        const int g = slots(threadIdx.x);
+        const SlotMem m = smem[threadIdx.x];   // read whole before the first store
+        d->root_c0[g] = m.root0; d->root_c1[g] = m.root1; d->leaf_c0[g] = m.leaf0; d->leaf_c1[g] = m.leaf1;
+        d->game_id[g] = m.gid; d->sims_done[g] = m.sims; d->n_alloc[g] = m.nalloc; d->pending[g] = m.pend;
+        d->pending_depth[g] = m.pdepth; d->pending_info[g] = m.pinfo; d->need_root[g] = m.need_root();
+        d->ply[g] = m.ply; d->state[g] = m.state(); d->has_leaf[g] = m.has_leaf() ? 1 : 0;
+    }
+}
+
+// the network's answers (value, seven priors per slot) as the previous launch -- or c4_step's evaluator -- left them
+template <int TS, class DevT>
+__device__ __forceinline__ void load_answers(DevT *d, const SlotMap slots, const float *values, const float *priors,
+                                             float *s_val, float *s_pri)
+{
+    for (int i = threadIdx.x; i < TS * 8; i += c4net::NTHREADS) {
+        const int p = i >> 3, k = i & 7;
+        const int g = slots(p);
+        const bool ok = g < d->G;
+        if (k == 7) s_val[p] = ok ? values[g] : 0.0f;
+        else s_pri[p * 7 + k] = ok ? priors[(size_t)g * 7 + k] : 0.0f;
+    }
+}
+
+template <int TS, class DevT>
+__device__ __forceinline__ void store_answers(DevT *d, const SlotMap slots, float *values, float *priors,
+                                              const float *s_val, const float *s_pri)
+{
+    for (int i = threadIdx.x; i < TS * 8; i += c4net::NTHREADS) {
+        const int p = i >> 3, k = i & 7;
+        const int g = slots(p);
+        if (g < d->G) {
+            if (k == 7) values[g] = s_val[p];
+            else priors[(size_t)g * 7 + k] = s_pri[p * 7 + k];
+        }
+    }
+}
+
+// the launch's counters go to the row of the workgroup's first slot (integer sums: the host adds the rows up)
+template <class DevT>
+__device__ __forceinline__ void flush_stats(DevT *d, const SlotMap slots, const uint32_t *s_stats)
+{
+    if (threadIdx.x < N_STATS && slots.first < d->G) d->stats[(size_t)slots.first * N_STATS + threadIdx.x] += s_stats[threadIdx.x];
+}
 
 // ------------------------------------------------------------------------------------------
 // device helpers
@@ -1380,28 +1456,12 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_kernel(Dev d, c4n
     PathEntry (*s_path)[MAX_DEPTH] = reinterpret_cast<PathEntry (*)[MAX_DEPTH]>(&act[0][0]);
     Rec (*s_l1)[GROUP] = reinterpret_cast<Rec (*)[GROUP]>(&act[0][0] + sizeof(PathEntry) * MAX_DEPTH * TS / sizeof(_Float16));
     const int slot0 = blockIdx.x * TS;
+    const SlotMap slots{slot0, 1};
     const int wv = threadIdx.x >> 6;
     // ---- launch prologue: slot states and the pending network answers, global -> LDS
-    if (threadIdx.x < TS) {
-        const int p = threadIdx.x, g = slot0 + p;
-        SlotMem m = {};
-        m.flags = SlotMem::pack(SLOT_PARKED, 0, 0);
-        if (g < d.G) {
-            m.root0 = d.root_c0[g]; m.root1 = d.root_c1[g]; m.leaf0 = d.leaf_c0[g]; m.leaf1 = d.leaf_c1[g];
-            m.gid = d.game_id[g]; m.sims = d.sims_done[g]; m.nalloc = d.n_alloc[g]; m.pend = d.pending[g];
-            m.pdepth = d.pending_depth[g]; m.pinfo = d.pending_info[g];
-            m.ply = d.ply[g]; m.flags = SlotMem::pack(d.state[g], d.has_leaf[g], d.need_root[g]);
-            m.root_w = *(const double *)(d.pool + (size_t)g * d.cap * (BLOCK_BYTES / 8));   // Rec::w of node 0
-        }
-        smem[p] = m;
-    }
+    if (threadIdx.x < TS) smem[threadIdx.x] = load_slot(&d, slots(threadIdx.x));
     if (threadIdx.x < N_STATS) s_stats[threadIdx.x] = 0;
-    for (int i = threadIdx.x; i < TS * 8; i += NTHREADS) {   // answers of the previous launch
-        const int p = i >> 3, k = i & 7;
-        const bool ok = slot0 + p < d.G;
-        if (k == 7) s_val[p] = ok ? values[slot0 + p] : 0.0f;
-        else s_pri[p * 7 + k] = ok ? priors[(size_t)(slot0 + p) * 7 + k] : 0.0f;
-    }
+    load_answers<TS>(&d, slots, values, priors, s_val, s_pri);   // answers of the previous launch
     __syncthreads();
     unsigned long long t_tree = 0, t_net = 0, t_own = 0;   // diagnostic (C4_TREE_STAMPS=1)
     for (int step = 0; step < n_steps; ++step) {
@@ -1448,22 +1508,9 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_kernel(Dev d, c4n
         if (d.has_stamps) t_net += __builtin_amdgcn_s_memtime() - tc;
     }
     // ---- launch epilogue: LDS -> global (the next launch, c4_step, read-outs and the host see the Dev arrays)
-    if (threadIdx.x < TS && slot0 + threadIdx.x < d.G) {
-        const int p = threadIdx.x, g = slot0 + p;
-        const SlotMem m = smem[p];
-        d.root_c0[g] = m.root0; d.root_c1[g] = m.root1; d.leaf_c0[g] = m.leaf0; d.leaf_c1[g] = m.leaf1;
-        d.game_id[g] = m.gid; d.sims_done[g] = m.sims; d.n_alloc[g] = m.nalloc; d.pending[g] = m.pend;
-        d.pending_depth[g] = m.pdepth; d.pending_info[g] = m.pinfo; d.need_root[g] = m.need_root();
-        d.ply[g] = m.ply; d.state[g] = m.state(); d.has_leaf[g] = m.has_leaf() ? 1 : 0;
-    }
-    if (threadIdx.x < N_STATS) d.stats[(size_t)slot0 * N_STATS + threadIdx.x] += s_stats[threadIdx.x];   // the workgroup's row
-    for (int i = threadIdx.x; i < TS * 8; i += NTHREADS) {
-        const int p = i >> 3, k = i & 7;
-        if (slot0 + p < d.G) {
-            if (k == 7) values[slot0 + p] = s_val[p];
-            else priors[(size_t)(slot0 + p) * 7 + k] = s_pri[p * 7 + k];
-        }
-    }
+    store_slots<TS>(&d, slots, smem);
+    flush_stats(&d, slots, s_stats);
+    store_answers<TS>(&d, slots, values, priors, s_val, s_pri);
     if (d.has_stamps && blockIdx.x < 128 && (threadIdx.x & 63) == 0) {   // rows 2b: per-wave own tree work, 2b+1: phases
         unsigned long long *o = d.cold->stamps + blockIdx.x * 16;
         o[wv] = t_own;
@@ -1510,7 +1557,8 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_wave_kernel(const
     static_assert(OWN_PATH || (sizeof(PathEntry) * MAX_DEPTH + sizeof(Rec) * GROUP) * SPW <= sizeof(_Float16) * WBUF, "a wave's path stacks must fit its activation planes");
     const int slot0 = blockIdx.x * TS;
     const int wv = threadIdx.x >> 6;
-    // ---- launch prologue: slot states, pending answers and the MLP tables, global -> LDS
+    // ---- launch prologue: slot states, pending answers and the MLP tables, global -> LDS.  (This kernel and c4_match_wave_kernel keep
+    // their own prologue and epilogue text: with any of the shared launch helpers their step loops' scalar spills move.)
     if (threadIdx.x < TS) {
         const int p = threadIdx.x, g = slot0 + p;
         SlotMem m = {};
@@ -1657,7 +1705,7 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_match_wave_kernel(const De
     static_assert(OWN_PATH || (sizeof(PathEntry) * MAX_DEPTH + sizeof(Rec) * GROUP) * SPW <= sizeof(_Float16) * WBUF, "a wave's path stacks must fit its activation planes");
     const int slot0 = blockIdx.x * TS;
     const int wv = threadIdx.x >> 6;
-    // ---- launch prologue: as c4_selfplay_wave_kernel, plus the slots' player assignment
+    // ---- launch prologue: as c4_selfplay_wave_kernel (own text, see there), plus the slots' player assignment
     if (threadIdx.x < TS) {
         const int p = threadIdx.x, g = slot0 + p;
         SlotMem m = {};
@@ -1874,20 +1922,11 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
     // blockIdx.x + p * gridDim.x, so that a batch smaller than TS x CUs still puts work on EVERY CU (1,200 games -- the
     // reference's generation, config.py:64 -- are 4-5 slots on each of 256 CUs instead of 16 slots on 75 of them).
     const int wg_first = spread ? (int)blockIdx.x : (int)blockIdx.x * TS, wg_stride = spread ? (int)gridDim.x : 1;
-    auto gslot = [&](int p) -> int { return wg_first + p * wg_stride; };
+    const SlotMap slots{wg_first, wg_stride};
     // ---- launch prologue: slot states, pending answers and the MLP tables, global -> LDS
     if (threadIdx.x < TS) {
-        const int p = threadIdx.x, g = gslot(p);
-        SlotMem m = {};
-        m.flags = SlotMem::pack(SLOT_PARKED, 0, 0);
-        if (g < d.G) {
-            m.root0 = d.root_c0[g]; m.root1 = d.root_c1[g]; m.leaf0 = d.leaf_c0[g]; m.leaf1 = d.leaf_c1[g];
-            m.gid = d.game_id[g]; m.sims = d.sims_done[g]; m.nalloc = d.n_alloc[g]; m.pend = d.pending[g];
-            m.pdepth = d.pending_depth[g]; m.pinfo = d.pending_info[g];
-            m.ply = d.ply[g]; m.flags = SlotMem::pack(d.state[g], d.has_leaf[g], d.need_root[g]);
-            m.root_w = *(const double *)(d.pool + (size_t)g * d.cap * (BLOCK_BYTES / 8));   // Rec::w of node 0
-        }
-        smem[p] = m;
+        const int p = threadIdx.x;
+        const SlotMem m = smem[p] = load_slot(&d, slots(p));
         s_req[p] = m.has_leaf() ? REQ_ANSWERED : REQ_IDLE;   // a leaf carried over from the previous launch has its answer
     }
     if (threadIdx.x < N_STATS) s_stats[threadIdx.x] = 0;
@@ -1896,20 +1935,14 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
     if (threadIdx.x < 4) s_req[3 * TS + threadIdx.x] = 0;
 #endif
     if (threadIdx.x == 0) s_tree_done = 0;
-    for (int i = threadIdx.x; i < TS * 8; i += NTHREADS) {   // answers of the previous launch
-        const int p = i >> 3, k = i & 7;
-        const int g = gslot(p);
-        const bool ok = g < d.G;
-        if (k == 7) s_val[p] = ok ? values[g] : 0.0f;
-        else s_pri[p * 7 + k] = ok ? priors[(size_t)g * 7 + k] : 0.0f;
-    }
+    load_answers<TS>(&d, slots, values, priors, s_val, s_pri);   // answers of the previous launch
     for (int i = threadIdx.x; i < MLP_F4; i += NTHREADS) mlp[i] = nd.mlp[i];
     stage_bias_lds(nd, s_bias);
     if (W0Lds<MODE>::FRAGS > 1) stage_w0_lds(nd, s_w0);
     if (threadIdx.x < 64) build_tab16<WaveRow<MODE>::CS>(s_tab16, threadIdx.x);
     for (int i = threadIdx.x; i < TS * MAX_DEPTH; i += NTHREADS) {   // paths of leaves pending from the previous launch
         const int p = i / MAX_DEPTH, k = i - p * MAX_DEPTH;
-        if (gslot(p) < d.G) s_path[p][k] = d.path[(size_t)gslot(p) * MAX_DEPTH + k];
+        if (slots(p) < d.G) s_path[p][k] = d.path[(size_t)slots(p) * MAX_DEPTH + k];
     }
     __syncthreads();
     // Which slots a tree wave walks: the workgroup's ACTIVE slots, sorted by ply, dealt out in TW contiguous chunks of equal size
@@ -2120,25 +2153,11 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
     // ---- launch epilogue: LDS -> global
     for (int i = threadIdx.x; i < TS * MAX_DEPTH; i += NTHREADS) {   // paths of the leaves whose answers wait for the next launch
         const int p = i / MAX_DEPTH, k = i - p * MAX_DEPTH;
-        if (gslot(p) < d.G && smem[p].has_leaf()) d.path[(size_t)gslot(p) * MAX_DEPTH + k] = s_path[p][k];
+        if (slots(p) < d.G && smem[p].has_leaf()) d.path[(size_t)slots(p) * MAX_DEPTH + k] = s_path[p][k];
     }
-    if (threadIdx.x < TS && gslot(threadIdx.x) < d.G) {
-        const int p = threadIdx.x, g = gslot(p);
-        const SlotMem m = smem[p];
-        d.root_c0[g] = m.root0; d.root_c1[g] = m.root1; d.leaf_c0[g] = m.leaf0; d.leaf_c1[g] = m.leaf1;
-        d.game_id[g] = m.gid; d.sims_done[g] = m.sims; d.n_alloc[g] = m.nalloc; d.pending[g] = m.pend;
-        d.pending_depth[g] = m.pdepth; d.pending_info[g] = m.pinfo; d.need_root[g] = m.need_root();
-        d.ply[g] = m.ply; d.state[g] = m.state(); d.has_leaf[g] = m.has_leaf() ? 1 : 0;
-    }
-    if (threadIdx.x < N_STATS && wg_first < d.G) d.stats[(size_t)wg_first * N_STATS + threadIdx.x] += s_stats[threadIdx.x];   // the row of the workgroup's first slot
-    for (int i = threadIdx.x; i < TS * 8; i += NTHREADS) {
-        const int p = i >> 3, k = i & 7;
-        const int g = gslot(p);
-        if (g < d.G) {
-            if (k == 7) values[g] = s_val[p];
-            else priors[(size_t)g * 7 + k] = s_pri[p * 7 + k];
-        }
-    }
+    store_slots<TS>(&d, slots, smem);
+    flush_stats(&d, slots, s_stats);
+    store_answers<TS>(&d, slots, values, priors, s_val, s_pri);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2620,6 +2639,75 @@ struct Scratch {
     }
 };
 
+// ---- kernel dispatch: run-time choices (evaluator, net mode, position queue, slots per workgroup, tree waves) become the
+// kernels' template arguments here.  Only what these functions spell is instantiated.
+
+// f(std::integral_constant<int, V>{}) for the V among Vs that equals v, for the last of them if none does
+template <int V, int... Vs, class F>
+void with_constant(int v, F &&f)
+{
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_constant<Vs...>(v, f);
+}
+template <class F>
+void with_bool(bool v, F &&f)
+{
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+struct FusedArgs {   // what every launch of a fused self-play kernel passes on
+    c4net::NetDev nd;
+    float *values, *priors;
+    int n_steps;
+    hipStream_t st;
+};
+
+template <int TS, int MODE, int TW, bool QUEUE>
+void launch_split_kernel(c4_engine *e, const FusedArgs &a, dim3 grid, int spread)
+{
+    hipLaunchKernelGGL((c4_selfplay_split_kernel<TS, MODE, TW, QUEUE>), grid, dim3(c4net::NTHREADS), 0, a.st, e->d_dev, a.nd, a.values, a.priors, a.n_steps, spread);
+}
+
+template <int MODE, bool QUEUE>
+void launch_split(c4_engine *e, const FusedArgs &a)
+{
+    // the split kernel spreads a batch that would leave CUs without a workgroup over all of them (slot = workgroup + p x workgroups)
+    const int dense_wgs = (e->d.G + e->fused_slots - 1) / e->fused_slots;
+    const int spread = (!e->pack_dense && dense_wgs < e->cus && e->d.G > dense_wgs) ? 1 : 0;
+    const dim3 grid(spread ? std::min(e->cus, e->d.G) : dense_wgs);
+    if (e->fused_slots == 32) return launch_split_kernel<32, MODE, 4, QUEUE>(e, a, grid, spread);   // (a wave holds at most 8 slots: no fewer than 4 tree waves)
+    // (64-filter reference precision: four tree waves and four network waves at 16 and at 32 slots, nothing else)
+    if constexpr (MODE != c4net::NETMODE_F64_PRECISE) {
+        // tree waves of the split kernel: 4 (one per SIMD) for the 32-filter nets (f32x3: 230 M expansions/s against 222 M with
+        // 2 tree waves); the 64-filter forward is slow enough to want more network waves: 2 tree waves of 8 slots and 6
+        // network waves at 16 slots per CU (111 against 104 M)
+        // (the position-queue instantiations exist for the default split only: C4_SPLIT_TW is a tuning aid of self-play)
+        const int tw = (e->split_tw && !QUEUE) ? e->split_tw : (MODE == c4net::NETMODE_F64 ? 2 : 4);
+        if (tw == 2) return launch_split_kernel<16, MODE, 2, QUEUE>(e, a, grid, spread);
+        if constexpr (!QUEUE)
+            if (tw == 3) return launch_split_kernel<16, MODE, 3, QUEUE>(e, a, grid, spread);
+    }
+    launch_split_kernel<16, MODE, 4, QUEUE>(e, a, grid, spread);
+}
+
+template <int MODE, bool QUEUE>
+void launch_wave(c4_engine *e, const FusedArgs &a)
+{
+    const dim3 blk(c4net::NTHREADS);
+    if (e->fused_slots == 32) hipLaunchKernelGGL((c4_selfplay_wave_kernel<32, MODE, QUEUE>), dim3((e->d.G + 31) / 32), blk, 0, a.st, e->d_dev, a.nd, a.values, a.priors, a.n_steps);
+    else hipLaunchKernelGGL((c4_selfplay_wave_kernel<16, MODE, QUEUE>), dim3((e->d.G + 15) / 16), blk, 0, a.st, e->d_dev, a.nd, a.values, a.priors, a.n_steps);
+}
+
+template <bool QUEUE>
+void launch_block(c4_engine *e, const FusedArgs &a)
+{
+    const dim3 blk(c4net::NTHREADS);
+    if (e->fused_slots == 32) hipLaunchKernelGGL((c4_selfplay_kernel<32, QUEUE>), dim3((e->d.G + 31) / 32), blk, 0, a.st, e->d, a.nd, a.values, a.priors, a.n_steps);
+    else hipLaunchKernelGGL((c4_selfplay_kernel<16, QUEUE>), dim3((e->d.G + 15) / 16), blk, 0, a.st, e->d, a.nd, a.values, a.priors, a.n_steps);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2695,8 +2783,9 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
         e->cus = cus;
-        // 16 slots per workgroup while that fills the chip once (one workgroup per CU: its LDS), 32 beyond; a batch that does
-        // not fill TS x CUs slots is SPREAD over all CUs by the split kernel (see c4_selfplay_steps)
+        // 16 slots per workgroup while that fills the chip once (one workgroup per CU: its LDS), 32 beyond (the tree phase is
+        // latency bound, so its cost is shared by twice the slots; smaller batches keep 16 so that no CU stays idle); a batch
+        // that does not fill TS x CUs slots is SPREAD over all CUs by the split kernel (see launch_split)
         e->fused_slots = (cfg->n_slots > 16 * cus) ? 32 : 16;
         e->pack_dense = 0;
         if (const char *pk = getenv("C4_FUSED_PACK")) e->pack_dense = strcmp(pk, "dense") == 0;
@@ -2935,17 +3024,11 @@ int c4_step_range(c4_engine *e, const void *values_dev, const void *priors_dev, 
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
     const dim3 grid((slot_count + SLOTS_PER_BLOCK - 1) / SLOTS_PER_BLOCK), block(BLOCK);
     // (a position-queue engine runs the QUEUE instantiations; every other engine the kernels it always ran)
-#define C4_LAUNCH_STEP(EVAL)                                                                                                      \
-    do {                                                                                                                          \
-        if (e->is_queue) hipLaunchKernelGGL((c4_step_kernel<EVAL, true>), grid, block, 0, st, d, values_dev, priors_dev, planes_dev); \
-        else hipLaunchKernelGGL((c4_step_kernel<EVAL>), grid, block, 0, st, d, values_dev, priors_dev, planes_dev);                \
-    } while (0)
-    switch (e->cfg.eval_mode) {
-    case C4_EVAL_EXTERNAL_F32: C4_LAUNCH_STEP(C4_EVAL_EXTERNAL_F32); break;
-    case C4_EVAL_EXTERNAL_F64: C4_LAUNCH_STEP(C4_EVAL_EXTERNAL_F64); break;
-    default: C4_LAUNCH_STEP(C4_EVAL_CENTRE); break;
-    }
-#undef C4_LAUNCH_STEP
+    with_constant<C4_EVAL_EXTERNAL_F32, C4_EVAL_EXTERNAL_F64, C4_EVAL_CENTRE>(e->cfg.eval_mode, [&](auto eval) {
+        with_bool(e->is_queue, [&](auto queue) {
+            hipLaunchKernelGGL((c4_step_kernel<decltype(eval)::value, decltype(queue)::value>), grid, block, 0, st, d, values_dev, priors_dev, planes_dev);
+        });
+    });
     HIPCHK(e, hipGetLastError());
     e->launches += 1;
     return C4_OK;
@@ -2960,71 +3043,32 @@ int c4_selfplay_steps(c4_engine *e, c4_net *net, float *values_dev, float *prior
     c4net::NetDev nd = net->d;
     nd.stamps = nullptr;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
-    // 32 slots per workgroup once that still gives every CU a workgroup (the tree phase is latency bound,
-    // so its cost is shared by twice the slots); smaller batches keep 16 so that no CU stays idle
+    const FusedArgs a{nd, values_dev, priors_dev, (int)n_steps, st};
     if (e->fused_wave) {   // wave-autonomous variant; it reads the engine description from device memory
         if (memcmp(&e->d_uploaded, &e->d, sizeof(Dev)) != 0) {
             HIPCHK(e, hipMemcpyAsync(e->d_dev, &e->d, sizeof(Dev), hipMemcpyHostToDevice, st));
             HIPCHK(e, hipStreamSynchronize(st));   // the source is a member that may change right after this call
             e->d_uploaded = e->d;
         }
-        const dim3 g32((e->d.G + 31) / 32), g16((e->d.G + 15) / 16), blk(c4net::NTHREADS);
-        // tree waves of the split kernel: 4 (one per SIMD) for the 32-filter nets (f32x3: 230 M expansions/s against 222 M with
-        // 2 tree waves); the 64-filter forward is slow enough to want more network waves: 2 tree waves of 8 slots and 6
-        // network waves at 16 slots per CU (111 against 104 M)
-        // (the position-queue instantiations exist for the default split only: C4_SPLIT_TW is a tuning aid of self-play)
-        const int tw = (e->split_tw && !e->is_queue) ? e->split_tw : (nd.mode == c4net::NETMODE_F64 ? 2 : 4);
-        // the split kernel spreads a batch that would leave CUs without a workgroup over all of them (slot = workgroup + p x workgroups)
-        const int dense_wgs = (e->d.G + e->fused_slots - 1) / e->fused_slots;
-        const int spread = (!e->pack_dense && dense_wgs < e->cus && e->d.G > dense_wgs) ? 1 : 0;
-        const dim3 gsp(spread ? std::min(e->cus, e->d.G) : dense_wgs);
-#define C4_LAUNCH_SPLIT(TSV, MODE, TWV) hipLaunchKernelGGL((c4_selfplay_split_kernel<TSV, MODE, TWV>), gsp, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps, spread)
-#define C4_LAUNCH_SPLIT_Q(TSV, MODE, TWV) hipLaunchKernelGGL((c4_selfplay_split_kernel<TSV, MODE, TWV, true>), gsp, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps, spread)
-#define C4_LAUNCH_WAVE(MODE)                                                                                                       \
-    do {                                                                                                                           \
-        if (e->is_queue) {                                                                                                         \
-            if (e->fused_wave == 2) {                                                                                              \
-                if (e->fused_slots == 32) C4_LAUNCH_SPLIT_Q(32, MODE, 4);                                                          \
-                else if (tw == 2) C4_LAUNCH_SPLIT_Q(16, MODE, 2);                                                                  \
-                else C4_LAUNCH_SPLIT_Q(16, MODE, 4);                                                                               \
-            } else if (e->fused_slots == 32) hipLaunchKernelGGL((c4_selfplay_wave_kernel<32, MODE, true>), g32, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps); \
-            else hipLaunchKernelGGL((c4_selfplay_wave_kernel<16, MODE, true>), g16, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps); \
-        } else if (e->fused_wave == 2) {                                                                                           \
-            if (e->fused_slots == 32) C4_LAUNCH_SPLIT(32, MODE, 4);   /* (a wave holds at most 8 slots: no fewer than 4 tree waves) */ \
-            else if (tw == 2) C4_LAUNCH_SPLIT(16, MODE, 2);                                                                        \
-            else if (tw == 3) C4_LAUNCH_SPLIT(16, MODE, 3);                                                                        \
-            else C4_LAUNCH_SPLIT(16, MODE, 4);                                                                                     \
-        } else if (e->fused_slots == 32) hipLaunchKernelGGL((c4_selfplay_wave_kernel<32, MODE>), g32, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps); \
-        else hipLaunchKernelGGL((c4_selfplay_wave_kernel<16, MODE>), g16, blk, 0, st, e->d_dev, nd, values_dev, priors_dev, (int)n_steps); \
-    } while (0)
-        if (nd.mode == c4net::NETMODE_F64_PRECISE) {
-            // 24,768 B of planes per network wave: four network waves (99 KB) fit next to the tree state, eight forwards per
-            // workgroup (the wave-autonomous kernel) do not.  Four tree waves and four network waves at 16 and at 32 slots.
-            if (e->fused_wave != 2) {
-                set_err(e->err, "C4_FUSED_MODE=wave cannot hold the 64-filter reference-precision net (eight waves' planes exceed a CU's LDS); use the default split kernel");
-                return C4_ESTATE;
-            }
-            if (e->is_queue) {
-                if (e->fused_slots == 32) C4_LAUNCH_SPLIT_Q(32, c4net::NETMODE_F64_PRECISE, 4);
-                else C4_LAUNCH_SPLIT_Q(16, c4net::NETMODE_F64_PRECISE, 4);
-            } else if (e->fused_slots == 32) C4_LAUNCH_SPLIT(32, c4net::NETMODE_F64_PRECISE, 4);
-            else C4_LAUNCH_SPLIT(16, c4net::NETMODE_F64_PRECISE, 4);
-        } else if (nd.mode == c4net::NETMODE_F64) C4_LAUNCH_WAVE(c4net::NETMODE_F64);
-        else if (nd.mode == c4net::NETMODE_F32_PRECISE) C4_LAUNCH_WAVE(c4net::NETMODE_F32_PRECISE);
-        else C4_LAUNCH_WAVE(c4net::NETMODE_F32_F16);
-#undef C4_LAUNCH_WAVE
-#undef C4_LAUNCH_SPLIT_Q
-#undef C4_LAUNCH_SPLIT
+        // 24,768 B of planes per network wave: four network waves (99 KB) fit next to the tree state, eight forwards per
+        // workgroup (the wave-autonomous kernel) do not
+        if (nd.mode == c4net::NETMODE_F64_PRECISE && e->fused_wave != 2) {
+            set_err(e->err, "C4_FUSED_MODE=wave cannot hold the 64-filter reference-precision net (eight waves' planes exceed a CU's LDS); use the default split kernel");
+            return C4_ESTATE;
+        }
+        with_constant<c4net::NETMODE_F64_PRECISE, c4net::NETMODE_F64, c4net::NETMODE_F32_PRECISE, c4net::NETMODE_F32_F16>(nd.mode, [&](auto mode) {
+            with_bool(e->is_queue, [&](auto queue) {
+                constexpr int MODE = decltype(mode)::value;
+                constexpr bool QUEUE = decltype(queue)::value;
+                if (e->fused_wave == 2) launch_split<MODE, QUEUE>(e, a);
+                else if constexpr (MODE != c4net::NETMODE_F64_PRECISE) launch_wave<MODE, QUEUE>(e, a);
+            });
+        });
     } else if (nd.mode != c4net::NETMODE_F32_F16) {
         set_err(e->err, "C4_FUSED_MODE=block serves only the 32-filter fp16 net; use the default wave-autonomous kernel");
         return C4_ESTATE;
-    } else if (e->is_queue) {
-        if (e->fused_slots == 32) hipLaunchKernelGGL((c4_selfplay_kernel<32, true>), dim3((e->d.G + 31) / 32), dim3(c4net::NTHREADS), 0, st, e->d, nd, values_dev, priors_dev, (int)n_steps);
-        else hipLaunchKernelGGL((c4_selfplay_kernel<16, true>), dim3((e->d.G + 15) / 16), dim3(c4net::NTHREADS), 0, st, e->d, nd, values_dev, priors_dev, (int)n_steps);
-    } else if (e->fused_slots == 32)
-        hipLaunchKernelGGL(c4_selfplay_kernel<32>, dim3((e->d.G + 31) / 32), dim3(c4net::NTHREADS), 0, st, e->d, nd, values_dev, priors_dev, (int)n_steps);
-    else
-        hipLaunchKernelGGL(c4_selfplay_kernel<16>, dim3((e->d.G + 15) / 16), dim3(c4net::NTHREADS), 0, st, e->d, nd, values_dev, priors_dev, (int)n_steps);
+    } else if (e->is_queue) launch_block<true>(e, a);
+    else launch_block<false>(e, a);
     HIPCHK(e, hipGetLastError());
     e->launches += n_steps;
     return C4_OK;
@@ -3079,11 +3123,9 @@ int c4_match_steps(c4_engine *e, c4_net *net, int32_t net_index, float *values_d
     }
     const Dev *dk = e->d_match_dev + net_index;
     const dim3 grid((e->d.G + 15) / 16), blk(c4net::NTHREADS);
-#define C4_LAUNCH_MATCH(MODE) hipLaunchKernelGGL((c4_match_wave_kernel<16, MODE>), grid, blk, 0, st, dk, nd, values_dev, priors_dev, (int)n_steps, (const uint8_t *)e->match_side_o, (const uint8_t *)e->match_side_x, (int)net_index)
-    if (nd.mode == c4net::NETMODE_F64) C4_LAUNCH_MATCH(c4net::NETMODE_F64);
-    else if (nd.mode == c4net::NETMODE_F32_PRECISE) C4_LAUNCH_MATCH(c4net::NETMODE_F32_PRECISE);
-    else C4_LAUNCH_MATCH(c4net::NETMODE_F32_F16);
-#undef C4_LAUNCH_MATCH
+    with_constant<c4net::NETMODE_F64, c4net::NETMODE_F32_PRECISE, c4net::NETMODE_F32_F16>(nd.mode, [&](auto mode) {
+        hipLaunchKernelGGL((c4_match_wave_kernel<16, decltype(mode)::value>), grid, blk, 0, st, dk, nd, values_dev, priors_dev, (int)n_steps, (const uint8_t *)e->match_side_o, (const uint8_t *)e->match_side_x, (int)net_index);
+    });
     HIPCHK(e, hipGetLastError());
     e->launches += n_steps;
     return C4_OK;

@@ -193,6 +193,26 @@ def test_rows_do_not_depend_on_launches_cache_or_driver():
         assert (st["eval_cache_hits"] > 0) == hits, (what, st)
 
 
+@pytest.mark.parametrize("mode,slots,precision", [("wave", 16, "f16"), ("wave", 32, "f16"), ("wave", 16, "f32x3"),
+                                                  ("block", 16, "f16"), ("block", 32, "f16")])
+def test_older_fused_kernels_serve_a_queue(monkeypatch, mode, slots, precision):
+    """The position-queue twins of the wave-autonomous and the workgroup-synchronous kernel.  18 slots: the last workgroup is
+    ragged (2 of 16 slots, 18 of 32); one step per launch: every launch ends with leaves in flight, so the rows pass through
+    the kernels' launch prologue and epilogue all the time."""
+    from connect4_amd.analysis import run_queue
+    from connect4_amd.mcts import MCTSConfig
+    monkeypatch.setenv("C4_FUSED_MODE", mode)
+    monkeypatch.setenv("C4_FUSED_SLOTS", str(slots))
+    monkeypatch.setenv("C4_FUSED_PACK", "dense")
+    eng = run_queue(MCTSConfig(SIMS), positions_50(), evaluator(precision), n_slots=18, steps_per_launch=1)
+    try:
+        rows, st = eng.queue_results(), eng.stats()
+    finally:
+        eng.close()
+    same_rows(rows, reference_50(precision), "%s kernel, %d slots per workgroup, %s" % (mode, slots, precision))
+    assert st["moves"] == 50 and st["simulations"] == 50 * SIMS
+
+
 def test_tapes_are_indexed_by_position():
     """Root noise and sampled moves: drawn from np.random position by position as MCTS.make_moves draws them, row i and
     ply 0 of the tapes serve position i whichever slot searches it."""
