@@ -79,11 +79,12 @@ def _kind(evaluator):
 
 
 def run_queue(config: MCTSConfig, boards, evaluator, n_slots: Optional[int] = None, device: int = 0,
-              eval_cache_log2_entries: int = 0, steps_per_launch: int = 64, fused: Optional[bool] = None):
+              eval_cache_log2_entries: int = 0, steps_per_launch: int = 64, fused: Optional[bool] = None, on_launch=None):
     """Queue the positions and search them all; returns the Engine (every row finished, the caller closes it) for
     queue_results / queue_export.  The arguments are search_positions' and:
     fused: None = the fused kernels whenever the evaluator is a DeviceNetEvaluator over a FusedNet; False = the host-driven
     c4_step + forward loop on the same queue engine (same rows: which launch runs a simulation never changes a result).
+    on_launch: called with the Engine after every c4_selfplay_steps launch (e.g. to ask it for last_fused_kernel()).
     Root noise and sampled moves are drawn from np.random with the reference's calls, position by position, as
     MCTS.make_moves draws them, and reach the kernel as tapes indexed by position."""
     packed = pack_boards(boards)
@@ -137,7 +138,7 @@ def run_queue(config: MCTSConfig, boards, evaluator, n_slots: Optional[int] = No
                 if eng.stats()["active_slots"] == 0:
                     break
         elif use_fused:
-            _drive_fused(eng, dev_eval.net, max(1, int(steps_per_launch)))
+            _drive_fused(eng, dev_eval.net, max(1, int(steps_per_launch)), on_launch=on_launch)
         else:
             from .mcts import _Searcher
             s = _Searcher(config, evaluator, device)      # its step loops, on this engine
@@ -154,7 +155,7 @@ def run_queue(config: MCTSConfig, boards, evaluator, n_slots: Optional[int] = No
     return eng
 
 
-def _drive_fused(eng, net, steps_per_launch, launches_per_poll=4):
+def _drive_fused(eng, net, steps_per_launch, launches_per_poll=4, on_launch=None):
     """c4_selfplay_steps until every slot has parked: the launches self-play uses; the host only polls."""
     import ctypes as C
 
@@ -169,6 +170,8 @@ def _drive_fused(eng, net, steps_per_launch, launches_per_poll=4):
             for _ in range(launches_per_poll):
                 L.check(eng._lib.c4_selfplay_steps(eng._h, net._h, C.c_void_p(values.data_ptr()), C.c_void_p(priors.data_ptr()),
                                                    steps_per_launch, C.c_void_p(stream)), eng._h)
+                if on_launch is not None:
+                    on_launch(eng)
             if eng.stats()["active_slots"] == 0:
                 return
 

@@ -2515,6 +2515,10 @@ void set_err(char *dst, const char *fmt, ...)
     if (dst != g_err) { strncpy(g_err, dst, 511); g_err[511] = 0; }
 }
 
+enum { FUSED_NONE, FUSED_SPLIT, FUSED_WAVE, FUSED_BLOCK, FUSED_MATCH };   // the four fused kernel families
+// one fused launch as c4_debug_last_fused_kernel reports it; tw < 0 / queue < 0 where the family has no such template argument
+struct FusedLaunch { int family, ts, mode, tw, queue, spread, grid; };
+
 }  // namespace
 
 struct c4_engine {
@@ -2534,7 +2538,10 @@ struct c4_engine {
     int cus;              // compute units of the device
     int pack_dense;       // C4_FUSED_PACK=dense: consecutive slots per workgroup even when that leaves CUs idle (tests of ragged workgroups)
     int fused_wave;       // 1: wave-autonomous fused kernel (c4_selfplay_wave_kernel); 2: tree waves + network waves (c4_selfplay_split_kernel)
-    int split_tw;         // tuning aid (C4_SPLIT_TW=2|4): tree waves of the split kernel at 16 slots per workgroup; 0 = by net mode
+    int split_tw;         // tuning aid (C4_SPLIT_TW=2|3|4): tree waves of the split kernel at 16 slots per workgroup; 0 = by net mode
+    // the last fused launch the runtime accepted (c4_debug_last_fused_kernel): family FUSED_NONE before the first one.  The launch
+    // functions write it when they issue the launch; fused_launch_status puts the earlier record back if the launch was refused
+    FusedLaunch last_fused;
     int tape_games;
     double *tape_noise, *tape_u;
     // net-vs-net matches (c4_match_assign / c4_match_steps); n_match_nets = c4_config.reserved[0], 0 = none of this exists
@@ -2667,6 +2674,7 @@ struct FusedArgs {   // what every launch of a fused self-play kernel passes on
 template <int TS, int MODE, int TW, bool QUEUE>
 void launch_split_kernel(c4_engine *e, const FusedArgs &a, dim3 grid, int spread)
 {
+    e->last_fused = {FUSED_SPLIT, TS, MODE, TW, QUEUE, spread, (int)grid.x};
     hipLaunchKernelGGL((c4_selfplay_split_kernel<TS, MODE, TW, QUEUE>), grid, dim3(c4net::NTHREADS), 0, a.st, e->d_dev, a.nd, a.values, a.priors, a.n_steps, spread);
 }
 
@@ -2678,34 +2686,56 @@ void launch_split(c4_engine *e, const FusedArgs &a)
     const int spread = (!e->pack_dense && dense_wgs < e->cus && e->d.G > dense_wgs) ? 1 : 0;
     const dim3 grid(spread ? std::min(e->cus, e->d.G) : dense_wgs);
     if (e->fused_slots == 32) return launch_split_kernel<32, MODE, 4, QUEUE>(e, a, grid, spread);   // (a wave holds at most 8 slots: no fewer than 4 tree waves)
-    // (64-filter reference precision: four tree waves and four network waves at 16 and at 32 slots, nothing else)
-    if constexpr (MODE != c4net::NETMODE_F64_PRECISE) {
-        // tree waves of the split kernel: 4 (one per SIMD) for the 32-filter nets (f32x3: 230 M expansions/s against 222 M with
-        // 2 tree waves); the 64-filter forward is slow enough to want more network waves: 2 tree waves of 8 slots and 6
-        // network waves at 16 slots per CU (111 against 104 M)
-        // (the position-queue instantiations exist for the default split only: C4_SPLIT_TW is a tuning aid of self-play)
-        const int tw = (e->split_tw && !QUEUE) ? e->split_tw : (MODE == c4net::NETMODE_F64 ? 2 : 4);
+    // tree waves of the split kernel at 16 slots: 4 (one per SIMD) for the 32-filter nets (f32x3: 230 M expansions/s against 222 M
+    // with 2 tree waves); the 64-filter fp16 forward is slow enough to want more network waves: 2 tree waves of 8 slots and 6
+    // network waves per CU (111 against 104 M); 64-filter reference precision: four tree waves and four network waves at 16
+    // and at 32 slots, nothing else
+    constexpr int DEFAULT_TW = MODE == c4net::NETMODE_F64 ? 2 : 4;
+    // C4_SPLIT_TW is a tuning aid of self-play for the three modes that have a choice.  Only the branches spelled for a
+    // (MODE, QUEUE) pair are instantiated: a position-queue engine and the 64-filter reference-precision net get the default
+    // split and no other kernel (tests/fused_matrix.py lists every instantiation; tests/test_fused_matrix_host.py compares
+    // that list with the library)
+    if constexpr (!QUEUE && MODE != c4net::NETMODE_F64_PRECISE) {
+        const int tw = e->split_tw ? e->split_tw : DEFAULT_TW;
         if (tw == 2) return launch_split_kernel<16, MODE, 2, QUEUE>(e, a, grid, spread);
-        if constexpr (!QUEUE)
-            if (tw == 3) return launch_split_kernel<16, MODE, 3, QUEUE>(e, a, grid, spread);
+        if (tw == 3) return launch_split_kernel<16, MODE, 3, QUEUE>(e, a, grid, spread);
+        return launch_split_kernel<16, MODE, 4, QUEUE>(e, a, grid, spread);
+    } else {
+        launch_split_kernel<16, MODE, DEFAULT_TW, QUEUE>(e, a, grid, spread);
     }
-    launch_split_kernel<16, MODE, 4, QUEUE>(e, a, grid, spread);
 }
 
 template <int MODE, bool QUEUE>
 void launch_wave(c4_engine *e, const FusedArgs &a)
 {
     const dim3 blk(c4net::NTHREADS);
-    if (e->fused_slots == 32) hipLaunchKernelGGL((c4_selfplay_wave_kernel<32, MODE, QUEUE>), dim3((e->d.G + 31) / 32), blk, 0, a.st, e->d_dev, a.nd, a.values, a.priors, a.n_steps);
-    else hipLaunchKernelGGL((c4_selfplay_wave_kernel<16, MODE, QUEUE>), dim3((e->d.G + 15) / 16), blk, 0, a.st, e->d_dev, a.nd, a.values, a.priors, a.n_steps);
+    const int ts = e->fused_slots == 32 ? 32 : 16;
+    const dim3 grid((e->d.G + ts - 1) / ts);
+    e->last_fused = {FUSED_WAVE, ts, MODE, -1, QUEUE, 0, (int)grid.x};
+    if (ts == 32) hipLaunchKernelGGL((c4_selfplay_wave_kernel<32, MODE, QUEUE>), grid, blk, 0, a.st, e->d_dev, a.nd, a.values, a.priors, a.n_steps);
+    else hipLaunchKernelGGL((c4_selfplay_wave_kernel<16, MODE, QUEUE>), grid, blk, 0, a.st, e->d_dev, a.nd, a.values, a.priors, a.n_steps);
 }
 
 template <bool QUEUE>
 void launch_block(c4_engine *e, const FusedArgs &a)
 {
     const dim3 blk(c4net::NTHREADS);
-    if (e->fused_slots == 32) hipLaunchKernelGGL((c4_selfplay_kernel<32, QUEUE>), dim3((e->d.G + 31) / 32), blk, 0, a.st, e->d, a.nd, a.values, a.priors, a.n_steps);
-    else hipLaunchKernelGGL((c4_selfplay_kernel<16, QUEUE>), dim3((e->d.G + 15) / 16), blk, 0, a.st, e->d, a.nd, a.values, a.priors, a.n_steps);
+    const int ts = e->fused_slots == 32 ? 32 : 16;
+    const dim3 grid((e->d.G + ts - 1) / ts);
+    e->last_fused = {FUSED_BLOCK, ts, -1, -1, QUEUE, 0, (int)grid.x};
+    if (ts == 32) hipLaunchKernelGGL((c4_selfplay_kernel<32, QUEUE>), grid, blk, 0, a.st, e->d, a.nd, a.values, a.priors, a.n_steps);
+    else hipLaunchKernelGGL((c4_selfplay_kernel<16, QUEUE>), grid, blk, 0, a.st, e->d, a.nd, a.values, a.priors, a.n_steps);
+}
+
+// after a fused launch was issued: C4_OK, or the runtime's refusal -- then `before`, the record of the last launch that did
+// start, is put back, so that c4_debug_last_fused_kernel never names a kernel that did not run
+int fused_launch_status(c4_engine *e, const FusedLaunch &before, const char *what)
+{
+    const hipError_t r = hipGetLastError();
+    if (r == hipSuccess) return C4_OK;
+    e->last_fused = before;
+    set_err(e->err, "%s: the kernel launch failed: %s", what, hipGetErrorString(r));
+    return C4_EDEVICE;
 }
 
 }  // namespace
@@ -2741,6 +2771,31 @@ int c4_debug_stamps(c4_engine *e, unsigned long long *out)
 }
 
 const char *c4_last_error(const c4_engine *e) { return e ? e->err : g_err; }
+
+/* diagnostic: the fused kernel of the last c4_selfplay_steps / c4_match_steps launch, spelled as its instantiation (the template
+ * arguments the family has, in order: TS, MODE, TW, QUEUE) with the run-time packing and the grid, e.g.
+ * "c4_selfplay_split_kernel<16,1,3,false> spread=0 grid=3"; "" before the first such launch.  Returns the length written, or
+ * C4_EINVAL (null argument, or `cap` too small for the name and its terminator) */
+int c4_debug_last_fused_kernel(c4_engine *e, char *buf, int cap)
+{
+    if (!e || !buf || cap <= 0) return C4_EINVAL;
+    const auto &f = e->last_fused;
+    char name[96] = "", tail[48] = "";
+    const char *q = f.queue ? "true" : "false";
+    switch (f.family) {
+    case FUSED_SPLIT: snprintf(name, sizeof(name), "c4_selfplay_split_kernel<%d,%d,%d,%s>", f.ts, f.mode, f.tw, q); break;
+    case FUSED_WAVE: snprintf(name, sizeof(name), "c4_selfplay_wave_kernel<%d,%d,%s>", f.ts, f.mode, q); break;
+    case FUSED_BLOCK: snprintf(name, sizeof(name), "c4_selfplay_kernel<%d,%s>", f.ts, q); break;
+    case FUSED_MATCH: snprintf(name, sizeof(name), "c4_match_wave_kernel<%d,%d>", f.ts, f.mode); break;
+    default: break;
+    }
+    if (f.family != FUSED_NONE) snprintf(tail, sizeof(tail), " spread=%d grid=%d", f.spread, f.grid);
+    const int n = (int)(strlen(name) + strlen(tail));
+    if (n >= cap) { buf[0] = 0; set_err(e->err, "c4_debug_last_fused_kernel: the name needs %d bytes, the buffer has %d", n + 1, cap); return C4_EINVAL; }
+    memcpy(buf, name, strlen(name));
+    memcpy(buf + strlen(name), tail, strlen(tail) + 1);
+    return n;
+}
 
 int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
 {
@@ -2779,6 +2834,7 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
     e->device = device;
     e->stream = nullptr;
     e->launches = 0;
+    e->last_fused = {FUSED_NONE, 0, 0, -1, -1, 0, 0};
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
@@ -3044,6 +3100,7 @@ int c4_selfplay_steps(c4_engine *e, c4_net *net, float *values_dev, float *prior
     nd.stamps = nullptr;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
     const FusedArgs a{nd, values_dev, priors_dev, (int)n_steps, st};
+    const FusedLaunch before = e->last_fused;
     if (e->fused_wave) {   // wave-autonomous variant; it reads the engine description from device memory
         if (memcmp(&e->d_uploaded, &e->d, sizeof(Dev)) != 0) {
             HIPCHK(e, hipMemcpyAsync(e->d_dev, &e->d, sizeof(Dev), hipMemcpyHostToDevice, st));
@@ -3069,7 +3126,7 @@ int c4_selfplay_steps(c4_engine *e, c4_net *net, float *values_dev, float *prior
         return C4_ESTATE;
     } else if (e->is_queue) launch_block<true>(e, a);
     else launch_block<false>(e, a);
-    HIPCHK(e, hipGetLastError());
+    if (int rc = fused_launch_status(e, before, "c4_selfplay_steps")) return rc;
     e->launches += n_steps;
     return C4_OK;
 }
@@ -3123,10 +3180,12 @@ int c4_match_steps(c4_engine *e, c4_net *net, int32_t net_index, float *values_d
     }
     const Dev *dk = e->d_match_dev + net_index;
     const dim3 grid((e->d.G + 15) / 16), blk(c4net::NTHREADS);
+    const FusedLaunch before = e->last_fused;
     with_constant<c4net::NETMODE_F64, c4net::NETMODE_F32_PRECISE, c4net::NETMODE_F32_F16>(nd.mode, [&](auto mode) {
+        e->last_fused = {FUSED_MATCH, 16, decltype(mode)::value, -1, -1, 0, (int)grid.x};
         hipLaunchKernelGGL((c4_match_wave_kernel<16, decltype(mode)::value>), grid, blk, 0, st, dk, nd, values_dev, priors_dev, (int)n_steps, (const uint8_t *)e->match_side_o, (const uint8_t *)e->match_side_x, (int)net_index);
     });
-    HIPCHK(e, hipGetLastError());
+    if (int rc = fused_launch_status(e, before, "c4_match_steps")) return rc;
     e->launches += n_steps;
     return C4_OK;
 }

@@ -143,6 +143,16 @@ class Engine:
         self._check(self._lib.c4_match_steps(self._h, net._h, int(net_index), C.c_void_p(values.data_ptr()),
                                              C.c_void_p(priors.data_ptr()), int(n_steps), C.c_void_p(stream or 0)))
 
+    def last_fused_kernel(self):
+        """The fused kernel the last selfplay_steps / match_steps call launched, e.g.
+        "c4_selfplay_split_kernel<16,1,3,false> spread=0 grid=3" (c4_debug_last_fused_kernel); "" before the first one.
+        Host bookkeeping: nothing is launched or waited for."""
+        buf = C.create_string_buffer(128)
+        rc = self._lib.c4_debug_last_fused_kernel(self._h, buf, len(buf))
+        if rc < 0:
+            self._check(rc)
+        return buf.value.decode("ascii")
+
     # -- position queue (c4_queue_positions ...; Engine(..., stop_after_move=True, position_queue=True)) ------
     def queue_positions(self, color0, color1):
         """Queue len(color0) positions of any number for the engine's slots: slot i starts on position i, and a slot

@@ -135,11 +135,12 @@ def device_match_reason(players):
 DEFAULT_STEPS_PER_LAUNCH = 4096   # quanta per launch: an upper bound (a launch ends when its net's slots have all moved); tools/bench_match.py
 
 
-def play_device_games(players, games, n_steps=None, eval_cache_log2_entries=0, net_order=None, timeout_s=3600.0):
+def play_device_games(players, games, n_steps=None, eval_cache_log2_entries=0, net_order=None, timeout_s=3600.0, on_launch=None):
     """Play `games` -- (Board opening, index of the player moving o, index of the player moving x) -- one per engine slot
     inside the fused match kernel and return their GameData (training_game.py:42-67: boards, moves, float64 values and
     visit policies, result) in the order of `games`, plus the engine's final statistics.  net_order: the order in which
-    the nets are served each round (default 0, 1, ...); it and n_steps never change a game."""
+    the nets are served each round (default 0, 1, ...); it and n_steps never change a game.  on_launch: called with the
+    Engine after every c4_match_steps launch (e.g. to ask it for last_fused_kernel())."""
     import torch
     from . import _lib as L
     from .engine import Engine
@@ -172,6 +173,8 @@ def play_device_games(players, games, n_steps=None, eval_cache_log2_entries=0, n
             while True:
                 for k in order:
                     eng.match_steps(nets[k], k, values, priors, n_steps, stream)
+                    if on_launch is not None:
+                        on_launch(eng)
                 st = eng.stats()
                 if st["active_slots"] == 0:
                     break
@@ -198,7 +201,7 @@ class DeviceMatch:
     order as GameData (boards before each move, moves, float64 values, visit-count policies, result), and `stats`."""
 
     def __init__(self, display, player_1, player_2, plies: int = 0, switch: bool = False, n_steps=None,
-                 eval_cache_log2_entries: int = 0, net_order=None):
+                 eval_cache_log2_entries: int = 0, net_order=None, on_launch=None):
         reason = device_match_reason([player_1, player_2])
         if reason is not None:
             raise ValueError(reason)
@@ -215,12 +218,14 @@ class DeviceMatch:
         self.n_steps = n_steps
         self.eval_cache_log2_entries = eval_cache_log2_entries
         self.net_order = net_order
+        self.on_launch = on_launch
         self.records = None
         self.stats = None
 
     def play(self, agents=1):
         self.records, self.stats = play_device_games([self._player_1, self._player_2], self.games, self.n_steps,
-                                                     self.eval_cache_log2_entries, self.net_order)
+                                                     self.eval_cache_log2_entries, self.net_order,
+                                                     **({} if self.on_launch is None else {"on_launch": self.on_launch}))
         out = score_results([r.result.value for r in self.records], self.n, self.switch)
         if self.display:
             print("The results for {} vs {} are: {} wins, {} draws, {} losses, {:.3f} return".format(

@@ -560,6 +560,19 @@ int c4_debug_fused_net_stamps(c4_engine *e, unsigned long long *out);
  * C4_TREE_STAMPS=1, else C4_ESTATE. */
 int c4_debug_latency_stamps(c4_engine *e, unsigned long long *out);
 
+/* diagnostic: which fused kernel the last c4_selfplay_steps / c4_match_steps call launched, as the instantiation's name with
+ * the template arguments its family has (TS, MODE, TW, QUEUE in that order; MODE is the net's mode 0 fp16 32 filters, 1 f32x3,
+ * 2 fp16 64 filters, 3 f32x3w), the run-time slot packing and the grid, e.g.
+ *     "c4_selfplay_split_kernel<16,1,3,false> spread=0 grid=3"    "c4_selfplay_wave_kernel<32,2,true> spread=0 grid=2"
+ *     "c4_selfplay_kernel<16,false> spread=0 grid=3"              "c4_match_wave_kernel<16,2> spread=0 grid=1"
+ * and "" before the first such launch.  A launch that the runtime refused (the call returned C4_EDEVICE) is not recorded: the
+ * name stays that of the last launch that started.  Host bookkeeping only: no device work, no synchronisation.  Returns the length written
+ * (without the terminator), or C4_EINVAL for a null argument or a `cap` that cannot hold the name and its terminator (128
+ * bytes always can).  The environment variables that choose among the kernels (C4_FUSED_MODE, C4_FUSED_SLOTS, C4_SPLIT_TW)
+ * are ignored where they do not apply; this call is how a caller learns what ran.  tests/fused_matrix.py lists every
+ * instantiation and how to reach it.  (An addition: C4_ABI_VERSION stays.) */
+int c4_debug_last_fused_kernel(c4_engine *e, char *buf, int cap);
+
 /* ---- train step (the reference: ModelWrapper.train, neural/pytorch/model.py:200-240) ----------
  * The convolutions, linear layers, losses and SGD of the train step are stock PyTorch-ROCm; batch normalisation in
  * training mode -- half of a stock step's GPU time at this net's shape -- is the library's own, fused with the residual add

@@ -1,4 +1,7 @@
 """Helpers shared by the GPU parity tests: drive the HIP engine with a host-side evaluator."""
+import functools
+from copy import copy
+
 import numpy as np
 
 
@@ -88,3 +91,67 @@ def drive_external(eng, eval_fn, dtype, max_steps=10_000_000):
     else:
         raise RuntimeError("engine did not finish")
     return n_evals
+
+
+# ---------------------------------------------------------------- position-queue rows
+ROW_FIELDS = ("state", "move", "value", "root_visits", "root_value_sum", "child_visits", "child_value_sum", "child_status", "root_prior",
+              "values_policy", "color0", "color1", "expansions", "simulations")
+
+
+def same_rows(got, want, what=""):
+    """Two lists of c4_root_result / c4_search_result rows, field for field and bit for bit."""
+    assert len(got) == len(want)
+    for i in range(len(want)):
+        a, b = root_fields(got[i]), root_fields(want[i])
+        for f in ROW_FIELDS:
+            assert a[f] == b[f], "%s row %d: %s differs: %r != %r" % (what, i, f, a[f], b[f])
+
+
+@functools.lru_cache(maxsize=None)
+def _positions_50():
+    from connect4_amd.board import Board
+    out = []
+    for a in range(7):
+        for b in range(7):
+            bd = Board()
+            bd.make_move(a)
+            bd.make_move(b)
+            out.append(bd)
+    mid = Board()
+    for m in (3, 3, 2, 4, 4, 2, 5, 1, 3, 0, 6, 6, 1):
+        mid.make_move(m)
+    assert mid.result is None
+    return tuple(out + [mid])
+
+
+def positions_50():
+    """The 49 two-ply openings and one mid-game position (the same Boards on every call: nobody moves on them)."""
+    return list(_positions_50())
+
+
+# ---------------------------------------------------------------- net-vs-net matches
+def game_key(gd):
+    """A game (GameData) as comparable Python values: moves, float64 values (None where the reference has None), the
+    policies' bits, the boards before each move and the result."""
+    return ([int(m) for m in gd.moves], list(gd.values), [np.asarray(p, dtype=np.float64).tobytes() for p in gd.priors],
+            [b.to_int_tuple() for b in gd.boards], gd.result.value)
+
+
+def host_lockstep_games(players, games):
+    """`games` -- (opening Board, index of the player moving o, index of the player moving x) -- ply by ply on the host
+    lock-step path: at every ply the boards where players[k] is to move are one MCTS.make_moves batch.  Returns GameData in
+    the order of `games`."""
+    from connect4_amd.training_game import GameData
+    boards = [copy(g[0]) for g in games]
+    out = [GameData() for _ in games]
+    while any(b.result is None for b in boards):
+        for k, p in enumerate(players):
+            idx = [i for i, b in enumerate(boards) if b.result is None and games[i][1 + b.age % 2] == k]
+            if not idx:
+                continue
+            before = [copy(boards[i]) for i in idx]
+            for i, b0, (move, value, tree) in zip(idx, before, p.make_moves([boards[i] for i in idx])):
+                out[i].add_move(b0, move, value, tree.get_values_policy())
+    for gd, b in zip(out, boards):
+        gd.result = b.result
+    return out

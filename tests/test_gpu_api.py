@@ -278,22 +278,42 @@ def test_split_kernel_other_nets_play_the_same_games(monkeypatch, kind):
     net.close()
 
 
-@pytest.mark.parametrize("precision", ["f32x3", "f16"])
+@pytest.mark.parametrize("precision", ["f32x3", "f16", "64f", "f32x3w"])
 def test_spread_workgroups_play_the_same_games(monkeypatch, precision):
     """A batch that does not fill 16 slots on every CU is spread over all CUs by the split kernel (slot = workgroup + p x
     workgroups: 1,200 games -- the reference's generation, config.py:64 -- are 4-5 slots on each of 256 CUs instead of 16
-    slots on 75 of them).  Same seed => the games of the dense packing, id by id; also with three tree waves."""
+    slots on 75 of them).  Same seed => the games of the dense packing, id by id; also with three tree waves.  The
+    64-filter nets (fp16 storage: two tree waves by default, and four; reference precision: four and nothing else) on
+    CUs + 32 slots: workgroups of one slot and of two.  The packing is a run-time argument of the kernel, so the engine's
+    record of the launch (Engine.last_fused_kernel) must say spread=1 for the spread runs and spread=0 for the dense ones."""
+    import torch
     from connect4_amd.config import MCTSConfig
     from connect4_amd.fused_net import FusedNet
-    from connect4_amd.net import random_init_state_dict
+    from connect4_amd.net import NetConfig, random_init_state_dict
     from connect4_amd.selfplay import SelfPlay
-    net = FusedNet(random_init_state_dict(seed=0), precision=precision)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if precision in ("64f", "f32x3w"):
+        net = FusedNet(random_init_state_dict(NetConfig(filters=64, n_fc_layers=6, n_residuals=2), seed=2),
+                       precision="f16" if precision == "64f" else "f32x3w")
+        mode, slots, n_games = (2 if precision == "64f" else 3), cus + 32, cus + 72
+        runs = (("dense", None), ("spread", None)) + ((("spread", "4"), ("dense", "4")) if precision == "64f" else ())
+        default_tw = 2 if precision == "64f" else 4
+    else:
+        net = FusedNet(random_init_state_dict(seed=0), precision=precision)
+        mode, slots, n_games = (1 if precision == "f32x3" else 0), 600, 700
+        runs = (("dense", "4"), ("spread", "4"), ("spread", "3"), ("dense", "3"))
+        default_tw = 4
     cfg = MCTSConfig.self_play(32)
     out = []
-    for pack, tw in (("dense", "4"), ("spread", "4"), ("spread", "3"), ("dense", "3")):
+    monkeypatch.delenv("C4_FUSED_MODE", raising=False)
+    monkeypatch.delenv("C4_FUSED_SLOTS", raising=False)
+    for pack, tw in runs:
         monkeypatch.setenv("C4_FUSED_PACK", pack)
-        monkeypatch.setenv("C4_SPLIT_TW", tw)
-        sp = SelfPlay(net, 600, cfg, seed=9, games_target=700, record_capacity_games=700, use_graph=False,
+        if tw is None:
+            monkeypatch.delenv("C4_SPLIT_TW", raising=False)
+        else:
+            monkeypatch.setenv("C4_SPLIT_TW", tw)
+        sp = SelfPlay(net, slots, cfg, seed=9, games_target=n_games, record_capacity_games=n_games, use_graph=False,
                       fused_loop=True, steps_per_launch=8)
         for _ in range(2000):
             sp.run_steps(32)
@@ -301,11 +321,18 @@ def test_spread_workgroups_play_the_same_games(monkeypatch, precision):
                 break
         games = sorted(sp.drain(), key=lambda g: g.game_id)
         st = sp.stats()
+        launched = sp.engine.last_fused_kernel()
         sp.close()
-        assert len(games) == 700 and st["bad_evals"] == 0 and st["dropped_games"] == 0
+        # 16 slots per workgroup: dense packing fills (slots + 15) // 16 workgroups, fewer than there are CUs; spread over
+        # min(CUs, slots) workgroups
+        assert slots <= 16 * cus and (slots + 15) // 16 < cus
+        assert launched == "c4_selfplay_split_kernel<16,%d,%s,false> spread=%d grid=%d" % (
+            mode, tw or default_tw, pack == "spread", min(cus, slots) if pack == "spread" else (slots + 15) // 16)
+        assert len(games) == n_games and st["bad_evals"] == 0 and st["dropped_games"] == 0
         out.append(([(g.game_id, g.moves, g.result.value, g.values, [list(p) for p in g.priors]) for g in games],
                     {k: st[k] for k in ("simulations", "expansions", "moves", "games_finished", "terminal_sims", "leaf_evals")}))
-    assert out[0] == out[1] == out[2] == out[3]
+    for other in out[1:]:
+        assert out[0] == other
     net.close()
 
 

@@ -2,11 +2,10 @@
 must be those of the host lock-step path (one MCTS.make_moves search per ply, the path test_gpu_api.py pins to the
 oracle), move for move and bit for bit, whatever the launch length, the order the nets are served in, the workgroup
 shape or the evaluation caches do.  Every configuration here is deterministic (no root noise, no sampled moves)."""
-from copy import copy
-
-import numpy as np
 import pytest
 
+from gpu_helpers import game_key as key_of
+from gpu_helpers import host_lockstep_games as host_games
 from net_models import stressed_state_dict
 
 pytestmark = pytest.mark.gpu
@@ -43,32 +42,6 @@ def _close_players():
         p.evaluator.net.close()
     _PLAYERS.clear()
     _HOST.clear()
-
-
-def key_of(gd):
-    """A game as comparable Python values: moves, float64 values (None where the reference has None), the policies' bits,
-    the boards before each move and the result."""
-    return ([int(m) for m in gd.moves], list(gd.values), [np.asarray(p, dtype=np.float64).tobytes() for p in gd.priors],
-            [b.to_int_tuple() for b in gd.boards], gd.result.value)
-
-
-def host_games(players, games):
-    """The same games ply by ply on the host lock-step path: at every ply the boards where players[k] is to move are one
-    MCTS.make_moves batch.  Returns GameData in the order of `games`."""
-    from connect4_amd.training_game import GameData
-    boards = [copy(g[0]) for g in games]
-    out = [GameData() for _ in games]
-    while any(b.result is None for b in boards):
-        for k, p in enumerate(players):
-            idx = [i for i, b in enumerate(boards) if b.result is None and games[i][1 + b.age % 2] == k]
-            if not idx:
-                continue
-            before = [copy(boards[i]) for i in idx]
-            for i, b0, (move, value, tree) in zip(idx, before, p.make_moves([boards[i] for i in idx])):
-                out[i].add_move(b0, move, value, tree.get_values_policy())
-    for gd, b in zip(out, boards):
-        gd.result = b.result
-    return out
 
 
 _HOST = {}

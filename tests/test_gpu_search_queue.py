@@ -5,13 +5,11 @@ bit -- whatever the number of slots, the kernel, the launch length or the evalua
 import numpy as np
 import pytest
 
-from gpu_helpers import random_undecided_positions, root_fields
+from gpu_helpers import positions_50, random_undecided_positions, same_rows
 from net_models import stressed_state_dict
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("state", "move", "value", "root_visits", "root_value_sum", "child_visits", "child_value_sum", "child_status", "root_prior",
-          "values_policy", "color0", "color1", "expansions", "simulations")
 _CACHE = {}
 
 
@@ -28,14 +26,6 @@ def _close_nets():
         if k[0] == "net":
             v.net.close()
     _CACHE.clear()
-
-
-def same_rows(got, want, what=""):
-    assert len(got) == len(want)
-    for i in range(len(want)):
-        a, b = root_fields(got[i]), root_fields(want[i])
-        for f in FIELDS:
-            assert a[f] == b[f], "%s row %d: %s differs: %r != %r" % (what, i, f, a[f], b[f])
 
 
 # ---------------------------------------------------------------- centre evaluator against the oracle
@@ -126,26 +116,6 @@ def evaluator(precision="f32x3", filters=32):
     from connect4_amd.net import NetConfig
     return once(("net", precision, filters), lambda: DeviceNetEvaluator(FusedNet(
         stressed_state_dict(NetConfig(filters=filters, n_residuals=1, n_fc_layers=1), seed=131), precision=precision)))
-
-
-def positions_50():
-    """The 49 two-ply openings and one mid-game position."""
-    from connect4_amd.board import Board
-
-    def make():
-        out = []
-        for a in range(7):
-            for b in range(7):
-                bd = Board()
-                bd.make_move(a)
-                bd.make_move(b)
-                out.append(bd)
-        mid = Board()
-        for m in (3, 3, 2, 4, 4, 2, 5, 1, 3, 0, 6, 6, 1):
-            mid.make_move(m)
-        assert mid.result is None
-        return out + [mid]
-    return once(("positions", 50), make)
 
 
 def one_slot_path(cfg, ev, boards, seed=None):
