@@ -2804,6 +2804,12 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
     if (cfg->abi_version != C4_ABI_VERSION) { set_err(g_err, "ABI version mismatch: caller %d, library %d", cfg->abi_version, C4_ABI_VERSION); return C4_EINVAL; }
     if (cfg->n_slots <= 0 || cfg->simulations <= 0 || cfg->pb_c_base <= 0) { set_err(g_err, "n_slots, simulations and pb_c_base must be positive"); return C4_EINVAL; }
     if (cfg->eval_mode < 0 || cfg->eval_mode > 2 || cfg->rng_mode < 0 || cfg->rng_mode > 1 || cfg->planes_dtype < 0 || cfg->planes_dtype > 2) { set_err(g_err, "bad eval_mode / rng_mode / planes_dtype"); return C4_EINVAL; }
+    // A score that is NaN poisons every comparison of the argmax (an all-NaN group has no winner): evaluator answers are made
+    // finite in the kernels, the configuration's doubles here.  inf * a zero prior, a NaN or negative Gamma shape and a mixing
+    // weight outside [0,1] are the ways a config reaches one.
+    if (!std::isfinite(cfg->pb_c_init)) { set_err(g_err, "pb_c_init = %g is not finite", cfg->pb_c_init); return C4_EINVAL; }
+    if (!std::isfinite(cfg->root_dirichlet_alpha) || cfg->root_dirichlet_alpha < 0.0) { set_err(g_err, "root_dirichlet_alpha = %g must be finite and >= 0", cfg->root_dirichlet_alpha); return C4_EINVAL; }
+    if (!(cfg->root_exploration_fraction >= 0.0 && cfg->root_exploration_fraction <= 1.0)) { set_err(g_err, "root_exploration_fraction = %g must lie in [0,1]", cfg->root_exploration_fraction); return C4_EINVAL; }
     // every evaluated node takes one 8-slot block; evaluations per move <= simulations + 1
     const uint64_t cap = (uint64_t)GROUP * ((uint64_t)cfg->simulations + 3);
     if (cap > (1u << 22)) { set_err(g_err, "simulations=%d exceeds the 22-bit node index (max %d)", cfg->simulations, (1 << 19) - 3); return C4_ECAPACITY; }
@@ -3052,6 +3058,14 @@ int c4_set_tapes(c4_engine *e, const double *gamma_noise, const double *uniforms
 {
     if (!e || n_games <= 0 || !gamma_noise || !uniforms) { if (e) set_err(e->err, "c4_set_tapes: bad argument"); return C4_EINVAL; }
     if (!e->d.rng_tape) { set_err(e->err, "engine was not created with C4_RNG_TAPE"); return C4_ESTATE; }
+    // checked before anything is freed or uploaded: a refused tape leaves the engine as it was
+    for (size_t i = 0, m = (size_t)42 * 7 * (size_t)n_games; i < m; ++i)
+        if (!(gamma_noise[i] >= 0.0) || !std::isfinite(gamma_noise[i])) {
+            set_err(e->err, "c4_set_tapes: gamma_noise[%zu][%zu][%zu] = %g is negative or not finite", i / (42 * 7), i / 7 % 42, i % 7, gamma_noise[i]);
+            return C4_EINVAL;
+        }
+    for (size_t i = 0, m = (size_t)42 * (size_t)n_games; i < m; ++i)
+        if (uniforms[i] != uniforms[i]) { set_err(e->err, "c4_set_tapes: uniforms[%zu][%zu] is NaN", i / 42, i % 42); return C4_EINVAL; }
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipDeviceSynchronize());
     if (e->tape_noise) (void)hipFree(e->tape_noise);

@@ -167,7 +167,13 @@ typedef struct {
 
 /* -- lifecycle ------------------------------------------------------------------------------- */
 /* Replaces constructing MCTS(name, MCTSConfig, evaluator) (mcts.py:70-76) + the game_pool /
- * InferenceServer scaffolding (game_pool.py:15-42, inference_server.py:15-63). */
+ * InferenceServer scaffolding (game_pool.py:15-42, inference_server.py:15-63).
+ * The config's doubles are checked, because a PUCT score that is NaN has no place in the argmax (evaluator answers are
+ * made finite for the same reason, c4_stats.bad_evals): C4_EINVAL with a message for a pb_c_init that is not finite
+ * (inf times a zero prior), a root_dirichlet_alpha that is not finite or negative (the Gamma shape of the in-kernel RNG),
+ * and a root_exploration_fraction that is not finite or outside [0, 1].  Negative pb_c_init and any pb_c_base >= 1 are
+ * served.  (With C4_EVAL_EXTERNAL_F32 the exploration factor is rounded to float32, as the reference's is: keep pb_c_init
+ * inside float32's range.)  (A stricter check, not a new layout: C4_ABI_VERSION stays.) */
 int c4_engine_create(const c4_config *cfg, int device, c4_engine **out);
 int c4_engine_destroy(c4_engine *e);
 const char *c4_last_error(const c4_engine *e /* may be NULL */);
@@ -182,7 +188,12 @@ int c4_clear_eval_cache(c4_engine *e);
 int c4_reset(c4_engine *e, const uint64_t *color0, const uint64_t *color1, int32_t n_active);
 
 /* C4_RNG_TAPE: gamma_noise[game][ply][7] raw Gamma(alpha,1) draws (mcts.py:175-177) and
- * uniforms[game][ply] (the one uniform np.random.choice consumes, tree.py:80). `n_games` rows. */
+ * uniforms[game][ply] (the one uniform np.random.choice consumes, tree.py:80). `n_games` rows.
+ * A Gamma draw that is negative or not finite, or a uniform that is NaN (a negative uniform means "no sampling: take
+ * best_move"), is C4_EINVAL and the engine stays as it was, its earlier tapes included.
+ * THE CALLER'S OBLIGATION: a row used at a root must not sum to zero over that root's legal columns.  Which columns are
+ * legal depends on the position, so this call cannot know; the reference divides 0 / 0 there too (mcts.py:178, 197-202),
+ * and the NaN prior that follows has no defined search. */
 int c4_set_tapes(c4_engine *e, const double *gamma_noise, const double *uniforms, int32_t n_games);
 
 /* -- the hot path --------------------------------------------------------------------------- */

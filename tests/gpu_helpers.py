@@ -65,9 +65,11 @@ def root_fields(r):
 
 def drive_external(eng, eval_fn, dtype, max_steps=10_000_000):
     """Run an EXTERNAL_* engine to completion with a Python evaluator (c0,c1)->(value, prior[7]).
-    Mirrors how evaluators.py:18-25 serves mcts.py:130, one leaf per slot per step."""
+    Mirrors how evaluators.py:18-25 serves mcts.py:130, one leaf per slot per step.  eval_fn may be a list with one
+    evaluator per slot (searches of different evaluators side by side in one engine)."""
     import torch
     G = eng.n_slots
+    per_slot = isinstance(eval_fn, (list, tuple))
     tdt = torch.float32 if dtype == np.float32 else torch.float64
     values = torch.zeros(G, dtype=tdt, device="cuda")
     priors = torch.zeros(G, 7, dtype=tdt, device="cuda")
@@ -81,7 +83,7 @@ def drive_external(eng, eval_fn, dtype, max_steps=10_000_000):
             if eng.stats()["active_slots"] == 0:
                 break
         for g in np.nonzero(has)[0]:
-            v, p = eval_fn(c0[g], c1[g])
+            v, p = (eval_fn[g] if per_slot else eval_fn)(c0[g], c1[g])
             hv[g] = v
             hp[g] = p
             n_evals += 1

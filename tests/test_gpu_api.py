@@ -534,3 +534,67 @@ def test_wide_net_runs_on_the_fused_kernel(oracle):
     for r in recs[:5]:
         replay_game(oracle_config(cfg), sp.engine, wide, r, noise[r.game_id], u[r.game_id])
     sp.close()
+
+
+CONFIG_REFUSED = [dict(pb_c_init=float("inf")), dict(pb_c_init=float("-inf")), dict(pb_c_init=float("nan")),
+                  dict(root_dirichlet_alpha=float("nan")), dict(root_dirichlet_alpha=float("inf")), dict(root_dirichlet_alpha=-0.3),
+                  dict(root_exploration_fraction=float("nan")), dict(root_exploration_fraction=float("inf")),
+                  dict(root_exploration_fraction=-0.25), dict(root_exploration_fraction=1.5)]
+
+
+@pytest.mark.parametrize("bad", CONFIG_REFUSED, ids=lambda d: "%s=%s" % next(iter(d.items())))
+def test_engine_create_refuses_doubles_that_can_make_a_score_nan(bad):
+    """A NaN score has no place in the argmax, so c4_engine_create refuses the configurations that can produce one (in
+    every evaluator and RNG mode); return codes only, nothing is stepped."""
+    from connect4_amd import _lib as L
+    from connect4_amd.engine import Engine
+    base = dict(pb_c_init=1.25, root_dirichlet_alpha=0.3, root_exploration_fraction=0.25)
+    for eval_mode in (L.EVAL_EXTERNAL_F32, L.EVAL_EXTERNAL_F64, L.EVAL_CENTRE):
+        for rng_mode in (L.RNG_PHILOX, L.RNG_TAPE):
+            with pytest.raises(L.EngineError) as ei:
+                Engine(4, 16, eval_mode=eval_mode, rng_mode=rng_mode, stop_after_move=True, **dict(base, **bad))
+            assert ei.value.code == L.EINVAL
+
+
+def test_engine_create_accepts_the_edges_of_the_config_ranges():
+    from connect4_amd import _lib as L
+    from connect4_amd.engine import Engine
+    for kw in (dict(pb_c_init=-0.5), dict(pb_c_init=0.0), dict(pb_c_init=9999.0), dict(pb_c_base=1), dict(pb_c_base=2 ** 31 - 1),
+               dict(root_dirichlet_alpha=0.0, root_exploration_fraction=1.0), dict(root_dirichlet_alpha=0.3, root_exploration_fraction=0.0),
+               dict(root_dirichlet_alpha=0.3, root_exploration_fraction=1.0), dict(root_dirichlet_alpha=1e-3, root_exploration_fraction=0.5)):
+        Engine(4, 16, eval_mode=L.EVAL_CENTRE, rng_mode=L.RNG_TAPE, stop_after_move=True, **kw).close()
+
+
+def test_set_tapes_refuses_draws_that_cannot_be_gamma_draws():
+    """A negative or non-finite Gamma draw, or a NaN uniform, is C4_EINVAL and the engine keeps the tapes it had: the search
+    that follows is the one the good tapes give."""
+    from connect4_amd import _lib as L
+    from connect4_amd.engine import Engine
+    good = np.random.RandomState(5).gamma(0.3, 1.0, size=(4, 42, 7))
+    u = np.full((4, 42), -1.0)
+    kw = dict(eval_mode=L.EVAL_CENTRE, rng_mode=L.RNG_TAPE, stop_after_move=True, root_dirichlet_alpha=0.3, root_exploration_fraction=0.25)
+
+    def search(eng):
+        eng.reset()
+        eng.run_centre()
+        return [(list(r.child_visits), list(r.child_value_sum), list(r.root_prior)) for r in eng.read_roots()]
+    with Engine(4, 32, **kw) as eng:
+        eng.set_tapes(good, u)
+        want = search(eng)
+        for where, value in (((0, 0, 0), -1e-300), ((3, 41, 6), float("nan")), ((1, 0, 3), float("inf")), ((2, 5, 1), float("-inf")),
+                             ((0, 0, 6), -1.0)):
+            bad = good.copy()
+            bad[where] = value
+            with pytest.raises(L.EngineError) as ei:
+                eng.set_tapes(bad, u)
+            assert ei.value.code == L.EINVAL
+        bad_u = u.copy()
+        bad_u[2, 7] = float("nan")
+        with pytest.raises(L.EngineError) as ei:
+            eng.set_tapes(good, bad_u)
+        assert ei.value.code == L.EINVAL
+        assert search(eng) == want                      # the engine stayed as it was
+        edge = good.copy()                              # zeros, the largest and the smallest doubles are draws
+        edge[0, 0] = [0.0, 1.7e308, 5e-324, 0.0, 1.0, 0.0, 0.0]
+        eng.set_tapes(edge, np.where(u < 0, u, 0.0))
+        eng.set_tapes(good, np.full((4, 42), float("inf")))     # only NaN is refused among the uniforms
