@@ -27,6 +27,7 @@ SOLVE_MAX_EMPTIES = 24
 SOLVE_DEEP_MAX_EMPTIES = 42
 SOLVE_TABLE_MIN_LOG2, SOLVE_TABLE_MAX_LOG2 = 10, 30
 SOLVE_SOLVED, SOLVE_TERMINAL, SOLVE_UNKNOWN, SOLVE_TOO_DEEP, SOLVE_INVALID = 0, 1, 2, 3, 4
+SOLVE_BOUND_NONE, SOLVE_BOUND_LOWER, SOLVE_BOUND_UPPER, SOLVE_BOUND_EXACT = 0, 1, 2, 3     # c4_solve_window's bound
 
 
 class EngineError(RuntimeError):
@@ -218,6 +219,10 @@ SIGNATURES = {
     "c4_solve_deep_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 5),
     "c4_solve_deep": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, C.c_int64, C.c_int64, C.c_int64, _P(C.c_int8), _P(C.c_int8),
                                 _P(C.c_int8), _i64p, _i64p]),
+    "c4_solve_window_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                      C.c_int64] + [C.c_void_p] * 7),
+    "c4_solve_window": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, _P(C.c_int8), _P(C.c_int8), C.c_int64, C.c_int64, C.c_int64] +
+                        [_P(C.c_int8)] * 5 + [_i64p, _i64p]),
 }
 
 _lib = None

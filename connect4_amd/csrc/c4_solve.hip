@@ -48,6 +48,15 @@
 //   * Answers are exact and do not depend on the table (alpha-beta returns the same root value for every sound set of
 //     bounds).  NODE COUNTS WITH A TABLE ARE NOT DETERMINISTIC: they depend on what other lanes stored first.  With a
 //     null table they are, and they equal k_solve_run's and solver._Search's.
+//
+// Windowed search (c4_solve_window / c4_solve_window_dev).  The deep search with the root's window given per row, alpha <
+// beta on the mover's score, instead of the whole range: fail-hard alpha-beta, the search every node below a root
+// already is.  A row answers with the score its root returns and that score's kind against the caller's window
+// (C4_SOLVE_BOUND_*): exact inside it, else a lower bound at or above beta or an upper bound at or below alpha.  The root's
+// table probe and enter_node may narrow the window the moves are searched with -- the root's own entry is stored against
+// that one, like any node's -- but the kind is judged against the window the caller gave, which stays in the caller's
+// arrays while the row is parked.  Nothing else changes: entries are true bounds whatever window found them, so one table
+// serves windowed and exact calls alike, and the entry points that pass no window enter the nodes they always entered.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -258,7 +267,8 @@ C4_HD void root_answer(int age, int score, int &outcome, int &final_age)
     final_age = abs_score > 0 ? 43 - abs_score : abs_score < 0 ? 43 + abs_score : CELLS;
 }
 
-C4_HD void enter_root(uint64_t c0, uint64_t c1, Lane &L)
+// alpha, beta: the caller's window on the mover's score (the full range for every search but a windowed one)
+C4_HD void enter_root(uint64_t c0, uint64_t c1, Lane &L, int alpha = -SCORE_MAX, int beta = SCORE_MAX)
 {
     const uint64_t occ = c0 | c1;
     const int age = popc64(occ);
@@ -267,8 +277,8 @@ C4_HD void enter_root(uint64_t c0, uint64_t c1, Lane &L)
     L.c1 = c1;
     L.d = 0;
     L.moves = 0;
-    L.alpha = -SCORE_MAX;
-    L.beta = SCORE_MAX;
+    L.alpha = alpha;
+    L.beta = beta;
     L.ret = 0;
     L.pending = false;
     L.done = false;
@@ -400,15 +410,43 @@ __device__ __forceinline__ void store_answer(const int64_t *boards, int64_t row,
     final_age[row] = (int8_t)fa;
 }
 
+// A windowed search (c4_solve_window*): where a row's window lives and where its answer goes.  score == nullptr: not a
+// windowed search, nothing here is read.  alpha == nullptr (then beta is, too): every row has the full window.  The
+// caller's arrays are the window's home for as long as the row is parked: the parked word holds the window of the top
+// frame, which the root's probe and the search narrow, and the answer's kind is judged against the caller's own.
+struct Window {
+    const int8_t *alpha, *beta;
+    int8_t *score, *bound;
+};
+
+C4_HD int bound_kind(int score, int alpha, int beta)
+{
+    return score >= beta ? C4_SOLVE_BOUND_LOWER : score <= alpha ? C4_SOLVE_BOUND_UPPER : C4_SOLVE_BOUND_EXACT;
+}
+
+// the root of windowed row `row` has returned `ret`: score and kind, and outcome and final age where the score is exact
+__device__ __forceinline__ void store_window_answer(const Window win, int64_t row, int age, int ret, int &outcome, int &final_age)
+{
+    const int a = win.alpha ? (int)win.alpha[row] : -SCORE_MAX, b = win.beta ? (int)win.beta[row] : SCORE_MAX;
+    const int kind = bound_kind(ret, a, b);
+    win.score[row] = (int8_t)ret;
+    win.bound[row] = (int8_t)kind;
+    outcome = -1;
+    final_age = -1;
+    if (kind == C4_SOLVE_BOUND_EXACT) root_answer(age, ret, outcome, final_age);
+}
+
 // one lane per row: status, the answers that need no search, the root of the others; unfinished[row] = 1
 // for a row that k_solve_run has to continue
 // for the deep search (`deep`): every depth is searchable, the root probes the table `tt` like any interior node, and the
-// parked word carries alpha0 where k_solve_run's carries ret (neither is read: the root is not pending); hits: or null
+// parked word carries alpha0 where k_solve_run's carries ret (neither is read: the root is not pending); hits: or null;
+// win: a windowed search's arrays (the root starts from the row's window, and a row answered here -- an immediate win, a
+// leaf root, a table entry that closes the window -- is judged like one answered by k_solve_deep), or nulls
 __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict__ boards, int64_t n, int64_t node_budget, Work w,
                                                       int8_t *__restrict__ status, int8_t *__restrict__ outcome,
                                                       int8_t *__restrict__ final_age, int64_t *__restrict__ nodes,
                                                       uint8_t *__restrict__ unfinished, bool deep, TableRef tt,
-                                                      int64_t *__restrict__ hits)
+                                                      int64_t *__restrict__ hits, Window win)
 {
     const int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (row >= n) return;
@@ -418,9 +456,14 @@ __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict_
     int64_t nd = 0;
     uint8_t more = 0;
     int hit = 0;
+    if (win.score) {        // a row without an answer keeps these
+        win.score[row] = 0;
+        win.bound[row] = C4_SOLVE_BOUND_NONE;
+    }
     if (st == C4_SOLVE_SOLVED) {
         Lane L;
-        enter_root(c0, c1, L);
+        if (win.score && win.alpha) enter_root(c0, c1, L, win.alpha[row], win.beta[row]);
+        else enter_root(c0, c1, L);
         nd = 1;
         if (deep && !L.done) {
             const uint64_t occ = c0 | c1;
@@ -437,7 +480,8 @@ __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict_
             }
             L.ret = L.done ? L.ret : L.alpha;       // the parked word's third field: alpha0
         }
-        if (L.done) root_answer(popc64(c0 | c1), L.ret, o, fa);
+        if (L.done && win.score) store_window_answer(win, row, popc64(c0 | c1), L.ret, o, fa);
+        else if (L.done) root_answer(popc64(c0 | c1), L.ret, o, fa);
         else if (nd >= node_budget) st = C4_SOLVE_UNKNOWN;
         else {
             more = 1;
@@ -521,7 +565,7 @@ __global__ void __launch_bounds__(BLOCK) k_solve_deep(const int64_t *__restrict_
                                                       int64_t node_budget, int64_t nodes_per_launch, Work w, TableRef tt,
                                                       int8_t *__restrict__ status, int8_t *__restrict__ outcome,
                                                       int8_t *__restrict__ final_age, int64_t *__restrict__ nodes,
-                                                      int64_t *__restrict__ hits, uint8_t *__restrict__ unfinished)
+                                                      int64_t *__restrict__ hits, uint8_t *__restrict__ unfinished, Window win)
 {
     __shared__ uint32_t s_moves[DEEP_MAX_PLY][BLOCK];
     __shared__ uint32_t s_ab[DEEP_MAX_PLY][BLOCK];
@@ -556,7 +600,13 @@ __global__ void __launch_bounds__(BLOCK) k_solve_deep(const int64_t *__restrict_
     nodes[row] = total + used;
     if (hits) hits[row] += L.hits;
     if (L.done) {
-        store_answer(boards, row, L, outcome, final_age);
+        if (win.score) {
+            int o, fa;
+            store_window_answer(win, row, popc64((uint64_t)boards[2 * row] | (uint64_t)boards[2 * row + 1]), L.ret, o, fa);
+            outcome[row] = (int8_t)o;
+            final_age[row] = (int8_t)fa;
+        } else
+            store_answer(boards, row, L, outcome, final_age);
         unfinished[i] = 0;
         return;
     }
@@ -636,7 +686,7 @@ int pick_device(int device)
 // parked frames (360 B a row), hits: table_hits or null; else k_solve_run
 int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t node_budget, int64_t per_launch, int8_t *status,
                 int8_t *outcome, int8_t *final_age, int64_t *nodes, bool deep = false, TableRef tt = TableRef{nullptr, 0},
-                int64_t *hits = nullptr)
+                int64_t *hits = nullptr, Window win = Window{nullptr, nullptr, nullptr, nullptr})
 {
     DevBuf mem, flags, act;
     const int max_ply = deep ? DEEP_MAX_PLY : MAX_PLY;
@@ -654,7 +704,7 @@ int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t no
     w.stk_ab = w.stk_moves + (size_t)n * max_ply;
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
     hipLaunchKernelGGL(k_solve_init, dim3(grid), dim3(BLOCK), 0, stream, boards, n, node_budget, w, status, outcome, final_age, nodes,
-                       flags.as<uint8_t>(), deep, tt, hits);
+                       flags.as<uint8_t>(), deep, tt, hits, win);
     SOLVE_CHECK(hipGetLastError());
     std::vector<uint8_t> host_flags((size_t)n);
     std::vector<int32_t> active, next;
@@ -673,7 +723,7 @@ int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t no
         SOLVE_CHECK(hipMemcpyAsync(act.p, active.data(), (size_t)m * 4, hipMemcpyHostToDevice, stream));
         if (deep)
             hipLaunchKernelGGL(k_solve_deep, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, boards, act.as<int32_t>(),
-                               m, node_budget, per_launch, w, tt, status, outcome, final_age, nodes, hits, flags.as<uint8_t>());
+                               m, node_budget, per_launch, w, tt, status, outcome, final_age, nodes, hits, flags.as<uint8_t>(), win);
         else
             hipLaunchKernelGGL(k_solve_run, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, boards, act.as<int32_t>(), m,
                                node_budget, per_launch, w, status, outcome, final_age, nodes, flags.as<uint8_t>());
@@ -697,6 +747,27 @@ int check_args(const void *boards, int64_t n, int64_t &node_budget, int64_t &per
     if (node_budget == 0) node_budget = DEFAULT_BUDGET;
     if (per_launch == 0) per_launch = DEFAULT_PER_LAUNCH;
     if (per_launch > ((int64_t)1 << 40)) per_launch = (int64_t)1 << 40;
+    return C4_OK;
+}
+
+// the pointers of a windowed call: alpha and beta come together (both null: the full window for every row)
+int check_window_args(const void *alpha, const void *beta, int64_t n, const void *score, const void *bound)
+{
+    if (n > 0 && (!score || !bound)) { set_solve_err("null argument"); return C4_EINVAL; }
+    if ((alpha == nullptr) != (beta == nullptr)) { set_solve_err("alpha and beta are given together, or both are null"); return C4_EINVAL; }
+    return C4_OK;
+}
+
+// host copies of the windows of n rows: -42 <= alpha < beta <= 42 in every row
+int check_windows(const int8_t *alpha, const int8_t *beta, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        const int a = alpha[i], b = beta[i];
+        if (a < -SCORE_MAX || b > SCORE_MAX || a >= b) {
+            set_solve_err("row %lld: the window (%d, %d) is not -%d <= alpha < beta <= %d", (long long)i, a, b, SCORE_MAX, SCORE_MAX);
+            return C4_EINVAL;
+        }
+    }
     return C4_OK;
 }
 
@@ -893,6 +964,86 @@ int c4_solve_deep(int device, c4_solve_table *table, const uint64_t *color0, con
     SOLVE_CHECK(hipMemcpy(nodes, nodes_d, (size_t)n * 8, hipMemcpyDeviceToHost));
     if (table_hits) SOLVE_CHECK(hipMemcpy(table_hits, hits_d, (size_t)n * 8, hipMemcpyDeviceToHost));
     SOLVE_CHECK(hipMemcpy(status, status_d, (size_t)n, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(outcome, outcome_d, (size_t)n, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(final_age, age_d, (size_t)n, hipMemcpyDeviceToHost));
+    return C4_OK;
+}
+
+int c4_solve_window_dev(int device, void *hip_stream, c4_solve_table *table, const int64_t *boards_dev, const int8_t *alpha_dev,
+                        const int8_t *beta_dev, int64_t n, int64_t node_budget, int64_t nodes_per_launch, int8_t *status_dev,
+                        int8_t *score_dev, int8_t *bound_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev,
+                        int64_t *table_hits_dev)
+{
+    int rc = check_args(boards_dev, n, node_budget, nodes_per_launch, status_dev, outcome_dev, final_age_dev, nodes_dev);
+    if (rc) return rc;
+    rc = check_window_args(alpha_dev, beta_dev, n, score_dev, bound_dev);
+    if (rc) return rc;
+    TableRef tt;
+    rc = table_ref(table, device, tt);
+    if (rc || n == 0) return rc;
+    rc = pick_device(device);
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (alpha_dev) {        // the windows are checked on the host before the first launch
+        std::vector<int8_t> ab((size_t)n * 2);
+        SOLVE_CHECK(hipMemcpyAsync(ab.data(), alpha_dev, (size_t)n, hipMemcpyDeviceToHost, stream));
+        SOLVE_CHECK(hipMemcpyAsync(ab.data() + n, beta_dev, (size_t)n, hipMemcpyDeviceToHost, stream));
+        SOLVE_CHECK(hipStreamSynchronize(stream));
+        rc = check_windows(ab.data(), ab.data() + n, n);
+        if (rc) return rc;
+    }
+    for (int64_t lo = 0; lo < n; lo += CHUNK_ROWS) {
+        const int64_t m = n - lo < CHUNK_ROWS ? n - lo : CHUNK_ROWS;
+        const Window win{alpha_dev ? alpha_dev + lo : nullptr, beta_dev ? beta_dev + lo : nullptr, score_dev + lo, bound_dev + lo};
+        rc = solve_chunk(stream, boards_dev + 2 * lo, m, node_budget, nodes_per_launch, status_dev + lo, outcome_dev + lo,
+                         final_age_dev + lo, nodes_dev + lo, true, tt, table_hits_dev ? table_hits_dev + lo : nullptr, win);
+        if (rc) return rc;
+    }
+    return C4_OK;
+}
+
+int c4_solve_window(int device, c4_solve_table *table, const uint64_t *color0, const uint64_t *color1, const int8_t *alpha,
+                    const int8_t *beta, int64_t n, int64_t node_budget, int64_t nodes_per_launch, int8_t *status, int8_t *score,
+                    int8_t *bound, int8_t *outcome, int8_t *final_age, int64_t *nodes, int64_t *table_hits)
+{
+    if (n > 0 && (!color0 || !color1)) { set_solve_err("null argument"); return C4_EINVAL; }
+    int rc = check_args(color0, n, node_budget, nodes_per_launch, status, outcome, final_age, nodes);
+    if (rc) return rc;
+    rc = check_window_args(alpha, beta, n, score, bound);
+    if (rc) return rc;
+    if (alpha) {
+        rc = check_windows(alpha, beta, n);
+        if (rc) return rc;
+    }
+    TableRef tt;
+    rc = table_ref(table, device, tt);
+    if (rc || n == 0) return rc;
+    rc = pick_device(device);
+    if (rc) return rc;
+    std::vector<int64_t> packed((size_t)n * 2);
+    for (int64_t i = 0; i < n; ++i) {
+        packed[(size_t)(2 * i)] = (int64_t)color0[i];
+        packed[(size_t)(2 * i + 1)] = (int64_t)color1[i];
+    }
+    DevBuf b, out;
+    SOLVE_CHECK(b.get((size_t)n * 16));
+    SOLVE_CHECK(out.get((size_t)n * 23));
+    int64_t *nodes_d = out.as<int64_t>(), *hits_d = nodes_d + n;
+    int8_t *status_d = (int8_t *)(hits_d + n), *outcome_d = status_d + n, *age_d = outcome_d + n, *score_d = age_d + n,
+           *bound_d = score_d + n, *alpha_d = bound_d + n, *beta_d = alpha_d + n;
+    SOLVE_CHECK(hipMemcpy(b.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+    if (alpha) {
+        SOLVE_CHECK(hipMemcpy(alpha_d, alpha, (size_t)n, hipMemcpyHostToDevice));
+        SOLVE_CHECK(hipMemcpy(beta_d, beta, (size_t)n, hipMemcpyHostToDevice));
+    }
+    rc = c4_solve_window_dev(device, nullptr, table, b.as<int64_t>(), alpha ? alpha_d : nullptr, alpha ? beta_d : nullptr, n, node_budget,
+                             nodes_per_launch, status_d, score_d, bound_d, outcome_d, age_d, nodes_d, hits_d);
+    if (rc) return rc;
+    SOLVE_CHECK(hipMemcpy(nodes, nodes_d, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (table_hits) SOLVE_CHECK(hipMemcpy(table_hits, hits_d, (size_t)n * 8, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(status, status_d, (size_t)n, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(score, score_d, (size_t)n, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(bound, bound_d, (size_t)n, hipMemcpyDeviceToHost));
     SOLVE_CHECK(hipMemcpy(outcome, outcome_d, (size_t)n, hipMemcpyDeviceToHost));
     SOLVE_CHECK(hipMemcpy(final_age, age_d, (size_t)n, hipMemcpyDeviceToHost));
     return C4_OK;

@@ -13,6 +13,9 @@ all calls share, and a split that spreads one hard position over many lanes.  Ne
 ``grid_triple`` ``(move, value, tree)`` per board, what ``grid_search(boards, plies=empties, evaluate_centre)`` returns
 ``label``       a ``LabelledSet`` (value = outcome, prior = uniform over the moves that keep it: the rule of
                 oinkoink/scripts/generate_7ply.py:83-91) and a report
+``solve_window`` the deep search from a root window per row: the score the root returns and whether it is exact, a lower or an
+                upper bound against that window; ``outcomes`` is the window (-1, +1), the cheapest search that tells who wins
+``label(exact=False)`` / ``label_values``  the same labels from outcome windows and null windows instead of exact scores
 ``solve_host``  a plain-Python mirror of the kernel's search -- same integer score, same pruning and move order, same node
                 counts -- for tests and for machines without a GPU; with ``table={}`` also of its probe / store logic
 ``HostTable``   the kernel's table (layout, slot function, always-replace) behind ``solve_host(table=...)``;
@@ -34,7 +37,8 @@ from .grid_search import GridTree, _terminal_value
 from .utils import Side
 
 __all__ = ["MAX_EMPTIES", "DEEP_MAX_EMPTIES", "DEFAULT_NODE_BUDGET", "STATUS_NAMES", "Solved", "HostAnswer", "Table", "HostTable",
-           "EntryFields", "entry_fields", "solve", "solve_host", "grid_triple", "label", "prior_from_children", "value_from_answer", "random_playout", "random_openings"]
+           "EntryFields", "entry_fields", "solve", "solve_host", "HostWindowAnswer", "Windowed", "BOUND_NAMES", "solve_window", "outcomes",
+           "label_values", "staged_labels", "grid_triple", "label", "prior_from_children", "value_from_answer", "random_playout", "random_openings"]
 
 MAX_EMPTIES = L.SOLVE_MAX_EMPTIES
 DEEP_MAX_EMPTIES = L.SOLVE_DEEP_MAX_EMPTIES     # every position: c4_solve_deep and solve(deep=True / table=)
@@ -44,6 +48,10 @@ STATUS_NAMES = {L.SOLVE_SOLVED: "solved", L.SOLVE_TERMINAL: "terminal", L.SOLVE_
 
 Solved = namedtuple("Solved", "status outcome final_age value nodes table_hits")
 HostAnswer = namedtuple("HostAnswer", "status outcome final_age value nodes")
+HostWindowAnswer = namedtuple("HostWindowAnswer", "status score bound outcome final_age value nodes")
+Windowed = namedtuple("Windowed", "status score bound outcome final_age nodes table_hits")
+BOUND_NAMES = {L.SOLVE_BOUND_NONE: "none", L.SOLVE_BOUND_LOWER: "lower", L.SOLVE_BOUND_UPPER: "upper", L.SOLVE_BOUND_EXACT: "exact"}
+SCORE_MAX = 42      # beyond every score: (-SCORE_MAX, SCORE_MAX) is the full window
 
 _BOARD = BOTTOM * ((1 << HEIGHT) - 1)
 _COL = (1 << HEIGHT) - 1
@@ -279,24 +287,50 @@ def _classify(c0, c1, max_empties=None):
     return L.SOLVE_SOLVED
 
 
-def solve_host(board, node_budget=None, table=None, deep=False):
+def _check_window(alpha, beta):
+    if not (float(alpha).is_integer() and float(beta).is_integer() and -SCORE_MAX <= alpha < beta <= SCORE_MAX):
+        raise ValueError("the window (%r, %r) is not -%d <= alpha < beta <= %d in whole numbers" % (alpha, beta, SCORE_MAX, SCORE_MAX))
+    return int(alpha), int(beta)
+
+
+def _bound_kind(score, alpha, beta):
+    return L.SOLVE_BOUND_LOWER if score >= beta else L.SOLVE_BOUND_UPPER if score <= alpha else L.SOLVE_BOUND_EXACT
+
+
+def solve_host(board, node_budget=None, table=None, deep=False, window=None):
     """The kernel's answer for one position, computed in plain Python: ``HostAnswer(status, outcome, final_age, value,
     nodes)``.  `board`: a Board or a ``(color0, color1)`` pair.  outcome / value are None where the status has none.
 
     deep=True is c4_solve_deep's table-free search (any number of empty squares, never TOO_DEEP).  table: a ``dict``, which
     implies deep -- the kernel's probe / store / bound logic on ``key -> (kind, score)`` entries; the dict may be shared by
     any number of calls, the answer does not depend on what it holds, the node count does.  A ``HostTable`` in its place
-    adds the kernel's slots and replacement: one row at a time it holds, word for word, what one lane leaves in a ``Table``."""
+    adds the kernel's slots and replacement: one row at a time it holds, word for word, what one lane leaves in a ``Table``.
+
+    window=(alpha, beta), -42 <= alpha < beta <= 42 on the mover's score, implies deep and is c4_solve_window's row: the
+    root is entered with that window instead of (-42, 42), and the answer is a ``HostWindowAnswer`` that also has the score
+    the root returns and its kind against the window (_lib.SOLVE_BOUND_*): exact inside it, a lower bound at or above beta,
+    an upper bound at or below alpha.  outcome, final_age and value are None / -1 unless the bound is exact; rows that are
+    not searched have score 0 and bound SOLVE_BOUND_NONE."""
     c0, c1 = (board.color if isinstance(board, Board) else board)
     c0, c1 = int(c0), int(c1)
     budget = DEFAULT_NODE_BUDGET if node_budget is None else int(node_budget)
-    st = _classify(c0, c1, DEEP_MAX_EMPTIES if deep or table is not None else MAX_EMPTIES)
+    if window is not None:
+        w_alpha, w_beta = _check_window(*window)
+    else:
+        w_alpha, w_beta = -SCORE_MAX, SCORE_MAX
+    st = _classify(c0, c1, DEEP_MAX_EMPTIES if deep or table is not None or window is not None else MAX_EMPTIES)
+
+    def answer(status, outcome, final_age, value, nodes, score=0, bound=L.SOLVE_BOUND_NONE):
+        if window is None:
+            return HostAnswer(status, outcome, final_age, value, nodes)
+        return HostWindowAnswer(status, score, bound, outcome, final_age, value, nodes)
+
     if st == L.SOLVE_TERMINAL:
         outcome = 1.0 if _wins(c0) else 0.0 if _wins(c1) else 0.5
         age = bin(c0 | c1).count("1")
-        return HostAnswer(st, outcome, age, float(value_from_answer(outcome, age)), 0)
+        return answer(st, outcome, age, float(value_from_answer(outcome, age)), 0)
     if st != L.SOLVE_SOLVED:
-        return HostAnswer(st, None, -1, None, 0)
+        return answer(st, None, -1, None, 0)
     occ = c0 | c1
     age = bin(occ).count("1")
     mine, theirs = (c1, c0) if age & 1 else (c0, c1)
@@ -305,17 +339,20 @@ def solve_host(board, node_budget=None, table=None, deep=False):
         score, nodes = 42 - age, 1
     else:
         try:
-            score = s.node(mine, theirs, age, -42, 42)
+            score = s.node(mine, theirs, age, w_alpha, w_beta)
         except _OverBudget:
-            return HostAnswer(L.SOLVE_UNKNOWN, None, -1, None, s.nodes)
+            return answer(L.SOLVE_UNKNOWN, None, -1, None, s.nodes)
         finally:
             if isinstance(table, HostTable):
                 table.hits += s.hits
         nodes = s.nodes
+    bound = _bound_kind(score, w_alpha, w_beta)
+    if bound != L.SOLVE_BOUND_EXACT:        # only a windowed search gets here: no score leaves (-42, 42)
+        return answer(L.SOLVE_SOLVED, None, -1, None, nodes, score, bound)
     abs_score = -score if age & 1 else score
     outcome = 1.0 if abs_score > 0 else 0.0 if abs_score < 0 else 0.5
     final_age = 43 - abs(abs_score) if abs_score else SIZE
-    return HostAnswer(L.SOLVE_SOLVED, outcome, final_age, float(value_from_answer(outcome, final_age)), nodes)
+    return answer(L.SOLVE_SOLVED, outcome, final_age, float(value_from_answer(outcome, final_age)), nodes, score, bound)
 
 
 # -- the device ------------------------------------------------------------------------------------------------------------
@@ -673,6 +710,113 @@ def solve(boards, node_budget=None, nodes_per_launch=None, device=0, table=None,
     return _finish(status, outcome, age, nodes, hits)
 
 
+# -- the deep search from a root window per row --------------------------------------------------------------------------
+def _window_arrays(alpha, beta, n):
+    """int8 [n] arrays of a scalar or per-row window, checked row by row; (None, None) for the full window."""
+    if alpha is None and beta is None:
+        return None, None
+    if alpha is None or beta is None:
+        raise ValueError("alpha and beta are given together, or both are None")
+    a = np.broadcast_to(np.asarray(alpha), (n,)) if np.ndim(alpha) == 0 else np.asarray(alpha)
+    b = np.broadcast_to(np.asarray(beta), (n,)) if np.ndim(beta) == 0 else np.asarray(beta)
+    if a.shape != (n,) or b.shape != (n,):
+        raise ValueError("alpha and beta are scalars or arrays of one entry per row (%d); got %s and %s" % (n, a.shape, b.shape))
+    bad = np.nonzero(~((a == np.floor(a)) & (b == np.floor(b)) & (a >= -SCORE_MAX) & (a < b) & (b <= SCORE_MAX)))[0]
+    if len(bad):
+        raise ValueError("row %d: the window (%r, %r) is not -%d <= alpha < beta <= %d in whole numbers" % (
+            bad[0], a[bad[0]].item(), b[bad[0]].item(), SCORE_MAX, SCORE_MAX))
+    return np.ascontiguousarray(a, dtype=np.int8), np.ascontiguousarray(b, dtype=np.int8)
+
+
+def _solve_window_dev(packed, alpha, beta, node_budget=None, nodes_per_launch=None, table=None):
+    """c4_solve_window_dev on a packed cuda tensor; alpha, beta: int8 NumPy arrays or None.  (status int8, score int8, bound
+    int8, outcome int8, final_age int8, nodes int64, table_hits int64) device tensors."""
+    import ctypes as C
+    import torch
+    n = int(packed.shape[0])
+    dev = packed.device
+    status, score, bound, outcome, age = (torch.empty(n, dtype=torch.int8, device=dev) for _ in range(5))
+    nodes = torch.empty(n, dtype=torch.int64, device=dev)
+    hits = torch.zeros(n, dtype=torch.int64, device=dev)
+    if n:
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        with torch.cuda.device(dev):
+            a_dev = torch.from_numpy(alpha).to(dev) if alpha is not None else None
+            b_dev = torch.from_numpy(beta).to(dev) if beta is not None else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+            _check(L.load().c4_solve_window_dev(idx, C.c_void_p(stream), table.handle if table is not None else None, ptr(packed),
+                                                ptr(a_dev), ptr(b_dev), n, int(node_budget or 0), int(nodes_per_launch or 0),
+                                                ptr(status), ptr(score), ptr(bound), ptr(outcome), ptr(age), ptr(nodes), ptr(hits)))
+    return status, score, bound, outcome, age, nodes, hits
+
+
+def _finish_window(status, score, bound, outcome, age, nodes, hits):
+    known = np.asarray(outcome) >= 0
+    return Windowed(np.asarray(status, dtype=np.int8), np.asarray(score, dtype=np.int8), np.asarray(bound, dtype=np.int8),
+                    np.where(known, np.asarray(outcome, dtype=np.float64) * 0.5, np.nan), np.asarray(age, dtype=np.int8),
+                    np.asarray(nodes, dtype=np.int64), np.asarray(hits, dtype=np.int64))
+
+
+def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, device=0, table=None):
+    """The deep search (``solve(deep=True)``: every position, optionally a ``Table``) from a root window per row.  alpha, beta:
+    scalars or per-row arrays on the mover's score (43 - final age for a win, final age - 43 for a loss, 0 for a draw),
+    -42 <= alpha < beta <= 42; both None: the full window.  `boards` as ``solve`` takes them.  Returns ``Windowed`` of arrays:
+
+      status     int8, _lib.SOLVE_* -- ``solve``'s, never TOO_DEEP
+      score      int8, the mover's score as the root returns it (0 where the row has no answer)
+      bound      int8, _lib.SOLVE_BOUND_* (BOUND_NAMES): EXACT where alpha < score < beta -- the score is the position's;
+                 LOWER where score >= beta, UPPER where score <= alpha -- a true bound of that kind, possibly beyond the
+                 window (an immediate win answers 42 - age whatever was asked); NONE where the row was not searched to the end
+      outcome    float64 0.0 / 0.5 / 1.0 where the bound is exact and for finished positions, else NaN
+      final_age  int8, likewise, else -1
+      nodes, table_hits  as ``solve``
+
+    A narrower window never costs a table-free search more nodes than one that contains it; (-1, 1) answers who wins,
+    (v - 1, v) whether the mover's score reaches v."""
+    if table is not None:
+        device = table.device
+    n = int(boards.shape[0]) if _is_tensor(boards) else len(boards)
+    a, b = _window_arrays(alpha, beta, n)
+    if _is_tensor(boards):
+        res = _solve_window_dev(_packed_on_device(boards, device), a, b, node_budget, nodes_per_launch, table)
+        return _finish_window(*(t.cpu().numpy() for t in res))
+    import ctypes as C
+    status, score, bound, outcome, age = (np.zeros(n, dtype=np.int8) for _ in range(5))
+    nodes = np.zeros(n, dtype=np.int64)
+    hits = np.zeros(n, dtype=np.int64)
+    if n:
+        c0, c1 = _bits(boards)
+        i8 = C.POINTER(C.c_int8)
+        _check(L.load().c4_solve_window(device, table.handle if table is not None else None, c0.ctypes.data_as(L._u64p),
+                                        c1.ctypes.data_as(L._u64p), a.ctypes.data_as(i8) if a is not None else None,
+                                        b.ctypes.data_as(i8) if b is not None else None, n, int(node_budget or 0),
+                                        int(nodes_per_launch or 0), status.ctypes.data_as(i8), score.ctypes.data_as(i8),
+                                        bound.ctypes.data_as(i8), outcome.ctypes.data_as(i8), age.ctypes.data_as(i8),
+                                        nodes.ctypes.data_as(L._i64p), hits.ctypes.data_as(L._i64p)))
+    else:
+        outcome -= 1
+    return _finish_window(status, score, bound, outcome, age, nodes, hits)
+
+
+def _ages(rows):
+    return _popcount64(rows[:, 0] | rows[:, 1]) if len(rows) else np.zeros(0, dtype=np.int64)
+
+
+def outcomes(boards, node_budget=None, nodes_per_launch=None, device=0, table=None):
+    """Who wins each position: float64 0.0 (x) / 0.5 (draw) / 1.0 (o), NaN where the budget leaves a row unknown or the row is
+    invalid; a finished position answers with its own result.  One search per row with the window (-1, +1), the narrowest
+    that separates win, draw and loss -- how fast is not asked, and not paid for."""
+    res = solve_window(boards, -1, 1, node_budget, nodes_per_launch, device, table)
+    if _is_tensor(boards):
+        rows = boards.cpu().numpy().view(np.uint64).reshape(-1, 2)
+    else:
+        rows = np.stack(_bits(boards), axis=1) if len(boards) else np.zeros((0, 2), dtype=np.uint64)
+    sign = np.sign(res.score.astype(np.int64))
+    absolute = np.where(_ages(rows) & 1, -sign, sign)
+    return np.where(res.status == L.SOLVE_SOLVED, (absolute + 1) * 0.5, np.where(res.status == L.SOLVE_TERMINAL, res.outcome, np.nan))
+
+
 # -- grid_search's triple --------------------------------------------------------------------------------------------------
 def _check_root(board, deep=False):
     if board.result is not None:
@@ -754,7 +898,170 @@ def prior_from_children(outcome, child_outcomes, legal):
     return np.where(s > 0, p / np.maximum(s, 1.0), 0.0)
 
 
-def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, split_plies=0):
+def _wins_bits(p):
+    """bool [m]: the stones `p` (uint64 [m]) hold four in a row."""
+    out = np.zeros(p.shape, dtype=bool)
+    for s in (1, HEIGHT, H1, H1 + 1):
+        y = p & (p >> np.uint64(s))
+        out |= (y & (y >> np.uint64(2 * s))) != 0
+    return out
+
+
+def staged_labels(rows, window_solver, children_of=None, stage2=True):
+    """The labelling rule from outcomes alone, in two stages of windowed searches; plain NumPy around two callables, so the
+    device and the host mirror label by the same lines.
+
+    rows: uint64 [n, 2] distinct positions.  window_solver(rows uint64 [m, 2], alpha int8 [m], beta int8 [m]) -> (status,
+    score, nodes, table_hits) arrays of m: c4_solve_window's answers.  children_of(rows) -> (children uint64 [n, 7, 2], legal
+    bool [n, 7]), default ``_children_host``.
+
+    Stage 1: every row with the window (-1, +1); the sign of the score is V, the outcome for the mover.
+    Stage 2: for rows with V >= 0, each legal child that is not finished, with a null window on the child's mover's score:
+    (-1, 0) under V = +1, (0, 1) under V = 0.  The child keeps V iff it fails low (score <= alpha): it is lost for its mover,
+    or no better than drawn.  A finished child answers with its own result; under V = -1 every legal move keeps V and nothing
+    is searched.  The stage-2 rows are the distinct (position, window) pairs, mirror images merged (``_canonical`` is the
+    key, the image met first is the one searched), one batch.
+
+    Returns a dict: status int8 [n] (stage 1's, UNKNOWN also where a stage-2 row the position needs is), v int64 [n],
+    outcome int8 [n] (C4_RESULT_*, -1 where there is none), keep bool [n, 7] (the moves that keep the outcome), legal, and
+    stage1_rows / _nodes / _unknown / _hits and stage2_rows / _nodes / _unknown / _hits.  Raises RuntimeError if a fully
+    known position with V >= 0 has no keeping move: the searches would contradict each other.  stage2=False stops after
+    stage 1: keep and legal are all False and the stage-2 counts zero."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+    n = len(rows)
+    ones = np.ones(n, dtype=np.int8)
+    status, score, nodes1, hits1 = (np.asarray(a) for a in window_solver(rows, -ones, ones))
+    status = status.astype(np.int8)
+    solved = status == L.SOLVE_SOLVED
+    v = np.where(solved, np.sign(score.astype(np.int64)), 0)
+    odd = (_ages(rows) & 1) == 1
+    outcome = np.where(solved, np.where(odd, -v, v) + 1, -1).astype(np.int8)
+    if not stage2:
+        none = np.zeros((n, WIDTH), dtype=bool)
+        return {"status": status, "v": v, "outcome": outcome, "keep": none, "legal": none, "stage1_rows": n,
+                "stage1_nodes": int(nodes1.sum()), "stage1_unknown": int((status == L.SOLVE_UNKNOWN).sum()), "stage1_hits": int(hits1.sum()),
+                "stage2_rows": 0, "stage2_nodes": 0, "stage2_unknown": 0, "stage2_hits": 0}
+    children, legal = (children_of or _children_host)(rows)
+    children = np.asarray(children, dtype=np.uint64)
+    legal = np.asarray(legal).astype(bool) & solved[:, None]
+    moved = np.where(odd[:, None], children[:, :, 1], children[:, :, 0])        # the stones of the side that just moved
+    won = legal & _wins_bits(moved)
+    full = legal & ~won & ((_popcount64(children[:, :, 0] | children[:, :, 1]) == SIZE))
+    need = legal & ~won & ~full & (v >= 0)[:, None]
+    parent_v = np.broadcast_to(v[:, None], need.shape)[need]
+    # a stage-2 row is a (position, window) pair; mirror images are one pair, searched as the one met first (the move order
+    # breaks ties by column, so an image can cost other nodes than its original: none is the cheaper by rule)
+    asked = children[need]
+    triples = np.concatenate([_canonical(asked), parent_v.astype(np.uint64)[:, None]], axis=1) if need.any() else np.zeros((0, 3), dtype=np.uint64)
+    if len(triples):
+        _, first, inv = np.unique(triples, axis=0, return_index=True, return_inverse=True)
+        inv = np.asarray(inv, dtype=np.int64).reshape(-1)
+        uniq = np.concatenate([asked[first], triples[first, 2:]], axis=1)
+    else:
+        uniq, inv = triples, np.zeros(0, dtype=np.int64)
+    alpha2 = np.where(uniq[:, 2] == 1, -1, 0).astype(np.int8)
+    if len(uniq):
+        status2, score2, nodes2, hits2 = (np.asarray(a) for a in window_solver(np.ascontiguousarray(uniq[:, :2]), alpha2, (alpha2 + 1).astype(np.int8)))
+    else:
+        status2, score2, nodes2, hits2 = (np.zeros(0, dtype=np.int64) for _ in range(4))
+    known2 = status2 == L.SOLVE_SOLVED
+    keep = np.where((v < 0)[:, None], legal, (won & (v == 1)[:, None]) | (full & (v == 0)[:, None]))
+    keep[need] = (known2 & (score2 <= alpha2))[inv]
+    missing = np.zeros(need.shape, dtype=bool)
+    missing[need] = ~known2[inv]
+    unknown = solved & missing.any(axis=1)
+    broken = np.nonzero(solved & ~unknown & (v >= 0) & ~keep.any(axis=1))[0]
+    if len(broken):
+        i = int(broken[0])
+        raise RuntimeError("the position (%#x, %#x) has the outcome %+d for its mover and no move that keeps it" % (
+            int(rows[i, 0]), int(rows[i, 1]), int(v[i])))
+    status = np.where(unknown, L.SOLVE_UNKNOWN, status).astype(np.int8)
+    return {"status": status, "v": v, "outcome": np.where(unknown, -1, outcome).astype(np.int8), "keep": keep & ~unknown[:, None],
+            "legal": legal,
+            "stage1_rows": n, "stage1_nodes": int(nodes1.sum()), "stage1_unknown": int((status == L.SOLVE_UNKNOWN).sum() - unknown.sum()),
+            "stage1_hits": int(hits1.sum()),
+            "stage2_rows": len(uniq), "stage2_nodes": int(nodes2.sum()), "stage2_unknown": int((status2 == L.SOLVE_UNKNOWN).sum()),
+            "stage2_hits": int(hits2.sum())}
+
+
+def _rows_u64(boards):
+    """uint64 [n, 2] of a packed tensor, a uint64 / int64 [n, 2] array or a sequence of Boards or pairs."""
+    if _is_tensor(boards):
+        return boards.cpu().numpy().view(np.uint64).reshape(-1, 2)
+    if isinstance(boards, np.ndarray):
+        return np.ascontiguousarray(boards).view(np.uint64).reshape(-1, 2)
+    return np.stack(_bits(boards), axis=1) if len(boards) else np.zeros((0, 2), dtype=np.uint64)
+
+
+def _first_occurrences(rows):
+    """The distinct rows of uint64 [n, 2] in the order of their first occurrence."""
+    if len(rows) == 0:
+        return rows
+    _, first = np.unique(rows, axis=0, return_index=True)
+    return np.ascontiguousarray(rows[np.sort(first)])
+
+
+def _window_solver(node_budget, nodes_per_launch, device, table, host):
+    """staged_labels' window_solver on the device (c4_solve_window_dev) or, host=True, on ``solve_host`` (table: a dict or a
+    ``HostTable``)."""
+    if host:
+        def on_host(rows, alpha, beta):
+            ans = [solve_host((int(c0), int(c1)), node_budget, table=table, window=(int(a), int(b))) for (c0, c1), a, b in zip(rows, alpha, beta)]
+            return (np.array([a.status for a in ans], dtype=np.int8), np.array([a.score for a in ans], dtype=np.int8),
+                    np.array([a.nodes for a in ans], dtype=np.int64), np.zeros(len(ans), dtype=np.int64))
+        return on_host
+
+    def on_device(rows, alpha, beta):
+        import torch
+        packed = _packed_on_device(torch.from_numpy(np.ascontiguousarray(rows).view(np.int64)), device)
+        res = _solve_window_dev(packed, np.ascontiguousarray(alpha, dtype=np.int8), np.ascontiguousarray(beta, dtype=np.int8),
+                                node_budget, nodes_per_launch, table)
+        status, score, _, _, _, nodes, hits = (t.cpu().numpy() for t in res)
+        return status, score, nodes, hits
+    return on_device
+
+
+def _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors):
+    import torch
+    from .stats import LabelledSet
+    t0 = time.perf_counter()
+    if table is not None and not host:
+        device = table.device
+    if host:
+        rows_in, out_dev = _rows_u64(boards), torch.device("cpu")
+    else:
+        packed = _packed_on_device(boards, device)
+        rows_in, out_dev = _rows_u64(packed), packed.device
+    rows = _first_occurrences(rows_in)
+    solver_fn = _window_solver(node_budget, nodes_per_launch, device, table, host)
+    st = staged_labels(rows, solver_fn, stage2=with_priors)
+    keep = st["status"] == L.SOLVE_SOLVED
+    values = torch.from_numpy((st["outcome"][keep].astype(np.float32) * np.float32(0.5)))
+    bits = torch.from_numpy(np.ascontiguousarray(rows[keep]).view(np.int64)).to(out_dev).contiguous()
+    priors = None
+    if with_priors:
+        p = st["keep"][keep].astype(np.float64)
+        tot = p.sum(axis=1, keepdims=True)
+        priors = torch.from_numpy(np.where(tot > 0, p / np.maximum(tot, 1.0), 0.0).astype(np.float32)).to(out_dev).contiguous()
+    ls = LabelledSet(bits, values.to(out_dev).contiguous(), priors)
+    counts = np.bincount(st["status"].astype(np.int64), minlength=len(STATUS_NAMES))
+    report = {"positions": len(rows_in), "distinct": len(rows), "labelled": len(ls), "nodes": st["stage1_nodes"] + st["stage2_nodes"],
+              "exact": False, "table_log2_entries": getattr(table, "log2_entries", None),
+              "table_hits": st["stage1_hits"] + st["stage2_hits"]}
+    report.update({k: st[k] for k in ("stage1_rows", "stage1_nodes", "stage1_unknown", "stage2_rows", "stage2_nodes", "stage2_unknown")})
+    report.update({name: int(counts[code]) for code, name in STATUS_NAMES.items()})
+    report["seconds"] = time.perf_counter() - t0
+    return ls, report
+
+
+def label_values(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, host=False):
+    """Label positions with their outcome alone: ``(LabelledSet without priors, report)``, the kind of set the reference
+    scores by value only.  This is stage 1 of ``label(exact=False)`` -- one search per distinct position with the window
+    (-1, +1), at any depth -- and nothing else; rows, order and report as there."""
+    return _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors=False)
+
+
+def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, split_plies=0, exact=True, host=False, deep=False):
     """Label positions with their exact outcome: returns ``(LabelledSet, report)``.
 
     Each distinct position is solved once, together with its up-to-seven children (c4_solve_children_dev lists them) in one
@@ -764,7 +1071,23 @@ def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None,
     (STATUS_NAMES), nodes (parents and children) and seconds.
 
     table (a ``Table``) and split_plies are ``solve``'s; with either, positions of any depth are labelled (none is too deep)
-    and only the children that exist are solved.  The report then also says table_log2_entries and table_hits."""
+    and only the children that exist are solved.  The report then also says table_log2_entries and table_hits.  deep=True
+    is the same without either: the table-free deep search.
+
+    exact=False labels by outcome alone (``staged_labels``): the rule never asks how fast a game is won, so each distinct
+    position gets one search with the window (-1, +1), and only the unfinished children of positions that are not lost get
+    one null-window search each ("does this move keep the outcome?"), as one batch against the same `table`.  Positions of
+    any depth are taken, with or without a table.  Wherever both label a row the set equals exact=True's bit for bit; the
+    report says exact: False and, per stage, stage1_rows / stage1_nodes / stage1_unknown and stage2_rows / stage2_nodes /
+    stage2_unknown (nodes = stage1_nodes + stage2_nodes; unknown = stage1_unknown + the positions a stage-2 row leaves
+    open).  host=True (with exact=False) runs the same staging on ``solve_host`` -- no GPU; `table` is then a dict or a
+    ``HostTable``."""
+    if not exact:
+        if split_plies:
+            raise ValueError("split_plies belongs to exact=True: the staged labelling does not split")
+        return _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors=True)
+    if host:
+        raise ValueError("host=True labels with exact=False only")
     import torch
     from .stats import LabelledSet
     t0 = time.perf_counter()
@@ -779,7 +1102,7 @@ def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None,
         children, legal = _children_dev(uniq)
         is_legal = legal != 0
         total_hits = 0
-        if table is None and not split_plies:
+        if table is None and not split_plies and not deep:
             batch = torch.cat([uniq, children.reshape(n * WIDTH, 2)]).contiguous()
             status, outcome, _, nodes, _ = _solve_dev(batch, node_budget, nodes_per_launch)
             p_status, p_out = status[:n], outcome[:n]
@@ -787,7 +1110,7 @@ def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None,
         else:
             # the deep search reaches the empty board, so the zero rows of the illegal slots stay out of the batch
             res = solve(torch.cat([uniq, children[is_legal]]).contiguous(), node_budget, nodes_per_launch, device, table=table,
-                        split_plies=split_plies)
+                        deep=True, split_plies=split_plies)
             status = torch.from_numpy(res.status).to(packed.device)
             outcome = torch.from_numpy(np.where(np.isnan(res.outcome), -1, res.outcome * 2).astype(np.int8)).to(packed.device)
             nodes = torch.from_numpy(res.nodes)
@@ -807,7 +1130,7 @@ def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None,
         # illegal child slots are zero rows (the empty board: too deep, never searched, 0 nodes)
         total_nodes = int(nodes.sum().item())
     report = {"positions": n_in, "distinct": n, "labelled": len(ls), "nodes": total_nodes}
-    if table is not None or split_plies:
+    if table is not None or split_plies or deep:
         report.update(table_log2_entries=table.log2_entries if table is not None else None, table_hits=total_hits,
                       split_plies=int(split_plies))
     report.update({name: int(counts[code]) for code, name in STATUS_NAMES.items()})

@@ -728,6 +728,37 @@ int c4_solve_deep_dev(int device, void *hip_stream, c4_solve_table *table, const
 int c4_solve_deep(int device, c4_solve_table *table, const uint64_t *color0, const uint64_t *color1, int64_t n, int64_t node_budget,
                   int64_t nodes_per_launch, int8_t *status, int8_t *outcome, int8_t *final_age, int64_t *nodes, int64_t *table_hits);
 
+/* -- the deep search from a root window per row (c4_solve.hip) ----------------------------------------------------------- */
+/* c4_solve_window_dev / c4_solve_window are c4_solve_deep_dev / c4_solve_deep with the root's alpha-beta window given per
+ * row: alpha, beta int8 [n] on the mover's score (a game the mover wins at age a scores 43 - a, one the mover loses
+ * a - 43, a draw 0), -42 <= alpha < beta <= 42.  Both NULL: the full window (-42, 42) for every row; one NULL, or a bad
+ * window in any row: C4_EINVAL, the message names the first bad row, nothing is launched.  The search is fail-hard
+ * alpha-beta from that window, and a row that is searched to the end (status C4_SOLVE_SOLVED) answers with
+ *   score  int8, the mover's score as the root returns it
+ *   bound  int8, that score's kind against the caller's window:
+ *            C4_SOLVE_BOUND_EXACT  alpha < score < beta: the position's exact score
+ *            C4_SOLVE_BOUND_LOWER  score >= beta: the exact score is at least `score`
+ *            C4_SOLVE_BOUND_UPPER  score <= alpha: the exact score is at most `score`
+ *          The score of a bound may lie beyond the window (a mover who wins at once returns 42 - age whatever the window
+ *          is, a root that is decided without a move returns its value as it is); it is a true bound of its kind always.
+ *   outcome, final_age  as c4_solve_deep where bound is exact, else -1.
+ * Rows of every other status have score 0, bound C4_SOLVE_BOUND_NONE and the outcome and final_age c4_solve_deep gives
+ * them.  Statuses, nodes, table, table_hits, node_budget and nodes_per_launch are c4_solve_deep's; a window never makes a
+ * table-free search enter more nodes than a window that contains it.  A table may be shared between windowed and exact
+ * calls in any order: its entries are true bounds of their positions whatever window found them.  With (-1, 1) the score
+ * is the sign of the outcome for the mover; with (v - 1, v) it says whether the score is at least v. */
+#define C4_SOLVE_BOUND_NONE  0
+#define C4_SOLVE_BOUND_LOWER  1
+#define C4_SOLVE_BOUND_UPPER  2
+#define C4_SOLVE_BOUND_EXACT  3
+int c4_solve_window_dev(int device, void *hip_stream, c4_solve_table *table, const int64_t *boards_dev, const int8_t *alpha_dev,
+                        const int8_t *beta_dev, int64_t n, int64_t node_budget, int64_t nodes_per_launch, int8_t *status_dev,
+                        int8_t *score_dev, int8_t *bound_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev,
+                        int64_t *table_hits_dev);
+int c4_solve_window(int device, c4_solve_table *table, const uint64_t *color0, const uint64_t *color1, const int8_t *alpha,
+                    const int8_t *beta, int64_t n, int64_t node_budget, int64_t nodes_per_launch, int8_t *status, int8_t *score,
+                    int8_t *bound, int8_t *outcome, int8_t *final_age, int64_t *nodes, int64_t *table_hits);
+
 int c4_abi_version(void);
 
 #ifdef __cplusplus

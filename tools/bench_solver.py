@@ -11,7 +11,11 @@
 
     python tools/bench_solver.py --table [--budget-log2 20] [--out profiles/solver_table.json]
 
-  the deep search, its transposition table and the split instead: see bench_table below"""
+  the deep search, its transposition table and the split instead: see bench_table below
+
+    python tools/bench_solver.py --window [--part open,seven,seven_big] [--out profiles/solver_window.json]
+
+  labelling by outcome (label(exact=False)) against the exact labelling: see bench_window below"""
 import argparse
 import json
 import os
@@ -32,10 +36,15 @@ ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
 ap.add_argument("--out", default=None)
 ap.add_argument("--table", action="store_true", help="measure the deep search and its transposition table instead (below)")
 ap.add_argument("--budget-log2", type=int, default=20, help="--table: the node budget of one row in the budgeted parts")
+ap.add_argument("--window", action="store_true", help="measure the labelling by outcome windows instead (below)")
+ap.add_argument("--part", default="open,seven,seven_big", help="--window: the parts to run; the others are kept from the file")
+ap.add_argument("--big-budget-log2", type=int, default=24, help="--window: the node budget of one row in seven_big")
+ap.add_argument("--big-count", type=int, default=4096, help="--window: seven_big takes the first N of the 4,096 positions")
 args = ap.parse_args()
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "solver_table.json" if args.table else "solver.json")
-out = {"command": "python tools/bench_solver.py%s --out profiles/%s" % (" --table" if args.table else "", os.path.basename(args.out)),
+    args.out = os.path.join(ROOT, "profiles", "solver_window.json" if args.window else "solver_table.json" if args.table else "solver.json")
+out = {"command": "python tools/bench_solver.py%s --out profiles/%s" % (" --window" if args.window else " --table" if args.table else "",
+                                                                       os.path.basename(args.out)),
        "device": torch.cuda.get_device_name(0)}
 
 
@@ -139,8 +148,67 @@ def bench_table():
     dump()
 
 
+def bench_window():
+    """--window: writes profiles/solver_window.json (single runs; nothing is gated on these figures)
+
+      open          the 62 roots of tests/golden/solver_open.npz (25..32 empty squares) through label(exact=True) and
+                    label(exact=False), table-free and with a fresh Table(24) each: nodes (per stage), rows, seconds
+      seven         random_openings(7, 4096, seed) for seed 0 and for seed 7 (the positions of profiles/solver_table.json's
+                    seven_ply) through label(exact=False), Table(27) cleared per run, 2^20 nodes a row: labelled, unknown,
+                    nodes per stage, seconds; label_values on the same positions and a cleared table
+      seven_big     the first --big-count of the seed-0 positions, Table(27), 2^--big-budget-log2 nodes a row"""
+    import threading
+    from connect4_amd.solver import Table, label_values, random_openings
+    if os.path.exists(args.out):
+        out.update({k: v for k, v in json.load(open(args.out)).items() if k in ("open", "seven", "seven_big")})
+    parts = [p for p in args.part.split(",") if p]
+    threading.Thread(target=lambda: [(time.sleep(60), print("... %d min" % (i + 1), flush=True)) for i in range(60)], daemon=True).start()
+    solve(packed([random_playout(np.random.RandomState(1), 30)]))        # warm
+
+    def run(fn):
+        (ls, report), dt = timed(fn)
+        return {"report": report, "share_unknown": report["unknown"] / max(1, report["distinct"]), "seconds": dt}
+
+    if "open" in parts:
+        z = np.load(os.path.join(ROOT, "tests", "golden", "solver_open.npz"))
+        t = torch.from_numpy(np.stack([z["c0"], z["c1"]], axis=1).astype(np.uint64).view(np.int64)).cuda()
+        res = {"table_free": {"exact": run(lambda: label(t, deep=True)), "staged": run(lambda: label(t, exact=False))}}
+        with Table(24) as one, Table(24) as two:
+            res["2^24"] = {"exact": run(lambda: label(t, table=one)), "staged": run(lambda: label(t, exact=False, table=two))}
+        res["host_mirror_nodes"] = {"table_free": {"exact": 3827125, "staged": 968101, "stage1": 259422},
+                                    "note": "solver._Search on the same rows; the table-free device counts must equal these"}
+        out["open"] = res
+        print("open", json.dumps(res), flush=True)
+        dump()
+    if "seven" in parts:
+        seven = {}
+        with Table(27) as table:
+            for seed in (0, 7):
+                t = packed(random_openings(7, 4096, seed=seed))
+                table.clear()
+                seven["seed_%d" % seed] = {"staged": run(lambda: label(t, node_budget=1 << 20, table=table, exact=False))}
+                table.clear()
+                seven["seed_%d" % seed]["values_only"] = run(lambda: label_values(t, node_budget=1 << 20, table=table))
+                print("7-ply seed", seed, json.dumps(seven["seed_%d" % seed]), flush=True)
+        seven["budget"] = 1 << 20
+        seven["parent"] = {"labelled": 164, "share_unknown": 0.9599609375, "nodes": 25831368710, "seconds": 6.30,
+                           "note": "label(exact=True), seed 7, Table(27), 2^20 nodes a row: profiles/solver_table.json seven_ply[0]"}
+        out["seven"] = seven
+        dump()
+    if "seven_big" in parts:
+        t = packed(random_openings(7, 4096, seed=0)[:args.big_count])
+        with Table(27) as table:
+            big = run(lambda: label(t, node_budget=1 << args.big_budget_log2, table=table, exact=False))
+        out["seven_big"] = dict(big, budget=1 << args.big_budget_log2, positions=int(t.shape[0]), seed=0)
+        print("7-ply big", json.dumps(out["seven_big"]), flush=True)
+        dump()
+
+
 if args.table:
     bench_table()
+    sys.exit(0)
+if args.window:
+    bench_window()
     sys.exit(0)
 
 # 1. nodes per empty-square count: 512 seeded random playouts each, default budget

@@ -18,7 +18,16 @@ run_generations(test_sets={"endgame": "endgame.pth"}) read.  The labeller's repo
 reading self-play data: the reference's make_random_ips (scripts/generate_7ply.py), labelled by the same rule.  Positions
 with more than 24 empty squares need --table-log2 N (a shared transposition table of 2^N entries; solver.Table) and may
 use --split-plies K (solver.solve); --node-budget bounds the nodes of one row.  Positions the budget leaves unknown are
-dropped and counted."""
+dropped and counted.
+
+    python tools/make_test_set.py --openings 7 --count 4096 --outcome-only --table-log2 27 -o 7ply.pth
+    python tools/make_test_set.py --openings 8 --count 4096 --values-only --table-log2 27 -o 8ply.pth
+
+--outcome-only labels the same set from outcomes alone (label(exact=False)): one search per position with the window
+(-1, +1) and one null-window search per child that could keep the outcome, instead of exact scores of the position and all
+its children -- the same file wherever both label a row, for a fraction of the nodes.  --values-only stops after the first
+of those searches and writes values without priors (label_values), the kind of set the reference scores by value only.
+Both take positions of any depth with or without --table-log2, from --openings or from data sources; neither splits."""
 import argparse
 import json
 import os
@@ -49,6 +58,8 @@ def main(argv=None):
     ap.add_argument("--count", type=int, default=4096, help="with --openings: how many distinct positions")
     ap.add_argument("--table-log2", type=int, default=None, metavar="N", help="solve with a transposition table of 2^N entries")
     ap.add_argument("--split-plies", type=int, default=0, metavar="K")
+    ap.add_argument("--outcome-only", action="store_true", help="label from outcome windows and null windows (label(exact=False))")
+    ap.add_argument("--values-only", action="store_true", help="values without priors, one outcome-window search a position (label_values)")
     ap.add_argument("--node-budget", type=int, default=None)
     ap.add_argument("--min-age", type=int, default=18)
     ap.add_argument("--max-positions", type=int, default=None)
@@ -60,13 +71,18 @@ def main(argv=None):
         ap.error("give either sources or --openings")
     if a.openings is not None and not 0 <= a.openings <= 41:
         ap.error("--openings takes 0..41 plies")
-    if a.openings is not None and 42 - a.openings > 24 and a.table_log2 is None and not a.split_plies:
+    if a.outcome_only and a.values_only:
+        ap.error("--outcome-only and --values-only are two kinds of set: give one")
+    staged = a.outcome_only or a.values_only
+    if staged and a.split_plies:
+        ap.error("--split-plies belongs to the exact labelling")
+    if a.openings is not None and 42 - a.openings > 24 and a.table_log2 is None and not a.split_plies and not staged:
         ap.error("positions with more than 24 empty squares need --table-log2 (or --split-plies)")
     import torch
     import __graft_entry__ as entry
     entry.build()
     from connect4_amd import engine
-    from connect4_amd.solver import Table, label, random_openings
+    from connect4_amd.solver import Table, label, label_values, random_openings
     dev = torch.device("cuda", a.device)
     table = Table(a.table_log2, a.device) if a.table_log2 is not None else None
     parts, rows = [], 0
@@ -94,11 +110,17 @@ def main(argv=None):
         g = torch.Generator().manual_seed(a.seed)
         pick = torch.sort(torch.randperm(late, generator=g)[:a.max_positions]).values
         boards = boards[pick.to(dev)].contiguous()
-    ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, split_plies=a.split_plies)
+    if a.values_only:
+        ls, report = label_values(boards, node_budget=a.node_budget, device=a.device, table=table)
+    elif a.outcome_only:
+        ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, exact=False)
+    else:
+        ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, split_plies=a.split_plies)
     if table is not None:
         table.close()
     ls.save(a.output)
-    report = dict(report, rows_read=rows, distinct_late=late, min_age=a.min_age, output=a.output, openings=a.openings)
+    report = dict(report, rows_read=rows, distinct_late=late, min_age=a.min_age, output=a.output, openings=a.openings,
+                  mode="values-only" if a.values_only else "outcome-only" if a.outcome_only else "exact")
     print(json.dumps(report))
     hist = {k: int((ls.values == k).sum().item()) for k in (0.0, 0.5, 1.0)}
     print("%s: %d positions labelled (x wins %d, draws %d, o wins %d); %d unknown, %.2f s, %d nodes" % (
