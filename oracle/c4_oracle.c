@@ -977,3 +977,179 @@ void c4o_replay_stats(const c4o_replay *r, int64_t *lookups, int64_t *hits, int6
     if (hits) *hits = r->hits;
     if (table_entries) *table_entries = (int64_t)r->used;
 }
+
+/* ------------------------------------------------------------------ the exhaustive exact search (see c4_oracle.h)
+ * Plain on purpose: the value of a position is the maximum over every legal move of the negated value of the position it
+ * leads to, with c4o_make_move / c4o_wins deciding the end of the game -- and nothing else.  No window, no pruning, no
+ * ordering, no symmetry, no look at threats or parity, no early return on a winning move.  The memo is the one shortcut. */
+struct c4o_exact {
+    uint64_t *slot;      /* 0 = empty; else key | (score + 64) << 49 */
+    uint64_t mask;       /* entries - 1 */
+    uint64_t used;
+    uint64_t limit;      /* entries the memo may hold: 7/8 of its slots, so a probe always meets an empty slot */
+    int64_t  visited;    /* positions evaluated (memo misses) */
+    int64_t  hits;
+};
+
+#define EXACT_KEY_BITS 49
+#define EXACT_KEY_MASK (((uint64_t)1 << EXACT_KEY_BITS) - 1)
+#define EXACT_FULL 127   /* exact_value's answer when the memo cannot take another entry */
+
+/* The whole position in 49 bits: per column of h stones, occupied + BOTTOM is 2^h, and o's stones lie below bit h, so the
+ * 7-bit field 2^h + (o's stones) gives back h, o's stones and with them x's; no field carries into the next (at most
+ * 2^6 + 63).  BOTTOM makes every key non-zero. */
+static uint64_t exact_key(const c4o_board *b)
+{
+    return b->color[0] + (b->color[0] | b->color[1]) + BOTTOM;
+}
+
+static uint64_t exact_hash(uint64_t k)
+{
+    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ULL;
+    k ^= k >> 27; k *= 0x94d049bb133111ebULL;
+    return k ^ (k >> 31);
+}
+
+c4o_exact *c4o_exact_new(int log2_entries)
+{
+    if (log2_entries < C4O_EXACT_MIN_LOG2 || log2_entries > C4O_EXACT_MAX_LOG2) return NULL;
+    c4o_exact *x = (c4o_exact *)calloc(1, sizeof(*x));
+    if (!x) return NULL;
+    uint64_t entries = (uint64_t)1 << log2_entries;
+    x->slot = (uint64_t *)calloc(entries, sizeof(uint64_t));
+    if (!x->slot) { free(x); return NULL; }
+    x->mask = entries - 1;
+    x->limit = entries - entries / 8;
+    return x;
+}
+
+void c4o_exact_free(c4o_exact *x)
+{
+    if (!x) return;
+    free(x->slot);
+    free(x);
+}
+
+void c4o_exact_stats(const c4o_exact *x, int64_t *entries, int64_t *visited, int64_t *hits)
+{
+    if (entries) *entries = (int64_t)x->used;
+    if (visited) *visited = x->visited;
+    if (hits) *hits = x->hits;
+}
+
+/* The slot of `key`, or the empty slot it would take: linear probing, at most one pass over the memo (used <= limit <
+ * entries, so an empty slot ends it sooner). */
+static uint64_t exact_probe(const c4o_exact *x, uint64_t key)
+{
+    uint64_t at = exact_hash(key) & x->mask;
+    for (uint64_t step = 0; step <= x->mask; ++step) {
+        uint64_t w = x->slot[at];
+        if (w == 0 || (w & EXACT_KEY_MASK) == key) return at;
+        at = (at + 1) & x->mask;
+    }
+    return at; /* not reached: the memo always has empty slots */
+}
+
+/* The mover's score of an undecided position: 43 - final age if the mover wins, final age - 43 if it loses, 0 for a
+ * draw, under best play by both.  EXACT_FULL if the memo is full. */
+static int exact_value(c4o_exact *x, const c4o_board *b)
+{
+    uint64_t key = exact_key(b);
+    uint64_t at = exact_probe(x, key);
+    if (x->slot[at] != 0) {
+        x->hits += 1;
+        return (int)((x->slot[at] >> EXACT_KEY_BITS) & 0x7f) - 64;
+    }
+    if (x->used >= x->limit) return EXACT_FULL;
+    x->visited += 1;
+    int best = -64;
+    int mask = c4o_valid_mask(b);
+    for (int col = 0; col < WIDTH; ++col) {
+        if (!((mask >> col) & 1)) continue;
+        c4o_board child = *b;
+        int r = c4o_make_move(&child, col);
+        int v;
+        if (r == C4O_DRAW) v = 0;
+        else if (r != C4O_NONE) v = 43 - child.age;   /* only the side that moved can have won (board.py:166-168) */
+        else {
+            v = exact_value(x, &child);
+            if (v == EXACT_FULL) return EXACT_FULL;
+            v = -v;
+        }
+        if (v > best) best = v;
+    }
+    /* the searches below have filled other slots: find this position's again */
+    if (x->used >= x->limit) return EXACT_FULL;
+    at = exact_probe(x, key);
+    x->slot[at] = key | ((uint64_t)(best + 64) << EXACT_KEY_BITS);
+    x->used += 1;
+    return best;
+}
+
+/* A position the game can show: stones of the two sides apart, on the board, none floating, o has as many as x or one
+ * more, not both sides with four in a row. */
+static int exact_is_position(uint64_t c0, uint64_t c1)
+{
+    uint64_t occ = c0 | c1;
+    if ((c0 & c1) || (occ & ~(BOTTOM * (((uint64_t)1 << HEIGHT) - 1)))) return 0;
+    for (int c = 0; c < WIDTH; ++c) {
+        uint64_t col = (occ >> (H1 * c)) & COL1;
+        if (col & (col + 1)) return 0;
+    }
+    int d = popcnt64(c0) - popcnt64(c1);
+    if (d < 0 || d > 1) return 0;
+    return !(c4o_wins(c0) && c4o_wins(c1));
+}
+
+int64_t c4o_exact_scores(c4o_exact *x, const uint64_t *c0, const uint64_t *c1, int64_t n, int8_t *score,
+                         int8_t *child_score, int8_t *status)
+{
+    int64_t full = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        int8_t *kids = child_score + i * WIDTH;
+        for (int c = 0; c < WIDTH; ++c) kids[c] = C4O_EXACT_NO_MOVE;
+        score[i] = 0;
+        if (!exact_is_position(c0[i], c1[i])) { status[i] = C4O_EXACT_INVALID; continue; }
+        c4o_board b;
+        c4o_board_from_bits(&b, c0[i], c1[i]);
+        if (b.result != C4O_NONE) {
+            /* the game ended at this age: the side that moved last has won, or it is a draw */
+            status[i] = C4O_EXACT_FINISHED;
+            score[i] = (int8_t)(b.result == C4O_DRAW ? 0 : b.age - 43);
+            if (b.result != C4O_DRAW && (b.result == C4O_OWIN) == ((b.age & 1) == 0)) score[i] = (int8_t)(43 - b.age);
+            continue;
+        }
+        int mask = c4o_valid_mask(&b);
+        int best = -64, ok = 1;
+        for (int col = 0; col < WIDTH && ok; ++col) {
+            if (!((mask >> col) & 1)) continue;
+            c4o_board child = b;
+            int r = c4o_make_move(&child, col);
+            int v;
+            if (r == C4O_DRAW) v = 0;
+            else if (r != C4O_NONE) v = 43 - child.age;
+            else {
+                v = exact_value(x, &child);
+                if (v == EXACT_FULL) { ok = 0; break; }
+                v = -v;
+            }
+            kids[col] = (int8_t)v;
+            if (v > best) best = v;
+        }
+        if (ok) {
+            /* the root through the same function, so that it is in the memo and checked against its children's maximum */
+            int v = exact_value(x, &b);
+            if (v == EXACT_FULL) ok = 0;
+            else if (v != best) return -1;
+        }
+        if (!ok) {
+            for (int c = 0; c < WIDTH; ++c) kids[c] = C4O_EXACT_NO_MOVE;
+            status[i] = C4O_EXACT_CAPACITY;
+            full += 1;
+            continue;
+        }
+        score[i] = (int8_t)best;
+        status[i] = C4O_EXACT_SEARCHED;
+    }
+    return full;
+}

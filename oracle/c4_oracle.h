@@ -164,6 +164,38 @@ void        c4o_replay_apply(c4o_replay *r, int m, const int32_t *game_of, const
 int         c4o_replay_game(const c4o_replay *r, int i, c4o_move_record *rec /* cap 42 */, int *result);
 void        c4o_replay_stats(const c4o_replay *r, int64_t *lookups, int64_t *hits, int64_t *table_entries);
 
+/* ---- the exhaustive exact search: the yardstick of the exact solver (connect4_amd/csrc/c4_solve.hip, solver.py) ----
+ * The reference defines a position's exact value by GridSearch(plies >= empty squares): an exhaustive minimax with its
+ * terminal scoring (grid_search.py:21-71).  This is that search on the solver's integer score, and it STAYS PLAIN:
+ *   - no alpha-beta, no window, no threat or parity reasoning, no move ordering, no symmetry, no early return on a
+ *     winning move;
+ *   - every legal move (c4o_valid_mask) of every visited position is tried with c4o_make_move, and the end of a game is
+ *     what c4o_make_move / c4o_wins say it is;
+ *   - the only shortcut is the memo: keyed by the whole position, exact values only, written after all moves of the
+ *     position have been searched, valid across rows and calls;
+ *   - probing is bounded: a memo that cannot take another entry ends the row with C4O_EXACT_CAPACITY, it never loops.
+ * Anything cleverer belongs to the code under test, not here.
+ *
+ * The score is the mover's: 43 - final age if the mover wins under best play, final age - 43 if it loses, 0 for a draw
+ * (negamax of what c4_solve.hip documents). */
+#define C4O_EXACT_MIN_LOG2 4
+#define C4O_EXACT_MAX_LOG2 30
+#define C4O_EXACT_SEARCHED 0   /* an undecided position: score and child_score are filled */
+#define C4O_EXACT_FINISHED 1   /* the game is over: score is the mover's score of the result, no children */
+#define C4O_EXACT_INVALID  2   /* no position: overlapping, floating or off-board stones, wrong counts, two winners */
+#define C4O_EXACT_CAPACITY 3   /* the memo is full: no answer (a larger memo, or a new one, answers) */
+#define C4O_EXACT_NO_MOVE  (-128) /* child_score of a full column, and of every column of a row without an answer */
+
+typedef struct c4o_exact c4o_exact;
+c4o_exact *c4o_exact_new(int log2_entries);  /* a memo of 2^log2_entries eight-byte words, 7/8 of them usable; NULL: bad size / no memory */
+void       c4o_exact_free(c4o_exact *x);
+/* Row i: score[i], child_score[i][col] = the score of the position after the move in col, seen from row i's mover (so
+ * score[i] is their maximum), status[i] = C4O_EXACT_*.  Returns the number of rows that ended with C4O_EXACT_CAPACITY,
+ * or -1 if a memoised root value contradicts its children's (never, unless the memo is corrupt). */
+int64_t    c4o_exact_scores(c4o_exact *x, const uint64_t *c0, const uint64_t *c1, int64_t n, int8_t *score,
+                            int8_t *child_score /* [n][7] */, int8_t *status);
+void       c4o_exact_stats(const c4o_exact *x, int64_t *entries, int64_t *visited, int64_t *hits);
+
 #ifdef __cplusplus
 }
 #endif

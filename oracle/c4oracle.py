@@ -147,6 +147,12 @@ def lib():
         L.c4o_replay_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.c4o_replay_game.argtypes = [C.c_void_p, C.c_int, C.POINTER(MoveRecord), C.POINTER(C.c_int)]
         L.c4o_replay_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
+        L.c4o_exact_new.argtypes = [C.c_int]
+        L.c4o_exact_new.restype = C.c_void_p
+        L.c4o_exact_free.argtypes = [C.c_void_p]
+        L.c4o_exact_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.c4o_exact_scores.restype = C.c_int64
+        L.c4o_exact_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
         _lib = L
     return _lib
 
@@ -366,6 +372,72 @@ class ReplayPool:
         if self._p:
             lib().c4o_replay_free(self._p)
             self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+EXACT_SEARCHED, EXACT_FINISHED, EXACT_INVALID, EXACT_CAPACITY = 0, 1, 2, 3
+EXACT_NO_MOVE = -128
+
+
+class ExactCapacityError(RuntimeError):
+    """The memo of an ``Exact`` could not take another entry: the rows concerned have no answer."""
+
+
+class Exact:
+    """The exhaustive exact search (c4o_exact_*): every legal move of every position, a memo of exact values keyed by the
+    whole position, nothing else -- see c4_oracle.h.  One memo of ``2 ** log2_entries`` eight-byte words serves every call."""
+
+    def __init__(self, log2_entries=24):
+        self._p = lib().c4o_exact_new(int(log2_entries))
+        if not self._p:
+            raise ValueError("no memo of 2^%r entries" % (log2_entries,))
+        self.log2_entries = int(log2_entries)
+
+    def scores_raw(self, c0, c1):
+        """(score int8 [n], child_score int8 [n, 7], status int8 [n]) of the rows (c0[i], c1[i]); rows the memo is too
+        small for have the status EXACT_CAPACITY."""
+        c0 = np.ascontiguousarray(c0, dtype=np.uint64).reshape(-1)
+        c1 = np.ascontiguousarray(c1, dtype=np.uint64).reshape(-1)
+        assert c0.shape == c1.shape
+        n = len(c0)
+        score = np.zeros(n, dtype=np.int8)
+        child = np.full((n, 7), EXACT_NO_MOVE, dtype=np.int8)
+        status = np.zeros(n, dtype=np.int8)
+        rc = lib().c4o_exact_scores(self._p, c0.ctypes.data, c1.ctypes.data, n, score.ctypes.data, child.ctypes.data,
+                                    status.ctypes.data)
+        if rc < 0:
+            raise RuntimeError("the exact oracle's memo contradicts itself (rc=%d)" % rc)
+        assert rc == int((status == EXACT_CAPACITY).sum())
+        return score, child, status
+
+    def scores(self, c0, c1):
+        """``scores_raw``, raising ExactCapacityError if a row has no answer for want of memo."""
+        score, child, status = self.scores_raw(c0, c1)
+        if (status == EXACT_CAPACITY).any():
+            raise ExactCapacityError("%d of %d rows exceed the memo of 2^%d entries" % (
+                int((status == EXACT_CAPACITY).sum()), len(status), self.log2_entries))
+        return score, child, status
+
+    def stats(self):
+        vals = [C.c_int64() for _ in range(3)]
+        lib().c4o_exact_stats(self._p, *[C.byref(v) for v in vals])
+        return dict(zip(("entries", "visited", "hits"), [v.value for v in vals]))
+
+    def close(self):
+        if self._p:
+            lib().c4o_exact_free(self._p)
+            self._p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:

@@ -176,3 +176,27 @@ def host_oracle(cache=None):
         return out
 
     return exact_score_of_rows
+
+
+def exact_oracle(oracle, log2_entries=26, warm_rows=None):
+    """exact_score_of_rows from the oracle's exhaustive search (oracle/c4_oracle.c c4o_exact_scores: every legal move of every
+    position, a memo of exact values, nothing of the solver's reasoning) -- a yardstick that shares no rule with the search
+    that wrote the table.  `oracle`: the module oracle.c4oracle.  One memo of 2^log2_entries words serves every call of the
+    returned function; warm_rows (uint64 [m, 2]), searched first, put the positions below them into it, so that the
+    entries of a table those rows filled are memo hits.  Rows a full memo cannot answer go to a fresh one; a position that
+    is finished or invalid is UNSOLVED."""
+    state = {"memo": oracle.Exact(log2_entries)}
+
+    def exact_score_of_rows(rows):
+        rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+        score, _, status = state["memo"].scores_raw(rows[:, 0], rows[:, 1])
+        full = np.nonzero(status == oracle.EXACT_CAPACITY)[0]
+        if len(full):
+            state["memo"].close()
+            state["memo"] = oracle.Exact(log2_entries)
+            score[full], _, status[full] = state["memo"].scores_raw(rows[full, 0], rows[full, 1])
+        return np.where(status == oracle.EXACT_SEARCHED, score.astype(np.int64), UNSOLVED)
+
+    if warm_rows is not None:
+        exact_score_of_rows(warm_rows)
+    return exact_score_of_rows

@@ -1,7 +1,14 @@
 """The exact solver on the GPU (connect4_amd/csrc/c4_solve.hip behind connect4_amd/solver.py): against the unmodified
-reference's exhaustive search (tests/golden/solver.npz), against the device grid search that is pinned to it, against the
-host mirror's answers on deeper positions (tests/golden/solver_deep.npz), and -- where no yardstick reaches -- against
-itself: mirror symmetry and the fold over the children.  Then the labeller and tools/make_test_set.py end to end."""
+reference's exhaustive search (tests/golden/solver.npz, 3..10 empty squares), against the device grid search that is pinned
+to it, against the host mirror's answers on deeper positions (tests/golden/solver_deep.npz, 12..20 empty squares, node counts
+included), and against itself: mirror symmetry and the fold over the children.  Then the labeller and tools/make_test_set.py
+end to end.
+
+The yardsticks: up to 22 empty squares the kernel and the host mirror are both held to the oracle's exhaustive search --
+tests/test_gpu_solver_exact.py and tests/test_exact_oracle.py on tests/golden/solver_exact.npz -- which shares no rule with
+either and reproduces the reference's values bit for bit.  The host mirror's fixtures here add what that search does not
+have, the node counts; deeper than 22 empty squares the mirror, itself held to the oracle, and the self-checks below are what
+there is."""
 import importlib.util
 import json
 import os

@@ -1,0 +1,240 @@
+"""The exact solver on the GPU (connect4_amd/csrc/c4_solve.hip behind connect4_amd/solver.py) against the exhaustive oracle:
+tests/golden/solver_exact.npz, 7,456 positions at 1..22 empty squares with the scores of oracle/c4_oracle.c's c4o_exact_scores
+-- every legal move of every position and a memo, none of the solver's reasoning (tests/test_exact_oracle.py holds the file to
+the live oracle and the oracle to the unmodified reference).  The whole file is one batch.
+
+a. every entry point returns the oracle's outcome, final age and float64 value, bit for bit;
+b. the labels are the ones that follow from the oracle's child scores alone;
+c. a search from any root window reports the bound kind the oracle's score demands, and a true bound of that kind;
+d. after the rows with 12..18 empty squares have been searched against a table, every entry of it is a true bound of its
+   position by the oracle."""
+import time
+
+import numpy as np
+import pytest
+
+import solver_audit as A
+import solver_exact_cases as X
+from conftest import load_npz
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+TABLE_FREE_BUDGET = 1 << 20     # the host mirror walks the same tree: its dearest row of the file takes 74,256 nodes
+
+
+def packed(c0, c1):
+    return torch.from_numpy(np.stack([c0, c1], axis=1).astype(np.uint64).view(np.int64)).cuda()
+
+
+@pytest.fixture(scope="module")
+def gold():
+    """The fixture with what follows from its scores (computed once, shared, not modified)."""
+    from connect4_amd.solver import value_from_answer
+    z = load_npz("solver_exact.npz")
+    g = {k: z[k] for k in z.files}
+    g["age"] = 42 - g["empties"].astype(np.int64)
+    g["outcome"], g["final_age"] = X.answer_of_score(g["score"], g["age"])
+    g["value"] = value_from_answer(g["outcome"], g["final_age"])
+    g["t"] = packed(g["c0"], g["c1"])
+    return g
+
+
+def describe(g, i):
+    return "row %d (%#x, %#x), %d empty squares, strata %s" % (i, int(g["c0"][i]), int(g["c1"][i]), g["empties"][i],
+                                                                [name for name in X.STRATA if g[name][i]] or ["none"])
+
+
+def assert_oracles_answers(res, g, label, at=slice(None)):
+    from connect4_amd import _lib as L
+    ok = (res.status == L.SOLVE_SOLVED) & (res.outcome == g["outcome"][at]) & (res.final_age == g["final_age"][at])
+    for k in np.nonzero(~ok)[0][:5]:
+        i = int(np.arange(len(g["c0"]))[at][k])
+        print("%s: %s: the oracle's score %d (outcome %.1f, final age %d); the kernel: status %d, score %s (outcome %s, final age %d)" % (
+            label, describe(g, i), g["score"][i], g["outcome"][i], g["final_age"][i], res.status[k],
+            A.mover_score(res.outcome[k], res.final_age[k], g["age"][i]) if res.status[k] == L.SOLVE_SOLVED else None,
+            res.outcome[k], res.final_age[k]))
+    assert not (res.status == L.SOLVE_UNKNOWN).any(), "%s: %d rows UNKNOWN" % (label, (res.status == L.SOLVE_UNKNOWN).sum())
+    assert ok.all(), "%s: %d of %d rows differ from the oracle" % (label, (~ok).sum(), len(ok))
+    assert res.value.tobytes() == g["value"][at].tobytes()
+
+
+# -- a. the entry points -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["solve", "deep", "quota_256", "table_10", "table_20", "split_1", "split_2"])
+def test_every_entry_point_returns_the_oracles_answer(gold, mode):
+    from connect4_amd import solver
+    from connect4_amd.solver import Table, solve
+    assert gold["empties"].max() <= solver.MAX_EMPTIES
+    t0 = time.perf_counter()
+    if mode.startswith("table"):
+        with Table(int(mode[6:])) as table:
+            res = solve(gold["t"], table=table)
+        assert res.table_hits.sum() > 0
+    elif mode.startswith("split"):
+        res = solve(gold["t"], split_plies=int(mode[6:]))
+    else:
+        kw = {"solve": {}, "deep": {"deep": True}, "quota_256": {"nodes_per_launch": 256}}[mode]
+        res = solve(gold["t"], node_budget=TABLE_FREE_BUDGET, **kw)
+        assert (res.table_hits == 0).all() and res.nodes.max() < TABLE_FREE_BUDGET
+    print("%s: %d rows, %d nodes, the dearest row %d, %.2f s" % (mode, len(res.nodes), res.nodes.sum(), res.nodes.max(), time.perf_counter() - t0))
+    assert_oracles_answers(res, gold, mode)
+
+
+def test_host_rows_through_c4_solve(gold):
+    """The entry point that takes host arrays (c4_solve / c4_solve_deep): a sample across every depth."""
+    from connect4_amd.solver import solve
+    at = np.arange(0, len(gold["c0"]), 7)
+    rows = [(int(a), int(b)) for a, b in zip(gold["c0"][at], gold["c1"][at])]
+    assert_oracles_answers(solve(rows, node_budget=TABLE_FREE_BUDGET), gold, "c4_solve", at)
+    assert_oracles_answers(solve(rows, node_budget=TABLE_FREE_BUDGET, deep=True), gold, "c4_solve_deep", at)
+
+
+# -- b. the labels ---------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def want_labels(gold):
+    """The labels by the rule of the reference's generate_7ply.py:83-91, from the oracle's root and child scores alone."""
+    v, keep, prior = X.labels_of_children(gold["score"], gold["child_score"])
+    outcome = (np.where(gold["age"] & 1, -v, v) + 1) * 0.5
+    assert keep.any(axis=1).all() and np.array_equal(outcome, gold["outcome"])
+    return outcome, prior
+
+
+def assert_labels(ls, gold, outcome, prior, label):
+    rows = np.stack([gold["c0"], gold["c1"]], axis=1).astype(np.uint64)
+    assert np.array_equal(ls.boards.cpu().numpy().view(np.uint64), rows), label         # distinct rows, all solved, in order
+    values = ls.values.cpu().numpy()
+    assert values.dtype == np.float32 and values.tobytes() == outcome.astype(np.float32).tobytes(), label
+    if prior is None:
+        assert ls.priors is None
+        return
+    got = ls.priors.cpu().numpy()
+    bad = np.nonzero((got != prior).any(axis=1))[0]
+    for i in bad[:5]:
+        print("%s: %s: the children's scores %s give the prior %s; the labeller says %s" % (
+            label, describe(gold, int(i)), gold["child_score"][i].tolist(), prior[i].tolist(), got[i].tolist()))
+    assert got.dtype == np.float32 and len(bad) == 0 and got.tobytes() == prior.tobytes(), label
+
+
+@pytest.mark.parametrize("with_table", [False, True])
+def test_labels_follow_from_the_oracles_child_scores(gold, want_labels, with_table):
+    from connect4_amd.solver import Table, label, label_values, outcomes
+    outcome, prior = want_labels
+    table = Table(16) if with_table else None
+    try:
+        ls, report = label(gold["t"], table=table)
+        assert report["labelled"] == report["distinct"] == len(gold["c0"]) and report["unknown"] == 0
+        assert_labels(ls, gold, outcome, prior, "label")
+        ls, report = label(gold["t"], exact=False, table=table)
+        assert report["labelled"] == len(gold["c0"]) and report["unknown"] == 0 and report["exact"] is False
+        assert_labels(ls, gold, outcome, prior, "label(exact=False)")
+        assert outcomes(gold["t"], table=table).tobytes() == outcome.tobytes()
+        ls, report = label_values(gold["t"], table=table)
+        assert report["labelled"] == len(gold["c0"])
+        assert_labels(ls, gold, outcome, None, "label_values")
+    finally:
+        if table is not None:
+            table.close()
+
+
+@pytest.mark.parametrize("with_table", [False, True])
+def test_grid_triple_children_are_the_oracles(gold, with_table):
+    """Every row (the triples are Python objects, about a second): the children in column order
+    with the reference's absolute_value -- the bare result for a finished child (tree.py:27-38), else the float of the
+    child's exact score -- the root's search value, and Tree.best_move: the best child, ties to the higher column."""
+    from connect4_amd.board import Board
+    from connect4_amd.solver import Table, grid_triple, value_from_answer
+    at = np.arange(len(gold["c0"]))
+    boards = [Board.from_bits(int(a), int(b)) for a, b in zip(gold["c0"][at], gold["c1"][at])]
+    table = Table(16) if with_table else None
+    try:
+        got = grid_triple(boards, table=table)
+    finally:
+        if table is not None:
+            table.close()
+    for i, (move, value, tree) in zip(at, got):
+        kids = gold["child_score"][i].astype(np.int64)
+        names = [c for c in range(7) if kids[c] != X.NO_MOVE]
+        c_out, c_age = X.answer_of_score(-kids[names], gold["age"][i] + 1)
+        want = np.where(c_age == gold["age"][i] + 1, c_out, value_from_answer(c_out, c_age))
+        assert [c.name for c in tree.root.children] == names, describe(gold, i)
+        assert np.array([c.data.absolute_value for c in tree.root.children], dtype=np.float64).tobytes() == want.tobytes(), describe(gold, i)
+        assert np.float64(tree.root.data.search_value).tobytes() == gold["value"][i].tobytes(), describe(gold, i)
+        best = max(c for c in names if kids[c] == gold["score"][i])
+        assert (move, np.float64(value).tobytes()) == (best, want[names.index(best)].tobytes()), describe(gold, i)
+
+
+# -- c. windows ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_table", [False, True])
+def test_windowed_searches_obey_the_oracle(gold, with_table):
+    from connect4_amd import _lib as L
+    from connect4_amd.solver import Table, solve_window
+    assert (L.SOLVE_BOUND_LOWER, L.SOLVE_BOUND_UPPER, L.SOLVE_BOUND_EXACT) == (1, 2, 3)
+    exact = gold["score"].astype(np.int64)
+    table = Table(14) if with_table else None
+    kinds = set()
+    try:
+        for name, alpha, beta in X.windows(gold["score"]):
+            t0 = time.perf_counter()
+            res = solve_window(gold["t"], alpha, beta, table=table, node_budget=None if with_table else TABLE_FREE_BUDGET)
+            print("%s table, window %s: %d nodes, %d hits, %.2f s" % ("with a" if with_table else "no", name, res.nodes.sum(),
+                                                                      res.table_hits.sum(), time.perf_counter() - t0))
+            assert (res.status == L.SOLVE_SOLVED).all()
+            bad = X.window_violations(res.score, res.bound, alpha, beta, exact)
+            for k in bad[:5]:
+                print("window %s (%d, %d): %s: the oracle's score %d; the kernel returns %d as kind %d" % (
+                    name, alpha[k], beta[k], describe(gold, int(k)), exact[k], res.score[k], res.bound[k]))
+            assert len(bad) == 0, "window %s: %d of %d rows break the rule" % (name, len(bad), len(exact))
+            solved = res.bound == L.SOLVE_BOUND_EXACT
+            assert np.array_equal(res.final_age, np.where(solved, gold["final_age"], -1))
+            assert np.array_equal(np.nan_to_num(res.outcome, nan=-1.0), np.where(solved, gold["outcome"], -1.0))
+            kinds |= {(name, int(b)) for b in np.unique(res.bound)}
+    finally:
+        if table is not None:
+            table.close()
+    assert {("full", 3), ("outcome", 1), ("outcome", 2), ("outcome", 3), ("null_below", 1), ("null_above", 2)} <= kinds
+    assert {k for n, k in kinds if n == "full"} == {3} and {k for n, k in kinds if n.startswith("random")} == {1, 2, 3}
+
+
+# -- d. the table's entries ---------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def audit_rows(gold, oracle):
+    """The rows with 12..18 empty squares, and the oracle's exact_score_of_rows with those roots already searched: every
+    entry a search below them can write is then a memo hit."""
+    pick = (gold["empties"] >= 12) & (gold["empties"] <= 18)
+    rows = np.stack([gold["c0"][pick], gold["c1"][pick]], axis=1).astype(np.uint64)
+    t0 = time.perf_counter()
+    exact_score_of_rows = A.exact_oracle(oracle, 26, warm_rows=rows)
+    print("the oracle searches the %d roots in %.1f s" % (len(rows), time.perf_counter() - t0))
+    return pick, rows, exact_score_of_rows
+
+
+@pytest.mark.parametrize("log2_entries", [10, 14, 20])
+@pytest.mark.parametrize("how", ["exact", "windowed"])
+def test_table_entries_are_true_bounds_by_the_oracle(gold, audit_rows, log2_entries, how):
+    from connect4_amd import _lib as L
+    from connect4_amd.solver import Table, solve, solve_window
+    pick, rows, exact_score_of_rows = audit_rows
+    t = gold["t"][torch.from_numpy(np.nonzero(pick)[0]).cuda()].contiguous()
+    assert np.array_equal(exact_score_of_rows(rows), gold["score"][pick])
+    with Table(log2_entries) as table:
+        if how == "exact":
+            res = solve(t, table=table)
+            assert_oracles_answers(res, gold, "table 2^%d" % log2_entries, pick)
+            hits = res.table_hits.sum()
+        else:
+            hits = 0
+            for name, alpha, beta in X.windows(gold["score"]):
+                res = solve_window(t, alpha[pick], beta[pick], table=table)
+                assert (res.status == L.SOLVE_SOLVED).all()
+                assert len(X.window_violations(res.score, res.bound, alpha[pick], beta[pick], gold["score"][pick])) == 0, name
+                hits += res.table_hits.sum()
+        t0 = time.perf_counter()
+        report = {}
+        bad = A.audit(table.read(), log2_entries, exact_score_of_rows, report)
+    print("2^%d entries, %s searches: %s; %d violations; read + audit %.2f s" % (log2_entries, how, A.summary(report), len(bad),
+                                                                             time.perf_counter() - t0))
+    for v in bad[:10]:
+        print("   slot %d, word %#x: %s" % v)
+    assert bad == [] and report["left_out"] == 0          # every entry is a root or a position below one: in the memo
+    assert report["empties"][19:].sum() == 0 and min(report["lower"], report["upper"], report["exact"]) > 0 and hits > 0
