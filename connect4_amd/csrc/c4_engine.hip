@@ -606,9 +606,18 @@ __device__ __forceinline__ bool cache_probe(DevT &d, uint64_t c0, uint64_t c1, i
 {
     const uint64_t key = cache_key(c0, c1);
     const CacheEntry *e = cache_slot(d, key);
-    const uint64_t k = e->key, chk = e->check;
-    value = e->value;
-    prior_lane = lane < 7 ? e->prior[lane] : 0.0f;
+    // One memory round trip: key + check as one 16-byte load, and ONE payload word per lane -- lane k < 7 its prior[k], lane 7
+    // the value, i.e. word (lane + 1) & 7 of the eight floats behind the check -- both requested before the first wait.  The
+    // value then reaches the group's other lanes from lane 7 inside the wave (two DPP moves, no LDS crossbar).
+    const c4net::u32x4 kc = *reinterpret_cast<const c4net::u32x4 *>(e);
+    int wl = lane;
+    asm volatile("" : "+v"(wl));   // the word's index is computed here: hoisted, it would hold a register across the whole walk
+    const float word = (&e->value)[(wl + 1) & 7];
+    const uint64_t k = ((uint64_t)kc.y << 32) | kc.x, chk = ((uint64_t)kc.w << 32) | kc.z;
+    const int q3 = (int)dpp_u32<0xFF>(__float_as_uint(word));   // quad_perm [3,3,3,3]: lanes 4..7 hold lane 7's word
+    // row_half_mirror written to banks 0 and 2 only: lanes 0..3 take it from lanes 7..4, lanes 4..7 keep theirs
+    value = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(q3, q3, 0x141, 0xF, 0x5, false));
+    prior_lane = lane < 7 ? word : 0.0f;
     return k == key && chk == cache_check(key, value, prior_lane, lane);
 }
 template <class DevT>
