@@ -1,5 +1,5 @@
-// c4_solve.hip -- exact values of late-game positions (at most C4_SOLVE_MAX_EMPTIES empty squares) by
-// alpha-beta on gfx950, behind c4_solve / c4_solve_dev / c4_solve_children_dev of include/c4_engine.h.
+// c4_solve.hip -- exact values of positions by alpha-beta on gfx950, behind c4_solve / c4_solve_deep / c4_solve_window, their
+// _dev twins, the c4_solve_table_* calls and c4_solve_children_dev of include/c4_engine.h.
 //
 // The answer is the one the reference's GridSearch(plies >= empty squares) computes exhaustively
 // (oinkoink/grid_search.py:38-71: no evaluator is reached, the terminal scoring prefers faster wins and
@@ -10,35 +10,45 @@
 // The search keeps it from the side to move (negamax); outcome and final age leave the kernel, the float64
 // is formed from them by the caller as the reference writes it.
 //
-// Search.  One position per lane, iterative depth-first alpha-beta without a transposition table:
+// Search.  One position per lane, iterative depth-first alpha-beta:
 //   * a node is entered only when its mover cannot win at once (the root is checked, below the root the
 //     move list guarantees it), so an immediate win never costs a node;
 //   * the move list holds the non-losing moves only: a forced block if the opponent threatens, no move
 //     under a square the opponent wins on; an empty list is a loss two plies on;
 //   * the window is clipped to what is still possible (no win before age + 3, no loss before age + 4);
 //   * moves are ordered by the number of winning squares they create, ties centre first.
-// Pruning and ordering change the node count, never the value: the root's window is the whole range.
+// Pruning and ordering change the node count, never the value.
 //
 // Stack.  A frame is two 32-bit words (the ordered rest of the move list with the move played; alpha and
-// beta).  The top frame lives in registers, the frames below in LDS laid out [ply][lane] -- a lane's
-// column, so no lane reads another's and there is no barrier.  Boards are not stacked: the move played
-// is undone on the way back.
+// beta, and with a table the alpha the node's moves were entered with).  The top frame lives in registers, the
+// frames below in LDS laid out [ply][lane] -- a lane's column, so no lane reads another's and there is no
+// barrier.  Boards are not stacked: the move played is undone on the way back.
 //
 // Termination.  Every loop is bounded: a launch gives each lane a quota of nodes; a lane that has used
-// it stores its registers and frames to global memory and stops.  The host relaunches the unfinished
-// positions, compacted into a dense index list, until all are done or a position's total has reached
-// its budget (status UNKNOWN).  No lane waits for another lane, wave or workgroup; no atomics.
+// it parks -- its registers go into one word a row (pack_parked) and its frames into global memory -- and
+// stops.  The host relaunches the unfinished positions, compacted into a dense index list, until all are done
+// or a position's total has reached its budget (status UNKNOWN).  No lane waits for another lane, wave or
+// workgroup.
 //
-// Deep search (c4_solve_deep / c4_solve_deep_dev, k_solve_deep).  The same search -- the same enter_node, order_moves,
-// run_lane, frames and park / compact / relaunch loop -- with 42 plies of frames (2 x 42 x 64 x 4 B = 21 KiB of LDS, all
-// frames in LDS: seven one-wave workgroups still fit a CU) and, optionally, a transposition table in device memory that
-// every lane of every launch of every call shares.
+// One search, three options.  k_solve_init classifies every row and enters its root; k_solve_search<MAXP, T> is the
+// kernel that unparks, runs the quota (run_lane) and answers or parks again.  What a call chooses:
+//   * the frame depth MAXP.  k_solve_search<MAX_PLY, NoTable> (c4_solve, c4_solve_dev) has 24 plies of frames: 2 x 24 x 64
+//     x 4 B = 12 KiB of LDS a one-wave workgroup, thirteen workgroups a CU, rows with more empty squares are TOO_DEEP.
+//     k_solve_search<DEEP_MAX_PLY, TableRef> (c4_solve_deep*, c4_solve_window*) has 42: 21 KiB, all frames still in LDS,
+//     seven workgroups a CU, every position.  These two are the only instantiations.
+//   * the table T.  NoTable compiles no table, hit-count or window code.  A TableRef is a transposition table in device
+//     memory that every lane of every launch of every call shares, or none (e == nullptr: the table-free deep search).
+//   * the root window (c4_solve_window*, a Window of per-row arrays): alpha < beta on the mover's score instead of the
+//     whole range.
+// Table-free, neither the frame depth nor the launch quota changes a node count: it is solver._Search's.
+//
+// The table.
 //   * An entry is one aligned 64-bit word: the position's key in bits 0..48 (mover's stones + occupied + BOTTOM, which
 //     is injective), the score + 64 in bits 49..55, the bound's kind in bits 56..57 (lower, upper, exact; 0: empty).
 //     It is read by one relaxed 64-bit atomic load and written by one relaxed 64-bit atomic store: a reader sees a
 //     whole entry, old or new, and a hit compares the whole key, so it is a hit on this very position.
 //   * The score is the mover's 43 - final age form and is a true bound of the position's value whatever window it was
-//     found with, so an entry holds for every row, launch and call; a stale entry does not exist.
+//     found with, so an entry holds for every row, launch and call, windowed or not; a stale entry does not exist.
 //   * A node probes after enter_node says interior: an entry that closes the window is returned, another narrows
 //     it.  A node stores when it closes (its moves are used up, or one cuts off), against the window its moves were
 //     searched with: the frame keeps that alpha in bits 16..23 of its alpha / beta word.  Always replace.  Nodes with
@@ -46,17 +56,14 @@
 //   * Probe and store are straight-line code: the termination argument above holds word for word -- no lane waits for
 //     another, the only atomics are that load and that store.
 //   * Answers are exact and do not depend on the table (alpha-beta returns the same root value for every sound set of
-//     bounds).  NODE COUNTS WITH A TABLE ARE NOT DETERMINISTIC: they depend on what other lanes stored first.  With a
-//     null table they are, and they equal k_solve_run's and solver._Search's.
+//     bounds).  NODE COUNTS WITH A TABLE ARE NOT DETERMINISTIC: they depend on what other lanes stored first.
 //
-// Windowed search (c4_solve_window / c4_solve_window_dev).  The deep search with the root's window given per row, alpha <
-// beta on the mover's score, instead of the whole range: fail-hard alpha-beta, the search every node below a root
-// already is.  A row answers with the score its root returns and that score's kind against the caller's window
-// (C4_SOLVE_BOUND_*): exact inside it, else a lower bound at or above beta or an upper bound at or below alpha.  The root's
-// table probe and enter_node may narrow the window the moves are searched with -- the root's own entry is stored against
-// that one, like any node's -- but the kind is judged against the window the caller gave, which stays in the caller's
-// arrays while the row is parked.  Nothing else changes: entries are true bounds whatever window found them, so one table
-// serves windowed and exact calls alike, and the entry points that pass no window enter the nodes they always entered.
+// The root window.  Fail-hard alpha-beta from the caller's window, the search every node below a root already is.  A
+// row answers with the score its root returns and that score's kind against the caller's window (C4_SOLVE_BOUND_*):
+// exact inside it, else a lower bound at or above beta or an upper bound at or below alpha.  The root's table probe and
+// enter_node may narrow the window the moves are searched with -- the root's own entry is stored against that one,
+// like any node's -- but the kind is judged against the window the caller gave, which stays in the caller's arrays while
+// the row is parked.  A call without a window enters the nodes of the full window (-42, 42).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -75,10 +82,10 @@ namespace {
 constexpr int MAX_EMPTIES = C4_SOLVE_MAX_EMPTIES;
 constexpr int MAX_PLY = MAX_EMPTIES;            // frames of one lane (a node with one empty square is a leaf)
 constexpr int DEEP_MAX_EMPTIES = C4_SOLVE_DEEP_MAX_EMPTIES;
-constexpr int DEEP_MAX_PLY = DEEP_MAX_EMPTIES;  // k_solve_deep's frames: 2 x 42 x 64 x 4 B = 21 KiB of LDS
+constexpr int DEEP_MAX_PLY = DEEP_MAX_EMPTIES;  // k_solve_search<DEEP_MAX_PLY, TableRef>'s frames
 constexpr int TT_MIN_EMPTIES = 6;               // nodes nearer the end are cheaper to search than to look up
 constexpr int TT_MIN_LOG2 = 10, TT_MAX_LOG2 = 30;
-constexpr int BLOCK = 64;                       // one wave per workgroup: 2 x 24 x 64 x 4 B = 12 KiB of LDS
+constexpr int BLOCK = 64;                       // one wave per workgroup: 2 x MAXP x 64 x 4 B of LDS
 constexpr uint64_t BOARD = BOTTOM * COLMASK;    // the 42 cells
 constexpr int SCORE_MAX = 42;                   // beyond every score (the fastest win, at age 7, scores 36)
 constexpr int64_t DEFAULT_BUDGET = (int64_t)1 << 26;
@@ -188,15 +195,48 @@ C4_HD uint32_t pack_ab(int alpha, int beta) { return (uint32_t)(alpha + 64) | ((
 constexpr uint64_t TT_KEY_MASK = (1ULL << 49) - 1;
 constexpr int TT_LOWER = 1, TT_UPPER = 2, TT_EXACT = 3;
 
-struct NoTable {        // k_solve_run: no table code is compiled
+struct NoTable {        // k_solve_search<MAX_PLY, NoTable>: no table, hit-count or window code is compiled
     static constexpr bool compiled = false;
 };
 
-struct TableRef {       // k_solve_deep: e == nullptr is the table-free search
+struct TableRef {       // k_solve_search<DEEP_MAX_PLY, TableRef>: e == nullptr is the table-free search
     static constexpr bool compiled = true;
     uint64_t *e;
     int shift;          // 64 - log2(entries)
 };
+
+// The parked word: the top frame of a lane that has stopped at its quota, Work::misc[row].  alpha | beta << 8 | third << 16
+// | d << 24 | pending << 30, the scores + 64.  The third field is what the lane needs of ret and alpha0, which are never
+// both live: ret if the node at depth d has returned (pending) or there is no table code (T = NoTable), else the alpha0
+// of the top frame -- a pending lane closes no node with the alpha0 it had, so unpark_lane gives it alpha.
+C4_HD uint32_t pack_parked(int alpha, int beta, int third, int d, int pending)
+{
+    return pack_ab(alpha, beta) | ((uint32_t)(third + 64) << 16) | ((uint32_t)d << 24) | ((uint32_t)pending << 30);
+}
+
+template <class T>
+C4_HD uint32_t park_lane(const Lane &L)
+{
+    int third = L.ret;
+    if constexpr (T::compiled) third = L.pending ? L.ret : L.alpha0;
+    return pack_parked(L.alpha, L.beta, third, L.d, L.pending ? 1 : 0);
+}
+
+template <class T>
+C4_HD void unpark_lane(uint32_t w, Lane &L)
+{
+    L.alpha = (int)(w & 0xff) - 64;
+    L.beta = (int)((w >> 8) & 0xff) - 64;
+    L.d = (int)((w >> 24) & 0x3f);
+    L.pending = ((w >> 30) & 1) != 0;
+    const int third = (int)((w >> 16) & 0xff) - 64;
+    if constexpr (T::compiled) {
+        L.ret = L.pending ? third : 0;
+        L.alpha0 = L.pending ? L.alpha : third;
+    } else
+        L.ret = third;
+    L.done = false;
+}
 
 C4_HD uint64_t tt_key(uint64_t mine, uint64_t occ) { return mine + occ + BOTTOM; }
 C4_HD bool tt_covers(const TableRef t, int age) { return t.e != nullptr && CELLS - age >= TT_MIN_EMPTIES; }
@@ -388,7 +428,7 @@ void set_solve_err(const char *fmt, ...)
 // work memory of one pass over `n` rows (row-indexed; frames [ply][row])
 struct Work {
     uint64_t *c0, *c1;          // the position a stopped lane stands at
-    uint32_t *moves, *misc;     // its top frame: move list; alpha | beta << 8 | ret << 16 | d << 24 | pending << 30
+    uint32_t *moves, *misc;     // its top frame: the move list; the parked word (pack_parked)
     uint32_t *stk_moves, *stk_ab;
     int64_t n;
 };
@@ -401,15 +441,6 @@ struct LdsStack {
     __device__ __forceinline__ uint32_t &ab(int p) { return a[p][lane]; }
 };
 
-__device__ __forceinline__ void store_answer(const int64_t *boards, int64_t row, const Lane &L, int8_t *outcome, int8_t *final_age)
-{
-    const int age = popc64((uint64_t)boards[2 * row] | (uint64_t)boards[2 * row + 1]);
-    int o, fa;
-    root_answer(age, L.ret, o, fa);
-    outcome[row] = (int8_t)o;
-    final_age[row] = (int8_t)fa;
-}
-
 // A windowed search (c4_solve_window*): where a row's window lives and where its answer goes.  score == nullptr: not a
 // windowed search, nothing here is read.  alpha == nullptr (then beta is, too): every row has the full window.  The
 // caller's arrays are the window's home for as long as the row is parked: the parked word holds the window of the top
@@ -417,6 +448,7 @@ __device__ __forceinline__ void store_answer(const int64_t *boards, int64_t row,
 struct Window {
     const int8_t *alpha, *beta;
     int8_t *score, *bound;
+    Window at(int64_t lo) const { return Window{alpha ? alpha + lo : nullptr, beta ? beta + lo : nullptr, score ? score + lo : nullptr, bound ? bound + lo : nullptr}; }
 };
 
 C4_HD int bound_kind(int score, int alpha, int beta)
@@ -425,7 +457,7 @@ C4_HD int bound_kind(int score, int alpha, int beta)
 }
 
 // the root of windowed row `row` has returned `ret`: score and kind, and outcome and final age where the score is exact
-__device__ __forceinline__ void store_window_answer(const Window win, int64_t row, int age, int ret, int &outcome, int &final_age)
+__device__ __forceinline__ void window_answer(const Window win, int64_t row, int age, int ret, int &outcome, int &final_age)
 {
     const int a = win.alpha ? (int)win.alpha[row] : -SCORE_MAX, b = win.beta ? (int)win.beta[row] : SCORE_MAX;
     const int kind = bound_kind(ret, a, b);
@@ -436,12 +468,32 @@ __device__ __forceinline__ void store_window_answer(const Window win, int64_t ro
     if (kind == C4_SOLVE_BOUND_EXACT) root_answer(age, ret, outcome, final_age);
 }
 
+// The root of `row` has returned `ret` in k_solve_search: the row's outcome and final age, by window_answer in a windowed
+// search (T has window code and win.score is not null), else by root_answer.  Each branch stores for itself, as the two
+// kernels this one replaced did: a common tail is other device code.
+template <class T>
+__device__ __forceinline__ void store_root_answer(const int64_t *boards, int64_t row, int ret, const Window win, int8_t *outcome, int8_t *final_age)
+{
+    int o, fa;
+    if constexpr (T::compiled) {
+        if (win.score) {
+            window_answer(win, row, popc64((uint64_t)boards[2 * row] | (uint64_t)boards[2 * row + 1]), ret, o, fa);
+            outcome[row] = (int8_t)o;
+            final_age[row] = (int8_t)fa;
+            return;
+        }
+    }
+    root_answer(popc64((uint64_t)boards[2 * row] | (uint64_t)boards[2 * row + 1]), ret, o, fa);
+    outcome[row] = (int8_t)o;
+    final_age[row] = (int8_t)fa;
+}
+
 // one lane per row: status, the answers that need no search, the root of the others; unfinished[row] = 1
-// for a row that k_solve_run has to continue
-// for the deep search (`deep`): every depth is searchable, the root probes the table `tt` like any interior node, and the
-// parked word carries alpha0 where k_solve_run's carries ret (neither is read: the root is not pending); hits: or null;
+// for a row that k_solve_search has to continue
+// deep: the row goes to k_solve_search<DEEP_MAX_PLY, TableRef> -- every depth is searchable and the root probes the table
+// `tt` like any interior node -- else to k_solve_search<MAX_PLY, NoTable>; hits: or null;
 // win: a windowed search's arrays (the root starts from the row's window, and a row answered here -- an immediate win, a
-// leaf root, a table entry that closes the window -- is judged like one answered by k_solve_deep), or nulls
+// leaf root, a table entry that closes the window -- is judged like one answered by k_solve_search), or nulls
 __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict__ boards, int64_t n, int64_t node_budget, Work w,
                                                       int8_t *__restrict__ status, int8_t *__restrict__ outcome,
                                                       int8_t *__restrict__ final_age, int64_t *__restrict__ nodes,
@@ -478,9 +530,9 @@ __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict_
                     L.done = true;
                 }
             }
-            L.ret = L.done ? L.ret : L.alpha;       // the parked word's third field: alpha0
+            L.ret = L.done ? L.ret : L.alpha;       // a root that parks is not pending: the third field is its alpha0 (pack_parked)
         }
-        if (L.done && win.score) store_window_answer(win, row, popc64(c0 | c1), L.ret, o, fa);
+        if (L.done && win.score) window_answer(win, row, popc64(c0 | c1), L.ret, o, fa);
         else if (L.done) root_answer(popc64(c0 | c1), L.ret, o, fa);
         else if (nd >= node_budget) st = C4_SOLVE_UNKNOWN;
         else {
@@ -488,7 +540,7 @@ __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict_
             w.c0[row] = L.c0;
             w.c1[row] = L.c1;
             w.moves[row] = L.moves;
-            w.misc[row] = pack_ab(L.alpha, L.beta) | ((uint32_t)(L.ret + 64) << 16);
+            w.misc[row] = pack_parked(L.alpha, L.beta, L.ret, 0, 0);     // depth 0, not pending
         }
     }
     status[row] = (int8_t)st;
@@ -499,15 +551,17 @@ __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict_
     if (hits) hits[row] = hit ? 1 : 0;
 }
 
-// one lane per unfinished row, through the dense list `active`: load, search up to the quota, store
-__global__ void __launch_bounds__(BLOCK) k_solve_run(const int64_t *__restrict__ boards, const int32_t *__restrict__ active, int32_t m,
-                                                     int64_t node_budget, int64_t nodes_per_launch, Work w,
-                                                     int8_t *__restrict__ status, int8_t *__restrict__ outcome,
-                                                     int8_t *__restrict__ final_age, int64_t *__restrict__ nodes,
-                                                     uint8_t *__restrict__ unfinished)
+// One lane per unfinished row, through the dense list `active`: unpark, search up to the quota, answer or park again.
+// MAXP: the frames a lane has, in LDS and in `w`.  T: NoTable -- tt, hits and win are not read -- or TableRef.
+template <int MAXP, class T>
+__global__ void __launch_bounds__(BLOCK) k_solve_search(const int64_t *__restrict__ boards, const int32_t *__restrict__ active, int32_t m,
+                                                        int64_t node_budget, int64_t nodes_per_launch, Work w, T tt,
+                                                        int8_t *__restrict__ status, int8_t *__restrict__ outcome,
+                                                        int8_t *__restrict__ final_age, int64_t *__restrict__ nodes,
+                                                        int64_t *__restrict__ hits, uint8_t *__restrict__ unfinished, Window win)
 {
-    __shared__ uint32_t s_moves[MAX_PLY][BLOCK];
-    __shared__ uint32_t s_ab[MAX_PLY][BLOCK];
+    __shared__ uint32_t s_moves[MAXP][BLOCK];
+    __shared__ uint32_t s_ab[MAXP][BLOCK];
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= m) return;
     const int64_t row = active[i];
@@ -517,15 +571,9 @@ __global__ void __launch_bounds__(BLOCK) k_solve_run(const int64_t *__restrict__
     L.c0 = w.c0[row];
     L.c1 = w.c1[row];
     L.moves = w.moves[row];
-    const uint32_t misc = w.misc[row];
-    L.alpha = (int)(misc & 0xff) - 64;
-    L.beta = (int)((misc >> 8) & 0xff) - 64;
-    L.ret = (int)((misc >> 16) & 0xff) - 64;
-    L.d = (int)((misc >> 24) & 0x3f);
-    L.pending = ((misc >> 30) & 1) != 0;
-    L.done = false;
-    if (L.d > MAX_PLY) L.d = MAX_PLY;
-    for (int p = 0; p < MAX_PLY; ++p) {
+    unpark_lane<T>(w.misc[row], L);
+    if (L.d > MAXP) L.d = MAXP;
+    for (int p = 0; p < MAXP; ++p) {        // the frames below the top one, from `w` into LDS
         if (p < L.d) {
             s_moves[p][threadIdx.x] = w.stk_moves[(int64_t)p * w.n + row];
             s_ab[p][threadIdx.x] = w.stk_ab[(int64_t)p * w.n + row];
@@ -534,10 +582,13 @@ __global__ void __launch_bounds__(BLOCK) k_solve_run(const int64_t *__restrict__
     const int64_t total = nodes[row];
     const int64_t left = node_budget - total;
     const int64_t quota = left < nodes_per_launch ? left : nodes_per_launch;
-    const int64_t used = run_lane<MAX_PLY>(L, stk, NoTable{}, quota);
+    const int64_t used = run_lane<MAXP>(L, stk, tt, quota);
     nodes[row] = total + used;
+    if constexpr (T::compiled) {
+        if (hits) hits[row] += L.hits;
+    }
     if (L.done) {
-        store_answer(boards, row, L, outcome, final_age);
+        store_root_answer<T>(boards, row, L.ret, win, outcome, final_age);
         unfinished[i] = 0;
         return;
     }
@@ -550,78 +601,8 @@ __global__ void __launch_bounds__(BLOCK) k_solve_run(const int64_t *__restrict__
     w.c0[row] = L.c0;
     w.c1[row] = L.c1;
     w.moves[row] = L.moves;
-    w.misc[row] = pack_ab(L.alpha, L.beta) | ((uint32_t)(L.ret + 64) << 16) | ((uint32_t)L.d << 24) | ((uint32_t)(L.pending ? 1 : 0) << 30);
-    for (int p = 0; p < MAX_PLY; ++p) {
-        if (p < L.d) {
-            w.stk_moves[(int64_t)p * w.n + row] = s_moves[p][threadIdx.x];
-            w.stk_ab[(int64_t)p * w.n + row] = s_ab[p][threadIdx.x];
-        }
-    }
-}
-
-// k_solve_run for positions of any depth, with or without a table (tt.e == nullptr).  The frames are DEEP_MAX_PLY deep, in
-// LDS and in `w`; the third field of the parked word is ret for a pending lane, else the top frame's alpha0.
-__global__ void __launch_bounds__(BLOCK) k_solve_deep(const int64_t *__restrict__ boards, const int32_t *__restrict__ active, int32_t m,
-                                                      int64_t node_budget, int64_t nodes_per_launch, Work w, TableRef tt,
-                                                      int8_t *__restrict__ status, int8_t *__restrict__ outcome,
-                                                      int8_t *__restrict__ final_age, int64_t *__restrict__ nodes,
-                                                      int64_t *__restrict__ hits, uint8_t *__restrict__ unfinished, Window win)
-{
-    __shared__ uint32_t s_moves[DEEP_MAX_PLY][BLOCK];
-    __shared__ uint32_t s_ab[DEEP_MAX_PLY][BLOCK];
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= m) return;
-    const int64_t row = active[i];
-    if (row < 0 || row >= w.n) return;
-    LdsStack stk{s_moves, s_ab, (int)threadIdx.x};
-    Lane L;
-    L.c0 = w.c0[row];
-    L.c1 = w.c1[row];
-    L.moves = w.moves[row];
-    const uint32_t misc = w.misc[row];
-    L.alpha = (int)(misc & 0xff) - 64;
-    L.beta = (int)((misc >> 8) & 0xff) - 64;
-    L.d = (int)((misc >> 24) & 0x3f);
-    L.pending = ((misc >> 30) & 1) != 0;
-    L.ret = L.pending ? (int)((misc >> 16) & 0xff) - 64 : 0;
-    L.alpha0 = L.pending ? L.alpha : (int)((misc >> 16) & 0xff) - 64;
-    L.done = false;
-    if (L.d > DEEP_MAX_PLY) L.d = DEEP_MAX_PLY;
-    for (int p = 0; p < DEEP_MAX_PLY; ++p) {
-        if (p < L.d) {
-            s_moves[p][threadIdx.x] = w.stk_moves[(int64_t)p * w.n + row];
-            s_ab[p][threadIdx.x] = w.stk_ab[(int64_t)p * w.n + row];
-        }
-    }
-    const int64_t total = nodes[row];
-    const int64_t left = node_budget - total;
-    const int64_t quota = left < nodes_per_launch ? left : nodes_per_launch;
-    const int64_t used = run_lane<DEEP_MAX_PLY>(L, stk, tt, quota);
-    nodes[row] = total + used;
-    if (hits) hits[row] += L.hits;
-    if (L.done) {
-        if (win.score) {
-            int o, fa;
-            store_window_answer(win, row, popc64((uint64_t)boards[2 * row] | (uint64_t)boards[2 * row + 1]), L.ret, o, fa);
-            outcome[row] = (int8_t)o;
-            final_age[row] = (int8_t)fa;
-        } else
-            store_answer(boards, row, L, outcome, final_age);
-        unfinished[i] = 0;
-        return;
-    }
-    if (total + used >= node_budget) {      // it would take a node beyond the budget to go on
-        status[row] = C4_SOLVE_UNKNOWN;
-        unfinished[i] = 0;
-        return;
-    }
-    unfinished[i] = 1;
-    w.c0[row] = L.c0;
-    w.c1[row] = L.c1;
-    w.moves[row] = L.moves;
-    w.misc[row] = pack_ab(L.alpha, L.beta) | ((uint32_t)((L.pending ? L.ret : L.alpha0) + 64) << 16) | ((uint32_t)L.d << 24) |
-                  ((uint32_t)(L.pending ? 1 : 0) << 30);
-    for (int p = 0; p < DEEP_MAX_PLY; ++p) {
+    w.misc[row] = park_lane<T>(L);
+    for (int p = 0; p < MAXP; ++p) {        // and back
         if (p < L.d) {
             w.stk_moves[(int64_t)p * w.n + row] = s_moves[p][threadIdx.x];
             w.stk_ab[(int64_t)p * w.n + row] = s_ab[p][threadIdx.x];
@@ -682,11 +663,19 @@ int pick_device(int device)
     return C4_OK;
 }
 
-// one pass: rows [0, n) of `boards`, n <= CHUNK_ROWS.  deep: k_solve_deep with the table `tt` (or none) and 42 plies of
-// parked frames (360 B a row), hits: table_hits or null; else k_solve_run
-int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t node_budget, int64_t per_launch, int8_t *status,
-                int8_t *outcome, int8_t *final_age, int64_t *nodes, bool deep = false, TableRef tt = TableRef{nullptr, 0},
-                int64_t *hits = nullptr, Window win = Window{nullptr, nullptr, nullptr, nullptr})
+// what every call answers, one entry a row; hits (a deep call's table_hits): or null
+struct Answers {
+    int8_t *status, *outcome, *final_age;
+    int64_t *nodes, *hits;
+    Answers at(int64_t lo) const { return Answers{status + lo, outcome + lo, final_age + lo, nodes + lo, hits ? hits + lo : nullptr}; }
+};
+
+constexpr Window NO_WINDOW{nullptr, nullptr, nullptr, nullptr};
+
+// one pass: rows [0, n) of `boards`, n <= CHUNK_ROWS.  deep: k_solve_search<DEEP_MAX_PLY, TableRef> with the table `tt` (or
+// none), 42 plies of parked frames (360 B a row) and the windows `win` (or none); else k_solve_search<MAX_PLY, NoTable>
+int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t node_budget, int64_t per_launch, bool deep, TableRef tt,
+                Answers out, Window win)
 {
     DevBuf mem, flags, act;
     const int max_ply = deep ? DEEP_MAX_PLY : MAX_PLY;
@@ -703,8 +692,8 @@ int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t no
     w.stk_moves = w.misc + n;
     w.stk_ab = w.stk_moves + (size_t)n * max_ply;
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(k_solve_init, dim3(grid), dim3(BLOCK), 0, stream, boards, n, node_budget, w, status, outcome, final_age, nodes,
-                       flags.as<uint8_t>(), deep, tt, hits, win);
+    hipLaunchKernelGGL(k_solve_init, dim3(grid), dim3(BLOCK), 0, stream, boards, n, node_budget, w, out.status, out.outcome, out.final_age,
+                       out.nodes, flags.as<uint8_t>(), deep, tt, out.hits, win);
     SOLVE_CHECK(hipGetLastError());
     std::vector<uint8_t> host_flags((size_t)n);
     std::vector<int32_t> active, next;
@@ -721,12 +710,14 @@ int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t no
         }
         const int32_t m = (int32_t)active.size();
         SOLVE_CHECK(hipMemcpyAsync(act.p, active.data(), (size_t)m * 4, hipMemcpyHostToDevice, stream));
+        const dim3 blocks((unsigned)((m + BLOCK - 1) / BLOCK));
         if (deep)
-            hipLaunchKernelGGL(k_solve_deep, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, boards, act.as<int32_t>(),
-                               m, node_budget, per_launch, w, tt, status, outcome, final_age, nodes, hits, flags.as<uint8_t>(), win);
+            hipLaunchKernelGGL((k_solve_search<DEEP_MAX_PLY, TableRef>), blocks, dim3(BLOCK), 0, stream, boards, act.as<int32_t>(), m, node_budget,
+                               per_launch, w, tt, out.status, out.outcome, out.final_age, out.nodes, out.hits, flags.as<uint8_t>(), win);
         else
-            hipLaunchKernelGGL(k_solve_run, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, boards, act.as<int32_t>(), m,
-                               node_budget, per_launch, w, status, outcome, final_age, nodes, flags.as<uint8_t>());
+            // NoTable{}, out.hits and win are arguments this instantiation never reads
+            hipLaunchKernelGGL((k_solve_search<MAX_PLY, NoTable>), blocks, dim3(BLOCK), 0, stream, boards, act.as<int32_t>(), m, node_budget,
+                               per_launch, w, NoTable{}, out.status, out.outcome, out.final_age, out.nodes, out.hits, flags.as<uint8_t>(), win);
         SOLVE_CHECK(hipGetLastError());
         SOLVE_CHECK(hipMemcpyAsync(host_flags.data(), flags.p, (size_t)m, hipMemcpyDeviceToHost, stream));
         SOLVE_CHECK(hipStreamSynchronize(stream));
@@ -738,11 +729,22 @@ int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t no
     return C4_OK;
 }
 
-int check_args(const void *boards, int64_t n, int64_t &node_budget, int64_t &per_launch, const void *status, const void *outcome,
-               const void *final_age, const void *nodes)
+// the device path of every entry point: n rows on the device, CHUNK_ROWS at a time
+int solve_rows(hipStream_t stream, const int64_t *boards, int64_t n, int64_t node_budget, int64_t per_launch, bool deep, TableRef tt,
+               Answers out, Window win)
+{
+    for (int64_t lo = 0; lo < n; lo += CHUNK_ROWS) {
+        const int64_t m = n - lo < CHUNK_ROWS ? n - lo : CHUNK_ROWS;
+        const int rc = solve_chunk(stream, boards + 2 * lo, m, node_budget, per_launch, deep, tt, out.at(lo), win.at(lo));
+        if (rc) return rc;
+    }
+    return C4_OK;
+}
+
+int check_args(int64_t n, int64_t &node_budget, int64_t &per_launch, const Answers &out)
 {
     if (n < 0) { set_solve_err("n < 0"); return C4_EINVAL; }
-    if (n > 0 && (!boards || !status || !outcome || !final_age || !nodes)) { set_solve_err("null argument"); return C4_EINVAL; }
+    if (n > 0 && (!out.status || !out.outcome || !out.final_age || !out.nodes)) { set_solve_err("null argument"); return C4_EINVAL; }
     if (node_budget < 0 || per_launch < 0) { set_solve_err("node_budget and nodes_per_launch must not be negative (0: the default)"); return C4_EINVAL; }
     if (node_budget == 0) node_budget = DEFAULT_BUDGET;
     if (per_launch == 0) per_launch = DEFAULT_PER_LAUNCH;
@@ -751,10 +753,10 @@ int check_args(const void *boards, int64_t n, int64_t &node_budget, int64_t &per
 }
 
 // the pointers of a windowed call: alpha and beta come together (both null: the full window for every row)
-int check_window_args(const void *alpha, const void *beta, int64_t n, const void *score, const void *bound)
+int check_window_args(const Window &win, int64_t n)
 {
-    if (n > 0 && (!score || !bound)) { set_solve_err("null argument"); return C4_EINVAL; }
-    if ((alpha == nullptr) != (beta == nullptr)) { set_solve_err("alpha and beta are given together, or both are null"); return C4_EINVAL; }
+    if (n > 0 && (!win.score || !win.bound)) { set_solve_err("null argument"); return C4_EINVAL; }
+    if ((win.alpha == nullptr) != (win.beta == nullptr)) { set_solve_err("alpha and beta are given together, or both are null"); return C4_EINVAL; }
     return C4_OK;
 }
 
@@ -798,6 +800,71 @@ int table_ref(const c4_solve_table *table, int device, TableRef &tt)
     return C4_OK;
 }
 
+// The checks of every entry point, in the order callers rely on: null and negative arguments; a windowed call's (`win` not
+// null) pointer pairing and, where its windows are in host memory, their ranges; the table's device.  Then n == 0 is
+// C4_OK before any device is touched, and the call's device is selected: the caller goes on if this returns C4_OK and n > 0.
+int check_call(int device, const c4_solve_table *table, bool have_boards, int64_t n, int64_t &node_budget, int64_t &per_launch,
+               const Answers &out, const Window *win, bool windows_on_host, TableRef &tt)
+{
+    if (n > 0 && !have_boards) { set_solve_err("null argument"); return C4_EINVAL; }
+    int rc = check_args(n, node_budget, per_launch, out);
+    if (rc == C4_OK && win) rc = check_window_args(*win, n);
+    if (rc == C4_OK && win && win->alpha && windows_on_host) rc = check_windows(win->alpha, win->beta, n);
+    if (rc == C4_OK) rc = table_ref(table, device, tt);
+    if (rc || n == 0) return rc;
+    return pick_device(device);
+}
+
+// The host-memory entry points: pack the boards, stage on the device the arrays the call has -- an entry of `host` or
+// `host_win` that is null is neither allocated nor copied -- search, and copy the answers back.  Nothing is written to
+// the caller's arrays unless the search returns C4_OK.
+int solve_staged(const uint64_t *color0, const uint64_t *color1, int64_t n, int64_t node_budget, int64_t per_launch, bool deep, TableRef tt,
+                 Answers host, Window host_win)
+{
+    std::vector<int64_t> packed((size_t)n * 2);
+    for (int64_t i = 0; i < n; ++i) {
+        packed[(size_t)(2 * i)] = (int64_t)color0[i];
+        packed[(size_t)(2 * i + 1)] = (int64_t)color1[i];
+    }
+    enum { NODES, HITS, STATUS, OUTCOME, AGE, SCORE, BOUND, ALPHA, BETA, ARRAYS };
+    struct Staged {
+        void *host;
+        size_t width;       // bytes an entry: the 8-byte arrays come first, so every array is aligned
+        bool upload;        // an input; else an answer, copied back
+        char *dev;
+    } arrays[ARRAYS];
+    arrays[NODES] = {host.nodes, 8, false, nullptr};
+    arrays[HITS] = {host.hits, 8, false, nullptr};
+    arrays[STATUS] = {host.status, 1, false, nullptr};
+    arrays[OUTCOME] = {host.outcome, 1, false, nullptr};
+    arrays[AGE] = {host.final_age, 1, false, nullptr};
+    arrays[SCORE] = {host_win.score, 1, false, nullptr};
+    arrays[BOUND] = {host_win.bound, 1, false, nullptr};
+    arrays[ALPHA] = {(void *)host_win.alpha, 1, true, nullptr};
+    arrays[BETA] = {(void *)host_win.beta, 1, true, nullptr};
+    size_t bytes = 0;
+    for (const Staged &a : arrays) bytes += a.host ? (size_t)n * a.width : 0;
+    DevBuf b, mem;
+    SOLVE_CHECK(b.get((size_t)n * 16));
+    SOLVE_CHECK(mem.get(bytes));
+    SOLVE_CHECK(hipMemcpy(b.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+    char *at = mem.as<char>();
+    for (Staged &a : arrays) {
+        if (!a.host) continue;
+        a.dev = at;
+        at += (size_t)n * a.width;
+        if (a.upload) SOLVE_CHECK(hipMemcpy(a.dev, a.host, (size_t)n * a.width, hipMemcpyHostToDevice));
+    }
+    const Answers out{(int8_t *)arrays[STATUS].dev, (int8_t *)arrays[OUTCOME].dev, (int8_t *)arrays[AGE].dev, (int64_t *)arrays[NODES].dev,
+                      (int64_t *)arrays[HITS].dev};
+    const Window win{(const int8_t *)arrays[ALPHA].dev, (const int8_t *)arrays[BETA].dev, (int8_t *)arrays[SCORE].dev, (int8_t *)arrays[BOUND].dev};
+    const int rc = solve_rows(nullptr, b.as<int64_t>(), n, node_budget, per_launch, deep, tt, out, win);
+    if (rc) return rc;
+    for (const Staged &a : arrays)
+        if (a.host && !a.upload) SOLVE_CHECK(hipMemcpy(a.host, a.dev, (size_t)n * a.width, hipMemcpyDeviceToHost));
+    return C4_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -807,46 +874,21 @@ const char *c4_solve_last_error(void) { return solve_err; }
 int c4_solve_dev(int device, void *hip_stream, const int64_t *boards_dev, int64_t n, int64_t node_budget, int64_t nodes_per_launch,
                  int8_t *status_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev)
 {
-    int rc = check_args(boards_dev, n, node_budget, nodes_per_launch, status_dev, outcome_dev, final_age_dev, nodes_dev);
+    const Answers out{status_dev, outcome_dev, final_age_dev, nodes_dev, nullptr};
+    TableRef tt;
+    const int rc = check_call(device, nullptr, boards_dev != nullptr, n, node_budget, nodes_per_launch, out, nullptr, false, tt);
     if (rc || n == 0) return rc;
-    rc = pick_device(device);
-    if (rc) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    for (int64_t lo = 0; lo < n; lo += CHUNK_ROWS) {
-        const int64_t m = n - lo < CHUNK_ROWS ? n - lo : CHUNK_ROWS;
-        rc = solve_chunk(stream, boards_dev + 2 * lo, m, node_budget, nodes_per_launch, status_dev + lo, outcome_dev + lo,
-                         final_age_dev + lo, nodes_dev + lo);
-        if (rc) return rc;
-    }
-    return C4_OK;
+    return solve_rows((hipStream_t)hip_stream, boards_dev, n, node_budget, nodes_per_launch, false, tt, out, NO_WINDOW);
 }
 
 int c4_solve(int device, const uint64_t *color0, const uint64_t *color1, int64_t n, int64_t node_budget, int64_t nodes_per_launch,
              int8_t *status, int8_t *outcome, int8_t *final_age, int64_t *nodes)
 {
-    if (n > 0 && (!color0 || !color1)) { set_solve_err("null argument"); return C4_EINVAL; }
-    int rc = check_args(color0, n, node_budget, nodes_per_launch, status, outcome, final_age, nodes);
+    const Answers out{status, outcome, final_age, nodes, nullptr};
+    TableRef tt;
+    const int rc = check_call(device, nullptr, color0 && color1, n, node_budget, nodes_per_launch, out, nullptr, false, tt);
     if (rc || n == 0) return rc;
-    rc = pick_device(device);
-    if (rc) return rc;
-    std::vector<int64_t> packed((size_t)n * 2);
-    for (int64_t i = 0; i < n; ++i) {
-        packed[(size_t)(2 * i)] = (int64_t)color0[i];
-        packed[(size_t)(2 * i + 1)] = (int64_t)color1[i];
-    }
-    DevBuf b, out;
-    SOLVE_CHECK(b.get((size_t)n * 16));
-    SOLVE_CHECK(out.get((size_t)n * 11));
-    int64_t *nodes_d = out.as<int64_t>();
-    int8_t *status_d = (int8_t *)(nodes_d + n), *outcome_d = status_d + n, *age_d = outcome_d + n;
-    SOLVE_CHECK(hipMemcpy(b.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-    rc = c4_solve_dev(device, nullptr, b.as<int64_t>(), n, node_budget, nodes_per_launch, status_d, outcome_d, age_d, nodes_d);
-    if (rc) return rc;
-    SOLVE_CHECK(hipMemcpy(nodes, nodes_d, (size_t)n * 8, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(status, status_d, (size_t)n, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(outcome, outcome_d, (size_t)n, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(final_age, age_d, (size_t)n, hipMemcpyDeviceToHost));
-    return C4_OK;
+    return solve_staged(color0, color1, n, node_budget, nodes_per_launch, false, tt, out, NO_WINDOW);
 }
 
 int c4_solve_table_create(int device, int log2_entries, c4_solve_table **out)
@@ -919,54 +961,21 @@ int c4_solve_deep_dev(int device, void *hip_stream, c4_solve_table *table, const
                       int64_t nodes_per_launch, int8_t *status_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev,
                       int64_t *table_hits_dev)
 {
-    int rc = check_args(boards_dev, n, node_budget, nodes_per_launch, status_dev, outcome_dev, final_age_dev, nodes_dev);
-    if (rc) return rc;
+    const Answers out{status_dev, outcome_dev, final_age_dev, nodes_dev, table_hits_dev};
     TableRef tt;
-    rc = table_ref(table, device, tt);
+    const int rc = check_call(device, table, boards_dev != nullptr, n, node_budget, nodes_per_launch, out, nullptr, false, tt);
     if (rc || n == 0) return rc;
-    rc = pick_device(device);
-    if (rc) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    for (int64_t lo = 0; lo < n; lo += CHUNK_ROWS) {
-        const int64_t m = n - lo < CHUNK_ROWS ? n - lo : CHUNK_ROWS;
-        rc = solve_chunk(stream, boards_dev + 2 * lo, m, node_budget, nodes_per_launch, status_dev + lo, outcome_dev + lo,
-                         final_age_dev + lo, nodes_dev + lo, true, tt, table_hits_dev ? table_hits_dev + lo : nullptr);
-        if (rc) return rc;
-    }
-    return C4_OK;
+    return solve_rows((hipStream_t)hip_stream, boards_dev, n, node_budget, nodes_per_launch, true, tt, out, NO_WINDOW);
 }
 
 int c4_solve_deep(int device, c4_solve_table *table, const uint64_t *color0, const uint64_t *color1, int64_t n, int64_t node_budget,
                   int64_t nodes_per_launch, int8_t *status, int8_t *outcome, int8_t *final_age, int64_t *nodes, int64_t *table_hits)
 {
-    if (n > 0 && (!color0 || !color1)) { set_solve_err("null argument"); return C4_EINVAL; }
-    int rc = check_args(color0, n, node_budget, nodes_per_launch, status, outcome, final_age, nodes);
-    if (rc) return rc;
+    const Answers out{status, outcome, final_age, nodes, table_hits};
     TableRef tt;
-    rc = table_ref(table, device, tt);
+    const int rc = check_call(device, table, color0 && color1, n, node_budget, nodes_per_launch, out, nullptr, false, tt);
     if (rc || n == 0) return rc;
-    rc = pick_device(device);
-    if (rc) return rc;
-    std::vector<int64_t> packed((size_t)n * 2);
-    for (int64_t i = 0; i < n; ++i) {
-        packed[(size_t)(2 * i)] = (int64_t)color0[i];
-        packed[(size_t)(2 * i + 1)] = (int64_t)color1[i];
-    }
-    DevBuf b, out;
-    SOLVE_CHECK(b.get((size_t)n * 16));
-    SOLVE_CHECK(out.get((size_t)n * 19));
-    int64_t *nodes_d = out.as<int64_t>(), *hits_d = nodes_d + n;
-    int8_t *status_d = (int8_t *)(hits_d + n), *outcome_d = status_d + n, *age_d = outcome_d + n;
-    SOLVE_CHECK(hipMemcpy(b.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-    rc = c4_solve_deep_dev(device, nullptr, table, b.as<int64_t>(), n, node_budget, nodes_per_launch, status_d, outcome_d, age_d,
-                           nodes_d, hits_d);
-    if (rc) return rc;
-    SOLVE_CHECK(hipMemcpy(nodes, nodes_d, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (table_hits) SOLVE_CHECK(hipMemcpy(table_hits, hits_d, (size_t)n * 8, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(status, status_d, (size_t)n, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(outcome, outcome_d, (size_t)n, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(final_age, age_d, (size_t)n, hipMemcpyDeviceToHost));
-    return C4_OK;
+    return solve_staged(color0, color1, n, node_budget, nodes_per_launch, true, tt, out, NO_WINDOW);
 }
 
 int c4_solve_window_dev(int device, void *hip_stream, c4_solve_table *table, const int64_t *boards_dev, const int8_t *alpha_dev,
@@ -974,15 +983,11 @@ int c4_solve_window_dev(int device, void *hip_stream, c4_solve_table *table, con
                         int8_t *score_dev, int8_t *bound_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev,
                         int64_t *table_hits_dev)
 {
-    int rc = check_args(boards_dev, n, node_budget, nodes_per_launch, status_dev, outcome_dev, final_age_dev, nodes_dev);
-    if (rc) return rc;
-    rc = check_window_args(alpha_dev, beta_dev, n, score_dev, bound_dev);
-    if (rc) return rc;
+    const Answers out{status_dev, outcome_dev, final_age_dev, nodes_dev, table_hits_dev};
+    const Window win{alpha_dev, beta_dev, score_dev, bound_dev};
     TableRef tt;
-    rc = table_ref(table, device, tt);
+    int rc = check_call(device, table, boards_dev != nullptr, n, node_budget, nodes_per_launch, out, &win, false, tt);
     if (rc || n == 0) return rc;
-    rc = pick_device(device);
-    if (rc) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     if (alpha_dev) {        // the windows are checked on the host before the first launch
         std::vector<int8_t> ab((size_t)n * 2);
@@ -992,61 +997,19 @@ int c4_solve_window_dev(int device, void *hip_stream, c4_solve_table *table, con
         rc = check_windows(ab.data(), ab.data() + n, n);
         if (rc) return rc;
     }
-    for (int64_t lo = 0; lo < n; lo += CHUNK_ROWS) {
-        const int64_t m = n - lo < CHUNK_ROWS ? n - lo : CHUNK_ROWS;
-        const Window win{alpha_dev ? alpha_dev + lo : nullptr, beta_dev ? beta_dev + lo : nullptr, score_dev + lo, bound_dev + lo};
-        rc = solve_chunk(stream, boards_dev + 2 * lo, m, node_budget, nodes_per_launch, status_dev + lo, outcome_dev + lo,
-                         final_age_dev + lo, nodes_dev + lo, true, tt, table_hits_dev ? table_hits_dev + lo : nullptr, win);
-        if (rc) return rc;
-    }
-    return C4_OK;
+    return solve_rows(stream, boards_dev, n, node_budget, nodes_per_launch, true, tt, out, win);
 }
 
 int c4_solve_window(int device, c4_solve_table *table, const uint64_t *color0, const uint64_t *color1, const int8_t *alpha,
                     const int8_t *beta, int64_t n, int64_t node_budget, int64_t nodes_per_launch, int8_t *status, int8_t *score,
                     int8_t *bound, int8_t *outcome, int8_t *final_age, int64_t *nodes, int64_t *table_hits)
 {
-    if (n > 0 && (!color0 || !color1)) { set_solve_err("null argument"); return C4_EINVAL; }
-    int rc = check_args(color0, n, node_budget, nodes_per_launch, status, outcome, final_age, nodes);
-    if (rc) return rc;
-    rc = check_window_args(alpha, beta, n, score, bound);
-    if (rc) return rc;
-    if (alpha) {
-        rc = check_windows(alpha, beta, n);
-        if (rc) return rc;
-    }
+    const Answers out{status, outcome, final_age, nodes, table_hits};
+    const Window win{alpha, beta, score, bound};
     TableRef tt;
-    rc = table_ref(table, device, tt);
+    const int rc = check_call(device, table, color0 && color1, n, node_budget, nodes_per_launch, out, &win, true, tt);
     if (rc || n == 0) return rc;
-    rc = pick_device(device);
-    if (rc) return rc;
-    std::vector<int64_t> packed((size_t)n * 2);
-    for (int64_t i = 0; i < n; ++i) {
-        packed[(size_t)(2 * i)] = (int64_t)color0[i];
-        packed[(size_t)(2 * i + 1)] = (int64_t)color1[i];
-    }
-    DevBuf b, out;
-    SOLVE_CHECK(b.get((size_t)n * 16));
-    SOLVE_CHECK(out.get((size_t)n * 23));
-    int64_t *nodes_d = out.as<int64_t>(), *hits_d = nodes_d + n;
-    int8_t *status_d = (int8_t *)(hits_d + n), *outcome_d = status_d + n, *age_d = outcome_d + n, *score_d = age_d + n,
-           *bound_d = score_d + n, *alpha_d = bound_d + n, *beta_d = alpha_d + n;
-    SOLVE_CHECK(hipMemcpy(b.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-    if (alpha) {
-        SOLVE_CHECK(hipMemcpy(alpha_d, alpha, (size_t)n, hipMemcpyHostToDevice));
-        SOLVE_CHECK(hipMemcpy(beta_d, beta, (size_t)n, hipMemcpyHostToDevice));
-    }
-    rc = c4_solve_window_dev(device, nullptr, table, b.as<int64_t>(), alpha ? alpha_d : nullptr, alpha ? beta_d : nullptr, n, node_budget,
-                             nodes_per_launch, status_d, score_d, bound_d, outcome_d, age_d, nodes_d, hits_d);
-    if (rc) return rc;
-    SOLVE_CHECK(hipMemcpy(nodes, nodes_d, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (table_hits) SOLVE_CHECK(hipMemcpy(table_hits, hits_d, (size_t)n * 8, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(status, status_d, (size_t)n, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(score, score_d, (size_t)n, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(bound, bound_d, (size_t)n, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(outcome, outcome_d, (size_t)n, hipMemcpyDeviceToHost));
-    SOLVE_CHECK(hipMemcpy(final_age, age_d, (size_t)n, hipMemcpyDeviceToHost));
-    return C4_OK;
+    return solve_staged(color0, color1, n, node_budget, nodes_per_launch, true, tt, out, win);
 }
 
 int c4_solve_children_dev(int device, void *hip_stream, const int64_t *boards_dev, int64_t n, int64_t *children_dev, int8_t *legal_dev)

@@ -445,31 +445,73 @@ class Table:
             pass
 
 
-def _solve_dev(packed, node_budget=None, nodes_per_launch=None, table=None, deep=False):
-    """c4_solve_dev -- or, with `deep` or a `table`, c4_solve_deep_dev -- on a packed cuda tensor: (status int8, outcome int8,
-    final_age int8, nodes int64, table_hits int64) device tensors."""
+def _solve_dev(packed, node_budget=None, nodes_per_launch=None, table=None, deep=False, window=None):
+    """A packed cuda tensor through the _dev entry point the arguments select: c4_solve_dev; with `deep` or a `table`
+    c4_solve_deep_dev; with `window` = (alpha, beta), int8 NumPy arrays or both None, c4_solve_window_dev.  Returns device
+    tensors (status int8, outcome int8, final_age int8, nodes int64, table_hits int64) and, with a window, (score int8, bound
+    int8) after them."""
     import ctypes as C
     import torch
     n = int(packed.shape[0])
     dev = packed.device
-    status = torch.empty(n, dtype=torch.int8, device=dev)
-    outcome = torch.empty(n, dtype=torch.int8, device=dev)
-    age = torch.empty(n, dtype=torch.int8, device=dev)
+    status, outcome, age = (torch.empty(n, dtype=torch.int8, device=dev) for _ in range(3))
+    extra = tuple(torch.empty(n, dtype=torch.int8, device=dev) for _ in range(2)) if window is not None else ()      # score, bound
     nodes = torch.empty(n, dtype=torch.int64, device=dev)
     hits = torch.zeros(n, dtype=torch.int64, device=dev)
     if n:
         idx = dev.index if dev.index is not None else torch.cuda.current_device()
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-            if deep or table is not None:
-                _check(L.load().c4_solve_deep_dev(idx, C.c_void_p(stream), table.handle if table is not None else None, ptr(packed), n,
-                                                  int(node_budget or 0), int(nodes_per_launch or 0), ptr(status), ptr(outcome),
-                                                  ptr(age), ptr(nodes), ptr(hits)))
+            a_dev, b_dev = (torch.from_numpy(x).to(dev) if x is not None else None for x in (window or (None, None)))
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+            handle = table.handle if table is not None else None
+            size = (n, int(node_budget or 0), int(nodes_per_launch or 0))
+            lib = L.load()
+            if window is not None:
+                rc = lib.c4_solve_window_dev(idx, stream, handle, ptr(packed), ptr(a_dev), ptr(b_dev), *size, ptr(status), ptr(extra[0]),
+                                             ptr(extra[1]), ptr(outcome), ptr(age), ptr(nodes), ptr(hits))
+            elif deep or table is not None:
+                rc = lib.c4_solve_deep_dev(idx, stream, handle, ptr(packed), *size, ptr(status), ptr(outcome), ptr(age), ptr(nodes),
+                                           ptr(hits))
             else:
-                _check(L.load().c4_solve_dev(idx, C.c_void_p(stream), ptr(packed), n, int(node_budget or 0),
-                                             int(nodes_per_launch or 0), ptr(status), ptr(outcome), ptr(age), ptr(nodes)))
-    return status, outcome, age, nodes, hits
+                rc = lib.c4_solve_dev(idx, stream, ptr(packed), *size, ptr(status), ptr(outcome), ptr(age), ptr(nodes))
+            _check(rc)
+    return (status, outcome, age, nodes, hits) + extra
+
+
+def _solve_arrays(boards, node_budget, nodes_per_launch, device, table, deep, window=None):
+    """``_solve_dev`` for a sequence of Boards or pairs, through the entry points that take host arrays (c4_solve, c4_solve_deep,
+    c4_solve_window): the same tuple, of NumPy arrays."""
+    import ctypes as C
+    n = len(boards)
+    status, outcome, age = (np.zeros(n, dtype=np.int8) for _ in range(3))
+    extra = tuple(np.zeros(n, dtype=np.int8) for _ in range(2)) if window is not None else ()     # score, bound
+    nodes = np.zeros(n, dtype=np.int64)
+    hits = np.zeros(n, dtype=np.int64)
+    if n:
+        bits = _bits(boards)
+        c0, c1 = (x.ctypes.data_as(L._u64p) for x in bits)
+        i8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int8)) if a is not None else None  # noqa: E731
+        i64 = lambda a: a.ctypes.data_as(L._i64p)  # noqa: E731
+        handle = table.handle if table is not None else None
+        size = (n, int(node_budget or 0), int(nodes_per_launch or 0))
+        lib = L.load()
+        if window is not None:
+            rc = lib.c4_solve_window(device, handle, c0, c1, i8(window[0]), i8(window[1]), *size, i8(status), i8(extra[0]), i8(extra[1]),
+                                     i8(outcome), i8(age), i64(nodes), i64(hits))
+        elif deep:
+            rc = lib.c4_solve_deep(device, handle, c0, c1, *size, i8(status), i8(outcome), i8(age), i64(nodes), i64(hits))
+        else:
+            rc = lib.c4_solve(device, c0, c1, *size, i8(status), i8(outcome), i8(age), i64(nodes))
+        _check(rc)
+    return (status, outcome, age, nodes, hits) + extra
+
+
+def _solve_any(boards, node_budget, nodes_per_launch, device, table, deep, window=None):
+    """``_solve_dev`` for a packed tensor on any device, ``_solve_arrays`` for anything else; NumPy arrays either way."""
+    if _is_tensor(boards):
+        return tuple(t.cpu().numpy() for t in _solve_dev(_packed_on_device(boards, device), node_budget, nodes_per_launch, table, deep, window))
+    return _solve_arrays(boards, node_budget, nodes_per_launch, device, table, deep, window)
 
 
 def _children_dev(packed):
@@ -489,14 +531,32 @@ def _children_dev(packed):
     return children, legal
 
 
+def _outcome(outcome):
+    """(known bool, float64 0.0 / 0.5 / 1.0 or NaN) of C4_RESULT_* codes, -1 where a row has none."""
+    known = np.asarray(outcome) >= 0
+    return known, np.where(known, np.asarray(outcome, dtype=np.float64) * 0.5, np.nan)
+
+
 def _finish(status, outcome, age, nodes, hits=None):
     status = np.asarray(status, dtype=np.int8)
     age = np.asarray(age, dtype=np.int8)
-    known = np.asarray(outcome) >= 0
-    out = np.where(known, np.asarray(outcome, dtype=np.float64) * 0.5, np.nan)
+    known, out = _outcome(outcome)
     value = np.where(known, value_from_answer(np.where(known, out, 0.0), np.where(known, age, 0)), np.nan)
     nodes = np.asarray(nodes, dtype=np.int64)
     return Solved(status, out, age, value, nodes, np.zeros_like(nodes) if hits is None else np.asarray(hits, dtype=np.int64))
+
+
+def _solve_window_dev(packed, alpha, beta, node_budget=None, nodes_per_launch=None, table=None):
+    """``_solve_dev(window=(alpha, beta))`` in c4_solve_window_dev's order of outputs: (status, score, bound, outcome, final_age,
+    nodes, table_hits)."""
+    status, outcome, age, nodes, hits, score, bound = _solve_dev(packed, node_budget, nodes_per_launch, table, window=(alpha, beta))
+    return status, score, bound, outcome, age, nodes, hits
+
+
+def _finish_window(status, outcome, age, nodes, hits, score, bound):
+    return Windowed(np.asarray(status, dtype=np.int8), np.asarray(score, dtype=np.int8), np.asarray(bound, dtype=np.int8),
+                    _outcome(outcome)[1], np.asarray(age, dtype=np.int8), np.asarray(nodes, dtype=np.int64),
+                    np.asarray(hits, dtype=np.int64))
 
 
 # -- the split: one hard position over many lanes -------------------------------------------------------------------------
@@ -685,29 +745,7 @@ def solve(boards, node_budget=None, nodes_per_launch=None, device=0, table=None,
         if not _is_tensor(boards) and len(boards) == 0:
             return _finish(*(np.zeros(0, dtype=np.int8),) * 3, np.zeros(0, dtype=np.int64))
         return _solve_split(_packed_on_device(boards, device), int(split_plies), node_budget, nodes_per_launch, table)
-    if _is_tensor(boards):
-        res = _solve_dev(_packed_on_device(boards, device), node_budget, nodes_per_launch, table, deep)
-        return _finish(*(t.cpu().numpy() for t in res))
-    import ctypes as C
-    n = len(boards)
-    status = np.zeros(n, dtype=np.int8)
-    outcome = np.zeros(n, dtype=np.int8)
-    age = np.zeros(n, dtype=np.int8)
-    nodes = np.zeros(n, dtype=np.int64)
-    hits = np.zeros(n, dtype=np.int64)
-    if n:
-        c0, c1 = _bits(boards)
-        i8 = C.POINTER(C.c_int8)
-        if deep:
-            _check(L.load().c4_solve_deep(device, table.handle if table is not None else None, c0.ctypes.data_as(L._u64p),
-                                          c1.ctypes.data_as(L._u64p), n, int(node_budget or 0), int(nodes_per_launch or 0),
-                                          status.ctypes.data_as(i8), outcome.ctypes.data_as(i8), age.ctypes.data_as(i8),
-                                          nodes.ctypes.data_as(L._i64p), hits.ctypes.data_as(L._i64p)))
-        else:
-            _check(L.load().c4_solve(device, c0.ctypes.data_as(L._u64p), c1.ctypes.data_as(L._u64p), n, int(node_budget or 0),
-                                     int(nodes_per_launch or 0), status.ctypes.data_as(i8), outcome.ctypes.data_as(i8),
-                                     age.ctypes.data_as(i8), nodes.ctypes.data_as(L._i64p)))
-    return _finish(status, outcome, age, nodes, hits)
+    return _finish(*_solve_any(boards, node_budget, nodes_per_launch, device, table, deep))
 
 
 # -- the deep search from a root window per row --------------------------------------------------------------------------
@@ -726,36 +764,6 @@ def _window_arrays(alpha, beta, n):
         raise ValueError("row %d: the window (%r, %r) is not -%d <= alpha < beta <= %d in whole numbers" % (
             bad[0], a[bad[0]].item(), b[bad[0]].item(), SCORE_MAX, SCORE_MAX))
     return np.ascontiguousarray(a, dtype=np.int8), np.ascontiguousarray(b, dtype=np.int8)
-
-
-def _solve_window_dev(packed, alpha, beta, node_budget=None, nodes_per_launch=None, table=None):
-    """c4_solve_window_dev on a packed cuda tensor; alpha, beta: int8 NumPy arrays or None.  (status int8, score int8, bound
-    int8, outcome int8, final_age int8, nodes int64, table_hits int64) device tensors."""
-    import ctypes as C
-    import torch
-    n = int(packed.shape[0])
-    dev = packed.device
-    status, score, bound, outcome, age = (torch.empty(n, dtype=torch.int8, device=dev) for _ in range(5))
-    nodes = torch.empty(n, dtype=torch.int64, device=dev)
-    hits = torch.zeros(n, dtype=torch.int64, device=dev)
-    if n:
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(dev):
-            a_dev = torch.from_numpy(alpha).to(dev) if alpha is not None else None
-            b_dev = torch.from_numpy(beta).to(dev) if beta is not None else None
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-            _check(L.load().c4_solve_window_dev(idx, C.c_void_p(stream), table.handle if table is not None else None, ptr(packed),
-                                                ptr(a_dev), ptr(b_dev), n, int(node_budget or 0), int(nodes_per_launch or 0),
-                                                ptr(status), ptr(score), ptr(bound), ptr(outcome), ptr(age), ptr(nodes), ptr(hits)))
-    return status, score, bound, outcome, age, nodes, hits
-
-
-def _finish_window(status, score, bound, outcome, age, nodes, hits):
-    known = np.asarray(outcome) >= 0
-    return Windowed(np.asarray(status, dtype=np.int8), np.asarray(score, dtype=np.int8), np.asarray(bound, dtype=np.int8),
-                    np.where(known, np.asarray(outcome, dtype=np.float64) * 0.5, np.nan), np.asarray(age, dtype=np.int8),
-                    np.asarray(nodes, dtype=np.int64), np.asarray(hits, dtype=np.int64))
 
 
 def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, device=0, table=None):
@@ -778,25 +786,7 @@ def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, d
         device = table.device
     n = int(boards.shape[0]) if _is_tensor(boards) else len(boards)
     a, b = _window_arrays(alpha, beta, n)
-    if _is_tensor(boards):
-        res = _solve_window_dev(_packed_on_device(boards, device), a, b, node_budget, nodes_per_launch, table)
-        return _finish_window(*(t.cpu().numpy() for t in res))
-    import ctypes as C
-    status, score, bound, outcome, age = (np.zeros(n, dtype=np.int8) for _ in range(5))
-    nodes = np.zeros(n, dtype=np.int64)
-    hits = np.zeros(n, dtype=np.int64)
-    if n:
-        c0, c1 = _bits(boards)
-        i8 = C.POINTER(C.c_int8)
-        _check(L.load().c4_solve_window(device, table.handle if table is not None else None, c0.ctypes.data_as(L._u64p),
-                                        c1.ctypes.data_as(L._u64p), a.ctypes.data_as(i8) if a is not None else None,
-                                        b.ctypes.data_as(i8) if b is not None else None, n, int(node_budget or 0),
-                                        int(nodes_per_launch or 0), status.ctypes.data_as(i8), score.ctypes.data_as(i8),
-                                        bound.ctypes.data_as(i8), outcome.ctypes.data_as(i8), age.ctypes.data_as(i8),
-                                        nodes.ctypes.data_as(L._i64p), hits.ctypes.data_as(L._i64p)))
-    else:
-        outcome -= 1
-    return _finish_window(status, score, bound, outcome, age, nodes, hits)
+    return _finish_window(*_solve_any(boards, node_budget, nodes_per_launch, device, table, True, (a, b)))
 
 
 def _ages(rows):
@@ -1014,9 +1004,8 @@ def _window_solver(node_budget, nodes_per_launch, device, table, host):
     def on_device(rows, alpha, beta):
         import torch
         packed = _packed_on_device(torch.from_numpy(np.ascontiguousarray(rows).view(np.int64)), device)
-        res = _solve_window_dev(packed, np.ascontiguousarray(alpha, dtype=np.int8), np.ascontiguousarray(beta, dtype=np.int8),
-                                node_budget, nodes_per_launch, table)
-        status, score, _, _, _, nodes, hits = (t.cpu().numpy() for t in res)
+        window = (np.ascontiguousarray(alpha, dtype=np.int8), np.ascontiguousarray(beta, dtype=np.int8))
+        status, _, _, nodes, hits, score, _ = (t.cpu().numpy() for t in _solve_dev(packed, node_budget, nodes_per_launch, table, window=window))
         return status, score, nodes, hits
     return on_device
 

@@ -17,28 +17,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_npz
+from solver_helpers import boards_of, one_lane_is_the_host_model, packed, same_answers, same_bits
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-def boards_of(c0, c1):
-    from connect4_amd.board import Board
-    return [Board.from_bits(int(a), int(b)) for a, b in zip(c0, c1)]
-
-
-def packed(boards):
-    return torch.from_numpy(np.array([b.color for b in boards], dtype=np.uint64).reshape(len(boards), 2).view(np.int64))
-
-
-def same_bits(a, b):
-    return np.asarray(a, dtype=np.float64).tobytes() == np.asarray(b, dtype=np.float64).tobytes()
-
-
-def same_answers(a, b, rows=slice(None)):
-    return (np.array_equal(a.status[rows], b.status[rows]) and same_bits(a.outcome[rows], b.outcome[rows])
-            and np.array_equal(a.final_age[rows], b.final_age[rows]) and same_bits(a.value[rows], b.value[rows]))
 
 
 @pytest.fixture(scope="module")
@@ -52,7 +35,7 @@ def deep():
     from connect4_amd.solver import solve
     z = load_npz("solver_deep.npz")
     boards = boards_of(z["c0"], z["c1"])
-    return z, boards, solve(packed(boards).cuda())
+    return z, boards, solve(packed(boards))
 
 
 # -- 1. the reference ------------------------------------------------------------------------------------------------------
@@ -61,7 +44,7 @@ def test_reference_fixture_bit_for_bit(ref):
     from connect4_amd.solver import grid_triple, solve
     boards = boards_of(ref["c0"], ref["c1"])
     want_outcome = np.where(ref["root_search"] > 0.9, 1.0, np.where(ref["root_search"] < 0.1, 0.0, 0.5))
-    for res in (solve(boards), solve(packed(boards).cuda()), solve(packed(boards))):       # c4_solve, c4_solve_dev (twice)
+    for res in (solve(boards), solve(packed(boards)), solve(packed(boards, cuda=False))):       # c4_solve, c4_solve_dev (twice)
         assert (res.status == L.SOLVE_SOLVED).all() and (res.nodes >= 1).all()
         assert same_bits(res.value, ref["root_search"]) and np.array_equal(res.outcome, want_outcome)
     for i, (move, value, tree) in enumerate(grid_triple(boards)):
@@ -107,10 +90,56 @@ def test_deep_fixture_at_the_default_budget(deep):
 def test_launch_boundaries_do_not_matter(deep):
     from connect4_amd.solver import solve
     _, boards, res = deep
-    t = packed(boards).cuda()
+    t = packed(boards)
     for per_launch in (256, 1 << 20):
         other = solve(t, nodes_per_launch=per_launch)
         assert same_answers(other, res) and np.array_equal(other.nodes, res.nodes)
+
+
+def test_every_parked_state_crosses_a_launch_boundary():
+    """With a quota of 1 node a launch a lane parks after every node it enters -- pending or not, at every depth, through
+    k_solve_init's parked word and k_solve_search's -- and with 3 at every third; either way the answers and node counts are
+    the default quota's and the host mirror's, on the late search, the deep search and the deep search from three windows.
+    64 seeded playouts with 6..12 empty squares, with special_rows() among them -- finished and invalid rows, which are never
+    searched, and a row with 25 empty squares, which is TOO_DEEP for the late search and searched by the others: 71 rows, two
+    workgroups.  A run relaunches once per node of its dearest row: on every path the host mirror's dearest takes at most 512.
+    Then the dearest rows one at a time against a table of 2^10 entries: one lane's table image is the host model's word for
+    word at both quotas."""
+    from connect4_amd.solver import HostTable, Table, random_playout, solve, solve_host, solve_window
+    rng = np.random.RandomState(9)
+    boards = [random_playout(rng, 42 - (6 + i % 7)) for i in range(64)]
+    host_nodes = np.array([solve_host(b).nodes for b in boards])
+    assert host_nodes.max() <= 512 and (host_nodes > 3).sum() >= 8         # the launches of a run; rows that park at both quotas
+    rows = [tuple(b.color) for b in boards]
+    for k, (c0, c1, _) in enumerate(special_rows()):
+        rows.insert(1 + 9 * k, (c0, c1))
+    t = packed(rows)
+
+    def unknown_is_nan(values):
+        return [np.nan if v is None else v for v in values]
+
+    def is_host_mirror(res, **how):
+        want = [solve_host(r, **how) for r in rows]
+        assert max(a.nodes for a in want) <= 512, how          # the launches of this path's runs at a quota of 1
+        fields = ["status", "outcome", "final_age", "nodes"] + (["score", "bound"] if "window" in how else ["value"])
+        return all(same_bits(getattr(res, f), unknown_is_nan([getattr(a, f) for a in want])) for f in fields)
+
+    def same_fields(a, b):
+        return all(x.dtype == y.dtype and x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+    paths = [(lambda **kw: solve(t, **kw), {}), (lambda **kw: solve(t, deep=True, **kw), {"deep": True})]
+    paths += [(lambda a=a, b=b, **kw: solve_window(t, a, b, **kw), {"window": (a, b)}) for a, b in ((-42, 42), (-1, 1), (0, 1))]
+    for run, how in paths:
+        res = run()
+        assert is_host_mirror(res, **how), how
+        for per_launch in (1, 3):
+            assert same_fields(run(nodes_per_launch=per_launch), res), (how, per_launch)
+    for per_launch in (1, 3):
+        for i in np.argsort(host_nodes, kind="stable")[-3:]:
+            with Table(10) as table:
+                host = HostTable(10)
+                nodes = one_lane_is_the_host_model(table, host, boards[i], "quota %d, %d empty squares" % (per_launch, 42 - boards[i].age), per_launch)
+                assert nodes > per_launch and host.stores > 0         # the lane has parked, and the table was written
 
 
 # -- 5. the budget ---------------------------------------------------------------------------------------------------------
@@ -121,7 +150,7 @@ def test_the_budget_never_lies(deep):
     order = np.argsort(z["nodes"], kind="stable")
     rows = np.concatenate([order[:24], order[-24:]])          # the cheapest and the dearest rows: both kinds are in the set
     assert z["nodes"][rows].min() <= 64 < z["nodes"][rows].max()
-    got = solve(packed([boards[i] for i in rows]).cuda(), node_budget=64)
+    got = solve(packed([boards[i] for i in rows]), node_budget=64)
     unknown = got.status == L.SOLVE_UNKNOWN
     assert unknown.any() and (~unknown).any()
     assert np.array_equal(unknown, z["nodes"][rows] > 64)
@@ -206,7 +235,7 @@ def test_symmetry_and_consistency_at_21_to_24_empty_squares():
             ks.append(len(rows))
             rows.append(cb)
         kids_of.append(ks)
-    res = solve(packed(rows).cuda(), node_budget=1 << 20)
+    res = solve(packed(rows), node_budget=1 << 20)
     unknown = res.status == L.SOLVE_UNKNOWN
     print("rows %d, unknown %d, nodes: total %d, max %d" % (len(rows), unknown.sum(), res.nodes.sum(), res.nodes.max()))
     assert unknown.mean() <= 0.05

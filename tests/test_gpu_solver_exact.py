@@ -16,16 +16,13 @@ import pytest
 import solver_audit as A
 import solver_exact_cases as X
 from conftest import load_npz
+from solver_helpers import packed
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 TABLE_FREE_BUDGET = 1 << 20     # the host mirror walks the same tree: its dearest row of the file takes 74,256 nodes
-
-
-def packed(c0, c1):
-    return torch.from_numpy(np.stack([c0, c1], axis=1).astype(np.uint64).view(np.int64)).cuda()
 
 
 @pytest.fixture(scope="module")
@@ -37,7 +34,7 @@ def gold():
     g["age"] = 42 - g["empties"].astype(np.int64)
     g["outcome"], g["final_age"] = X.answer_of_score(g["score"], g["age"])
     g["value"] = value_from_answer(g["outcome"], g["final_age"])
-    g["t"] = packed(g["c0"], g["c1"])
+    g["t"] = packed(np.stack([g["c0"], g["c1"]], axis=1))
     return g
 
 

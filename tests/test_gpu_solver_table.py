@@ -1,4 +1,4 @@
-"""The deep search and its transposition table on the GPU (k_solve_deep of connect4_amd/csrc/c4_solve.hip behind
+"""The deep search and its transposition table on the GPU (k_solve_search<DEEP_MAX_PLY, TableRef> of connect4_amd/csrc/c4_solve.hip behind
 solver.solve(deep= / table= / split_plies=)): against tests/golden/solver_open.npz (25..32 empty squares, answered table-free
 by the host mirror), against today's table-free search on late positions with mirror images and duplicates in the batch,
 and end to end through grid_triple, label and tools/make_test_set.py --openings."""
@@ -10,28 +10,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_npz
+from solver_helpers import boards_of, packed, same_answers, same_bits
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-def boards_of(c0, c1):
-    from connect4_amd.board import Board
-    return [Board.from_bits(int(a), int(b)) for a, b in zip(c0, c1)]
-
-
-def packed(boards):
-    return torch.from_numpy(np.array([b.color for b in boards], dtype=np.uint64).reshape(len(boards), 2).view(np.int64))
-
-
-def same_bits(a, b):
-    return np.asarray(a, dtype=np.float64).tobytes() == np.asarray(b, dtype=np.float64).tobytes()
-
-
-def same_answers(a, b, rows=slice(None)):
-    return (np.array_equal(a.status[rows], b.status[rows]) and same_bits(a.outcome[rows], b.outcome[rows])
-            and np.array_equal(a.final_age[rows], b.final_age[rows]) and same_bits(a.value[rows], b.value[rows]))
 
 
 @pytest.fixture(scope="module")
@@ -39,7 +22,7 @@ def fx():
     """The fixture, its boards, a packed device tensor of them (none is modified)."""
     z = load_npz("solver_open.npz")
     boards = boards_of(z["c0"], z["c1"])
-    return z, boards, packed(boards).cuda()
+    return z, boards, packed(boards)
 
 
 def is_fixture(res, z):
@@ -79,7 +62,7 @@ def test_table_is_todays_search_on_late_positions():
     rng = np.random.RandomState(33)
     roots = [random_playout(rng, 42 - (20 + i % 3)) for i in range(512)]
     rows = roots + [b.create_fliplr() for b in roots] + roots
-    t = packed(rows).cuda()
+    t = packed(rows)
     want = solve(t)
     with Table(24) as table:
         got = solve(t, table=table)

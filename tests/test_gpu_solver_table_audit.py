@@ -1,13 +1,14 @@
-"""The entries of the solver's transposition table on the GPU (k_solve_deep of connect4_amd/csrc/c4_solve.hip), read back with
-solver.Table.read() after the searches have returned and audited by tests/solver_audit.py: DESIGN 3.13's argument that
+"""The entries of the solver's transposition table on the GPU (k_solve_search<DEEP_MAX_PLY, TableRef> of
+connect4_amd/csrc/c4_solve.hip), read back with solver.Table.read() after the searches have returned and audited by
+tests/solver_audit.py: DESIGN 3.13's argument that
 answers do not depend on the table holds if every entry is a true bound of its position, and root answers do not show a
 false one (tests/test_solver_table_audit_host.py).
 
 * One row is one lane: probes and stores happen in program order, launches one after the other, so the image is defined and
   must be solver.HostTable's word for word, parked or not.
 * Many rows, the split, opening positions: store order is the device's own, so every entry is held to the exact score of
-  its position instead -- from k_solve_run (the default solve(): no table code is compiled into it), and for entries with more
-  than 20 empty squares from the table-free deep search under a node budget."""
+  its position instead -- from k_solve_search<MAX_PLY, NoTable> (the default solve(): no table code is compiled into it), and for
+  entries with more than 20 empty squares from the table-free deep search under a node budget."""
 import time
 
 import numpy as np
@@ -15,39 +16,14 @@ import pytest
 
 import solver_audit as A
 from conftest import load_npz
+from solver_helpers import gpu_oracle, one_lane_is_the_host_model, packed
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-ORACLE_MAX_EMPTIES = 20         # k_solve_run answers these in about a second (profiles/solver.json)
+ORACLE_MAX_EMPTIES = 20         # k_solve_search<MAX_PLY, NoTable> answers these in about a second (profiles/solver.json)
 DEEP_ORACLE_BUDGET = 1 << 16    # nodes a deeper entry gets from the table-free deep search: about 0.3 s a lane
-
-
-def packed(rows):
-    """int64 [n, 2] cuda tensor of Boards or of uint64 [n, 2] rows."""
-    if not isinstance(rows, np.ndarray):
-        rows = np.array([b.color for b in rows], dtype=np.uint64).reshape(len(rows), 2)
-    return torch.from_numpy(np.ascontiguousarray(rows).view(np.int64)).cuda()
-
-
-def gpu_oracle(rows):
-    """exact_score_of_rows: one batched table-free solve of the decoded positions.  Up to ORACLE_MAX_EMPTIES empty squares
-    that is the default solve() (k_solve_run); deeper rows go to solve(deep=True) under DEEP_ORACLE_BUDGET and stay
-    UNSOLVED where it does not suffice."""
-    from connect4_amd import _lib as L
-    from connect4_amd.solver import _popcount64, solve
-    age = _popcount64(rows[:, 0] | rows[:, 1])
-    out = np.full(len(rows), A.UNSOLVED, dtype=np.int64)
-    late = 42 - age <= ORACLE_MAX_EMPTIES
-    for pick, kw in ((late, {}), (~late, {"deep": True, "node_budget": DEEP_ORACLE_BUDGET})):
-        if pick.any():
-            res = solve(packed(rows[pick]), **kw)
-            assert (res.table_hits == 0).all() and np.isin(res.status, (L.SOLVE_SOLVED, L.SOLVE_UNKNOWN)).all()
-            assert kw or (res.status == L.SOLVE_SOLVED).all()
-            ok = res.status == L.SOLVE_SOLVED
-            out[pick] = np.where(ok, A.mover_score(np.where(ok, res.outcome, 0.5), res.final_age, age[pick]), A.UNSOLVED)
-    return out
 
 
 def audited(table, label):
@@ -55,7 +31,7 @@ def audited(table, label):
     t0 = time.perf_counter()
     words = table.read()
     report = {}
-    bad = A.audit(words, table.log2_entries, gpu_oracle, report)
+    bad = A.audit(words, table.log2_entries, gpu_oracle(ORACLE_MAX_EMPTIES, DEEP_ORACLE_BUDGET), report)
     print("%s: %s; %d violations; read + audit %.2f s" % (label, A.summary(report), len(bad), time.perf_counter() - t0))
     for v in bad[:10]:
         print("   slot %d, word %#x: %s" % v)
@@ -90,22 +66,10 @@ def many_roots():
 # -- 1. one lane is the host model, word for word -----------------------------------------------------------------------------
 @pytest.mark.parametrize("log2_entries, per_launch", [(10, None), (10, 256), (14, None), (14, 256)])
 def test_one_lane_is_the_host_model_word_for_word(single_rows, log2_entries, per_launch):
-    from connect4_amd import _lib as L
-    from connect4_amd.solver import HostTable, Table, solve, solve_host
+    from connect4_amd.solver import HostTable, Table
 
     def same_step(table, host, row, label):
-        hits_before = host.hits
-        want = solve_host(row, table=host)
-        got = solve(packed([row]), table=table, nodes_per_launch=per_launch)
-        image = table.read()
-        differ = np.nonzero(image != host.words)[0]
-        print("%s: nodes %d (host %d), hits %d (host %d), %d entries (host %d), %d words differ" % (
-            label, got.nodes[0], want.nodes, got.table_hits[0], host.hits - hits_before, np.count_nonzero(image),
-            np.count_nonzero(host.words), len(differ)))
-        assert got.status[0] == want.status == L.SOLVE_SOLVED and (got.outcome[0], got.final_age[0]) == (want.outcome, want.final_age)
-        assert len(differ) == 0, [(int(i), hex(int(image[i])), hex(int(host.words[i]))) for i in differ[:8]]
-        assert got.nodes[0] == want.nodes and got.table_hits[0] == host.hits - hits_before
-        return int(got.nodes[0])
+        return one_lane_is_the_host_model(table, host, row, label, per_launch)
 
     for row in single_rows:                                  # each row alone, a fresh table
         with Table(log2_entries) as table:

@@ -1,8 +1,8 @@
-"""The windowed deep search on the GPU (k_solve_init / k_solve_deep of connect4_amd/csrc/c4_solve.hip behind c4_solve_window /
-c4_solve_window_dev and solver.solve_window / outcomes / label(exact=False) / label_values): row for row against the host
-mirror's answers in tests/golden/solver_window.npz (tests/test_solver_window_host.py holds that file to solve_host), against
-c4_solve_deep with null windows, with tables of three sizes shared between windowed and exact calls and audited afterwards,
-and the staged labelling against today's exact one.
+"""The windowed deep search on the GPU (k_solve_init / k_solve_search<DEEP_MAX_PLY, TableRef> of connect4_amd/csrc/c4_solve.hip
+behind c4_solve_window / c4_solve_window_dev and solver.solve_window / outcomes / label(exact=False) / label_values): row for
+row against the host mirror's answers in tests/golden/solver_window.npz (tests/test_solver_window_host.py holds that file to
+solve_host), against c4_solve_deep with null windows, with tables of three sizes shared between windowed and exact calls and
+audited afterwards, and the staged labelling against today's exact one.
 
 With a table, "the same answer" is what tests/test_solver_window_host.py says: status, kind, the score where the kind is
 exact, and a true bound of that kind otherwise (a stored bound that closes the window is returned as it is)."""
@@ -16,15 +16,12 @@ import pytest
 import solver_audit as A
 import solver_window_cases as cases
 from conftest import ROOT, load_npz
+from solver_helpers import boards_of, gpu_oracle, packed
 from solver_window_cases import FIXTURES, WINDOWS
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-def packed(rows):
-    return torch.from_numpy(np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2).view(np.int64)).cuda()
 
 
 @pytest.fixture(scope="module")
@@ -188,23 +185,8 @@ def test_tables_shared_between_windowed_and_exact_searches_change_no_answer(pool
     assert log2_entries < 24 or (first.nodes.sum() < pool["nodes"].sum() and again.nodes.sum() < first.nodes.sum())
 
 
-ORACLE_MAX_EMPTIES = 20         # as tests/test_gpu_solver_table_audit.py: k_solve_run answers these, deeper entries get a budget
+ORACLE_MAX_EMPTIES = 20         # as tests/test_gpu_solver_table_audit.py: k_solve_search<MAX_PLY, NoTable> answers these, deeper entries get a budget
 DEEP_ORACLE_BUDGET = 1 << 16
-
-
-def gpu_oracle(rows):
-    from connect4_amd import _lib as L
-    from connect4_amd.solver import _popcount64, solve
-    age = _popcount64(rows[:, 0] | rows[:, 1])
-    out = np.full(len(rows), A.UNSOLVED, dtype=np.int64)
-    late = 42 - age <= ORACLE_MAX_EMPTIES
-    for pick, kw in ((late, {}), (~late, {"deep": True, "node_budget": DEEP_ORACLE_BUDGET})):
-        if pick.any():
-            res = solve(packed(rows[pick]), **kw)
-            ok = res.status == L.SOLVE_SOLVED
-            assert kw or ok.all()
-            out[pick] = np.where(ok, A.mover_score(np.where(ok, res.outcome, 0.5), res.final_age, age[pick]), A.UNSOLVED)
-    return out
 
 
 @pytest.mark.parametrize("log2_entries", [10, 14, 24])
@@ -229,7 +211,7 @@ def test_tables_written_by_windowed_searches_audit_clean(log2_entries):
         res = solve_window(packed(rows), alpha, beta, table=table, nodes_per_launch=256)
         assert (res.status == 0).all() and cases.consistent(res.score, res.bound, alpha, beta, exact).all()
         report = {}
-        bad = A.audit(table.read(), log2_entries, gpu_oracle, report)
+        bad = A.audit(table.read(), log2_entries, gpu_oracle(ORACLE_MAX_EMPTIES, DEEP_ORACLE_BUDGET), report)
     share = report["left_out"] / report["entries"]
     print("2^%d entries: %s; %d violations; %.2f %% left out; nodes %d, hits %d" % (log2_entries, A.summary(report), len(bad), 100.0 * share,
                                                                                res.nodes.sum(), res.table_hits.sum()))
@@ -317,15 +299,10 @@ def test_outcomes_and_label_values_agree_with_the_fixture(open_fx):
     assert r["labelled"] == r["solved"] == len(few)
     # mirror images among the parents: their children are the images of the originals' and are searched once
     some = rows[:16]
-    both = np.concatenate([some, np.array([(b.create_fliplr().color) for b in boards_of(some)], dtype=np.uint64)])
+    both = np.concatenate([some, np.array([(b.create_fliplr().color) for b in boards_of(some[:, 0], some[:, 1])], dtype=np.uint64)])
     _, r1 = label(packed(some), exact=False)
     _, r2 = label(packed(both), exact=False)
     assert r2["stage1_rows"] == 2 * r1["stage1_rows"] and r2["stage2_rows"] == r1["stage2_rows"] and r2["stage2_nodes"] == r1["stage2_nodes"]
-
-
-def boards_of(rows):
-    from connect4_amd.board import Board
-    return [Board.from_bits(int(a), int(b)) for a, b in rows]
 
 
 # -- 5. refusals at the C interface -------------------------------------------------------------------------------------------
