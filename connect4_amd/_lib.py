@@ -28,6 +28,10 @@ SOLVE_DEEP_MAX_EMPTIES = 42
 SOLVE_TABLE_MIN_LOG2, SOLVE_TABLE_MAX_LOG2 = 10, 30
 SOLVE_SOLVED, SOLVE_TERMINAL, SOLVE_UNKNOWN, SOLVE_TOO_DEEP, SOLVE_INVALID = 0, 1, 2, 3, 4
 SOLVE_BOUND_NONE, SOLVE_BOUND_LOWER, SOLVE_BOUND_UPPER, SOLVE_BOUND_EXACT = 0, 1, 2, 3     # c4_solve_window's bound
+# c4_solve_graph's state of a node
+SOLVE_NODE_INTERIOR, SOLVE_NODE_SELF, SOLVE_NODE_ANSWERED, SOLVE_NODE_OVER_BUDGET, SOLVE_NODE_DROPPED, SOLVE_NODE_PENDING = 0, 1, 2, 3, 4, 5
+SOLVE_GRAPH_MAX_PLIES = 8
+SOLVE_DEFAULT_NODES_PER_LAUNCH = 1 << 14
 
 
 class EngineError(RuntimeError):
@@ -223,6 +227,8 @@ SIGNATURES = {
                                       C.c_int64] + [C.c_void_p] * 7),
     "c4_solve_window": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, _P(C.c_int8), _P(C.c_int8), C.c_int64, C.c_int64, C.c_int64] +
                         [_P(C.c_int8)] * 5 + [_i64p, _i64p]),
+    "c4_solve_graph": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, _i64p, C.c_int, _P(C.c_int32), _P(C.c_int8), _P(C.c_int8), C.c_int64,
+                                 C.c_int64] + [_P(C.c_int8)] * 5 + [_i64p, _i64p] + [_P(C.c_int8)] * 3 + [_i64p, _i64p]),
 }
 
 _lib = None

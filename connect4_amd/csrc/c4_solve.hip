@@ -64,6 +64,16 @@
 // enter_node may narrow the window the moves are searched with -- the root's own entry is stored against that one,
 // like any node's -- but the kind is judged against the window the caller gave, which stays in the caller's arrays while
 // the row is parked.  A call without a window enters the nodes of the full window (-42, 42).
+//
+// The root driver (c4_solve_graph).  A layered graph of positions, built by the caller: its last level is searched by the
+// two kernels above, unchanged, from static windows -- a child of (a, b) has (-b, -a), a node with several parents the
+// union -- and between the launches a few one-lane-a-node kernels turn the answers into intervals, fold them up
+// (lo = max -hi_c, hi = max -lo_c), answer the rows of level 0 whose interval decides their window, mark down what an
+// undecided row can still use, and clear the unfinished flag of every row that is not marked: it is dropped instead of
+// running out its budget.  Every interval contains the node's exact score whatever was dropped or left unknown, so every
+// answer is a true bound.  The termination argument holds word for word: the new kernels are straight-line, no lane
+// waits for another, and the only new atomics are atomicMin / atomicMax on the 32-bit words of a child's window.  They use
+// no LDS and a handful of VGPRs.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -637,7 +647,180 @@ __global__ void __launch_bounds__(256) k_solve_children(const int64_t *__restric
     }
 }
 
-#define SOLVE_CHECK(expr)                                                                  \
+// -- the root driver: alpha-beta over a graph of positions (c4_solve_graph) ------------------------------------------------
+// The levels of the graph lie one after the other; the last one is searched by k_solve_init and k_solve_search<DEEP_MAX_PLY,
+// TableRef> from static windows, every kernel below is the book-keeping around that search: one lane a node, or a node and
+// a column, straight-line, every index checked.  Where several parents write one child they write with atomicMin /
+// atomicMax on a 32-bit word or store the same byte.  None of them uses LDS.
+struct GraphDev {
+    const int64_t *boards;      // [n_nodes][2]
+    const int32_t *child;       // [n_nodes][7]
+    int32_t *wa, *wb;           // the static window of every node
+    int32_t *lo, *hi;           // its interval
+    uint8_t *state;             // C4_SOLVE_NODE_*
+    uint8_t *needed;            // the marks of one mark-down
+    int32_t n_nodes, first_leaf;
+};
+
+C4_HD bool graph_decided(int lo, int hi, int a, int b) { return lo == hi || lo >= b || hi <= a; }
+
+// level 0's windows from the caller's, every other node's the empty union
+__global__ void __launch_bounds__(256) k_graph_window_init(GraphDev g, int32_t n0, const int8_t *__restrict__ alpha, const int8_t *__restrict__ beta)
+{
+    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= g.n_nodes) return;
+    const bool top = i < n0;
+    g.wa[i] = top ? (alpha ? (int)alpha[i] : -SCORE_MAX) : SCORE_MAX;
+    g.wb[i] = top ? (beta ? (int)beta[i] : SCORE_MAX) : -SCORE_MAX;
+}
+
+// one level's nodes [lo, hi) hand (-b, -a) to their children in [c_lo, c_hi): the union over the parents
+__global__ void __launch_bounds__(256) k_graph_windows(GraphDev g, int32_t lo, int32_t hi, int32_t c_lo, int32_t c_hi)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)(hi - lo) * WIDTH) return;
+    const int32_t node = lo + (int32_t)(t / WIDTH);
+    const int32_t c = g.child[(int64_t)node * WIDTH + (int)(t % WIDTH)];
+    if (c < c_lo || c >= c_hi) return;
+    atomicMin(&g.wa[c], -g.wb[node]);
+    atomicMax(&g.wb[c], -g.wa[node]);
+}
+
+// the windows of the last level as the search takes them
+__global__ void __launch_bounds__(256) k_graph_leaf_windows(GraphDev g, int8_t *__restrict__ alpha, int8_t *__restrict__ beta)
+{
+    const int32_t r = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= g.n_nodes - g.first_leaf) return;
+    alpha[r] = (int8_t)g.wa[g.first_leaf + r];
+    beta[r] = (int8_t)g.wb[g.first_leaf + r];
+}
+
+// every node's own interval and state from the answers the last level has so far; a node with children starts from
+// [-42, 42] and is folded afterwards
+__global__ void __launch_bounds__(256) k_graph_leaves(GraphDev g, const int8_t *__restrict__ status, const int8_t *__restrict__ score,
+                                                      const int8_t *__restrict__ bound, const int8_t *__restrict__ outcome,
+                                                      const int8_t *__restrict__ final_age)
+{
+    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= g.n_nodes) return;
+    bool inner = false;
+#pragma unroll
+    for (int c = 0; c < WIDTH; ++c) inner |= g.child[(int64_t)i * WIDTH + c] >= 0;
+    int lo = -SCORE_MAX, hi = SCORE_MAX, state = C4_SOLVE_NODE_INTERIOR;
+    if (!inner) {
+        const uint64_t c0 = (uint64_t)g.boards[2 * (int64_t)i], c1 = (uint64_t)g.boards[2 * (int64_t)i + 1];
+        const int age = popc64(c0 | c1);
+        int st, o, fa;
+        int s = 0, kind = C4_SOLVE_BOUND_NONE;
+        if (i >= g.first_leaf) {
+            const int32_t r = i - g.first_leaf;
+            st = status[r];
+            o = outcome[r];
+            fa = final_age[r];
+            s = score[r];
+            kind = bound[r];
+        } else {
+            st = classify(c0, c1, o, fa, DEEP_MAX_EMPTIES);
+            st = st == C4_SOLVE_SOLVED ? C4_SOLVE_INVALID : st;     // a position to be searched above the last level: no answer
+        }
+        state = C4_SOLVE_NODE_SELF;
+        if (st == C4_SOLVE_TERMINAL) {
+            const int abs_score = o == C4_RESULT_OWIN ? 43 - fa : o == C4_RESULT_XWIN ? fa - 43 : 0;
+            lo = hi = (age & 1) ? -abs_score : abs_score;
+        } else if (st == C4_SOLVE_UNKNOWN) {
+            state = C4_SOLVE_NODE_OVER_BUDGET;
+        } else if (st == C4_SOLVE_SOLVED) {
+            state = kind != C4_SOLVE_BOUND_NONE ? C4_SOLVE_NODE_ANSWERED : g.state[i] == C4_SOLVE_NODE_DROPPED ? C4_SOLVE_NODE_DROPPED : C4_SOLVE_NODE_PENDING;
+            lo = kind == C4_SOLVE_BOUND_EXACT || kind == C4_SOLVE_BOUND_LOWER ? s : lo;
+            hi = kind == C4_SOLVE_BOUND_EXACT || kind == C4_SOLVE_BOUND_UPPER ? s : hi;
+        }
+    }
+    g.lo[i] = lo;
+    g.hi[i] = hi;
+    g.state[i] = (uint8_t)state;
+}
+
+// fold one level [lo, hi) up from its children in [c_lo, c_hi)
+__global__ void __launch_bounds__(256) k_graph_fold(GraphDev g, int32_t lo, int32_t hi, int32_t c_lo, int32_t c_hi)
+{
+    const int32_t i = lo + (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= hi) return;
+    int f_lo = -99, f_hi = -99;
+    bool inner = false;
+#pragma unroll
+    for (int c = 0; c < WIDTH; ++c) {
+        const int32_t ch = g.child[(int64_t)i * WIDTH + c];
+        const bool ok = ch >= c_lo && ch < c_hi;
+        const int32_t at = ok ? ch : i;     // a column without a child loads the node's own words: always a valid index
+        const int l = g.lo[at], h = g.hi[at];
+        inner |= ok;
+        f_lo = ok && -h > f_lo ? -h : f_lo;
+        f_hi = ok && -l > f_hi ? -l : f_hi;
+    }
+    if (inner) {
+        g.lo[i] = f_lo;
+        g.hi[i] = f_hi;
+    }
+}
+
+// the answers of level 0 from its intervals, and its marks: a row is needed iff it is undecided
+__global__ void __launch_bounds__(256) k_graph_roots(GraphDev g, int32_t n0, int8_t *__restrict__ status, int8_t *__restrict__ score,
+                                                     int8_t *__restrict__ bound, int8_t *__restrict__ outcome, int8_t *__restrict__ final_age)
+{
+    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n0) return;
+    const uint64_t c0 = (uint64_t)g.boards[2 * (int64_t)i], c1 = (uint64_t)g.boards[2 * (int64_t)i + 1];
+    int o, fa;
+    int st = classify(c0, c1, o, fa, DEEP_MAX_EMPTIES);
+    int s = 0, kind = C4_SOLVE_BOUND_NONE;
+    bool need = false;
+    if (st == C4_SOLVE_SOLVED) {
+        const int lo = g.lo[i], hi = g.hi[i], a = g.wa[i], b = g.wb[i];
+        if (lo == hi) { s = lo; kind = bound_kind(lo, a, b); }
+        else if (lo >= b) { s = lo; kind = C4_SOLVE_BOUND_LOWER; }
+        else if (hi <= a) { s = hi; kind = C4_SOLVE_BOUND_UPPER; }
+        else { st = C4_SOLVE_UNKNOWN; need = g.state[i] == C4_SOLVE_NODE_INTERIOR; }
+        if (kind == C4_SOLVE_BOUND_EXACT) root_answer(popc64(c0 | c1), s, o, fa);
+    }
+    status[i] = (int8_t)st;
+    score[i] = (int8_t)s;
+    bound[i] = (int8_t)kind;
+    outcome[i] = (int8_t)o;
+    final_age[i] = (int8_t)fa;
+    g.needed[i] = need ? 1 : 0;
+}
+
+// mark one level [lo, hi) down: an open node needs the children that can still raise it above max(alpha, lo)
+__global__ void __launch_bounds__(256) k_graph_mark(GraphDev g, int32_t lo, int32_t hi, int32_t c_lo, int32_t c_hi)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)(hi - lo) * WIDTH) return;
+    const int32_t node = lo + (int32_t)(t / WIDTH);
+    const int32_t c = g.child[(int64_t)node * WIDTH + (int)(t % WIDTH)];
+    if (c < c_lo || c >= c_hi) return;
+    const int n_lo = g.lo[node], n_hi = g.hi[node], a = g.wa[node], b = g.wb[node];
+    if (!g.needed[node] || graph_decided(n_lo, n_hi, a, b)) return;
+    const int raised = a > n_lo ? a : n_lo;
+    const int c_lo_s = g.lo[c], c_hi_s = g.hi[c];
+    if (c_lo_s < c_hi_s && -c_lo_s > raised) g.needed[c] = 1;
+}
+
+// a row that would go on although no undecided row needs its leaf leaves the search: unfinished[i] = 0, state dropped.
+// active: the dense list the flags belong to, or null -- the flags are k_solve_init's, one a row
+__global__ void __launch_bounds__(256) k_graph_filter(GraphDev g, const int32_t *__restrict__ active, int32_t m, uint8_t *__restrict__ unfinished)
+{
+    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= m) return;
+    const int32_t row = active ? active[i] : i;
+    if (row < 0 || row >= g.n_nodes - g.first_leaf) return;
+    const int32_t node = g.first_leaf + row;
+    if (unfinished[i] && !g.needed[node]) {
+        unfinished[i] = 0;
+        g.state[node] = C4_SOLVE_NODE_DROPPED;
+    }
+}
+
+#define SOLVE_CHECK(expr)                                                               \
     do {                                                                                   \
         hipError_t _r = (expr);                                                            \
         if (_r != hipSuccess) {                                                            \
@@ -672,10 +855,47 @@ struct Answers {
 
 constexpr Window NO_WINDOW{nullptr, nullptr, nullptr, nullptr};
 
+// what c4_solve_graph hangs into solve_chunk's launch loop: the graph, the answers of its last level (the rows of the
+// search) and of level 0
+struct GraphPass {
+    GraphDev g;
+    const int64_t *level_start;     // host, n_levels + 1 entries
+    int n_levels;
+    Answers leaf;
+    Window leaf_win;
+    int8_t *status, *score, *bound, *outcome, *final_age;      // level 0
+};
+
+inline dim3 graph_grid(int64_t lanes) { return dim3((unsigned)((lanes + 255) / 256 > 0 ? (lanes + 255) / 256 : 1)); }
+
+// Between two launches of the search: the leaves' answers to intervals, fold up, level 0's answers, mark down, and the
+// filter over the flags the host is about to read (`active` and `m` as k_graph_filter takes them).  a memset and 2 * plies + 3 launches
+// of a few lanes a node, all enqueued on the search's stream: no lane waits for another.
+int graph_pass(hipStream_t stream, const GraphPass &p, const int32_t *active, int32_t m, uint8_t *unfinished)
+{
+    const GraphDev &g = p.g;
+    const int64_t *ls = p.level_start;
+    const int32_t n0 = (int32_t)ls[1];
+    SOLVE_CHECK(hipMemsetAsync(g.needed, 0, (size_t)g.n_nodes, stream));
+    hipLaunchKernelGGL(k_graph_leaves, graph_grid(g.n_nodes), dim3(256), 0, stream, g, p.leaf.status, p.leaf_win.score, p.leaf_win.bound,
+                       p.leaf.outcome, p.leaf.final_age);
+    for (int j = p.n_levels - 2; j >= 0; --j)
+        hipLaunchKernelGGL(k_graph_fold, graph_grid(ls[j + 1] - ls[j]), dim3(256), 0, stream, g, (int32_t)ls[j], (int32_t)ls[j + 1],
+                           (int32_t)ls[j + 1], (int32_t)ls[j + 2]);
+    hipLaunchKernelGGL(k_graph_roots, graph_grid(n0), dim3(256), 0, stream, g, n0, p.status, p.score, p.bound, p.outcome, p.final_age);
+    for (int j = 0; j <= p.n_levels - 2; ++j)
+        hipLaunchKernelGGL(k_graph_mark, graph_grid((ls[j + 1] - ls[j]) * WIDTH), dim3(256), 0, stream, g, (int32_t)ls[j], (int32_t)ls[j + 1],
+                           (int32_t)ls[j + 1], (int32_t)ls[j + 2]);
+    hipLaunchKernelGGL(k_graph_filter, graph_grid(m), dim3(256), 0, stream, g, active, m, unfinished);
+    SOLVE_CHECK(hipGetLastError());
+    return C4_OK;
+}
+
 // one pass: rows [0, n) of `boards`, n <= CHUNK_ROWS.  deep: k_solve_search<DEEP_MAX_PLY, TableRef> with the table `tt` (or
 // none), 42 plies of parked frames (360 B a row) and the windows `win` (or none); else k_solve_search<MAX_PLY, NoTable>
+// graph: c4_solve_graph's pass (graph_pass) after k_solve_init and after every launch, before the flags are read; else null
 int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t node_budget, int64_t per_launch, bool deep, TableRef tt,
-                Answers out, Window win)
+                Answers out, Window win, const GraphPass *graph = nullptr)
 {
     DevBuf mem, flags, act;
     const int max_ply = deep ? DEEP_MAX_PLY : MAX_PLY;
@@ -695,6 +915,10 @@ int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t no
     hipLaunchKernelGGL(k_solve_init, dim3(grid), dim3(BLOCK), 0, stream, boards, n, node_budget, w, out.status, out.outcome, out.final_age,
                        out.nodes, flags.as<uint8_t>(), deep, tt, out.hits, win);
     SOLVE_CHECK(hipGetLastError());
+    if (graph) {
+        const int rc = graph_pass(stream, *graph, nullptr, (int32_t)n, flags.as<uint8_t>());
+        if (rc) return rc;
+    }
     std::vector<uint8_t> host_flags((size_t)n);
     std::vector<int32_t> active, next;
     SOLVE_CHECK(hipMemcpyAsync(host_flags.data(), flags.p, (size_t)n, hipMemcpyDeviceToHost, stream));
@@ -719,6 +943,10 @@ int solve_chunk(hipStream_t stream, const int64_t *boards, int64_t n, int64_t no
             hipLaunchKernelGGL((k_solve_search<MAX_PLY, NoTable>), blocks, dim3(BLOCK), 0, stream, boards, act.as<int32_t>(), m, node_budget,
                                per_launch, w, NoTable{}, out.status, out.outcome, out.final_age, out.nodes, out.hits, flags.as<uint8_t>(), win);
         SOLVE_CHECK(hipGetLastError());
+        if (graph) {
+            const int rc = graph_pass(stream, *graph, act.as<int32_t>(), m, flags.as<uint8_t>());
+            if (rc) return rc;
+        }
         SOLVE_CHECK(hipMemcpyAsync(host_flags.data(), flags.p, (size_t)m, hipMemcpyDeviceToHost, stream));
         SOLVE_CHECK(hipStreamSynchronize(stream));
         next.clear();
@@ -1010,6 +1238,172 @@ int c4_solve_window(int device, c4_solve_table *table, const uint64_t *color0, c
     const int rc = check_call(device, table, color0 && color1, n, node_budget, nodes_per_launch, out, &win, true, tt);
     if (rc || n == 0) return rc;
     return solve_staged(color0, color1, n, node_budget, nodes_per_launch, true, tt, out, win);
+}
+
+// the graph of a c4_solve_graph call, all in host memory: C4_EINVAL names the first offender
+static int check_graph(const int64_t *level_start, int n_levels, const int32_t *child, const int8_t *alpha, const int8_t *beta)
+{
+    if (n_levels - 1 < 1 || n_levels - 1 > C4_SOLVE_GRAPH_MAX_PLIES) {
+        set_solve_err("a graph has 2..%d levels; got %d", C4_SOLVE_GRAPH_MAX_PLIES + 1, n_levels);
+        return C4_EINVAL;
+    }
+    if (level_start[0] != 0) { set_solve_err("level_start[0] = %lld, not 0", (long long)level_start[0]); return C4_EINVAL; }
+    for (int j = 0; j < n_levels; ++j)
+        if (level_start[j + 1] < level_start[j]) {
+            set_solve_err("level %d: level_start decreases from %lld to %lld", j, (long long)level_start[j], (long long)level_start[j + 1]);
+            return C4_EINVAL;
+        }
+    const int64_t n_nodes = level_start[n_levels];
+    if (n_nodes > (int64_t)1 << 30) { set_solve_err("%lld nodes: a graph takes 2^30", (long long)n_nodes); return C4_EINVAL; }
+    if (n_nodes - level_start[n_levels - 1] > CHUNK_ROWS) {
+        set_solve_err("the last level has %lld nodes, a graph takes %lld", (long long)(n_nodes - level_start[n_levels - 1]), (long long)CHUNK_ROWS);
+        return C4_EINVAL;
+    }
+    std::vector<uint8_t> has_parent((size_t)n_nodes, 0);
+    for (int j = 0; j < n_levels; ++j) {
+        const int64_t c_lo = level_start[j + 1], c_hi = j + 1 < n_levels ? level_start[j + 2] : level_start[j + 1];     // the last level: none
+        for (int64_t i = level_start[j]; i < level_start[j + 1]; ++i)
+            for (int c = 0; c < WIDTH; ++c) {
+                const int64_t ch = child[i * WIDTH + c];
+                if (ch == -1) continue;
+                if (ch < c_lo || ch >= c_hi) {
+                    set_solve_err("node %lld, column %d: child %lld is not a node of the next level", (long long)i, c, (long long)ch);
+                    return C4_EINVAL;
+                }
+                has_parent[(size_t)ch] = 1;
+            }
+    }
+    for (int64_t i = level_start[1]; i < n_nodes; ++i)
+        if (!has_parent[(size_t)i]) { set_solve_err("node %lld has no parent", (long long)i); return C4_EINVAL; }
+    if ((alpha == nullptr) != (beta == nullptr)) { set_solve_err("alpha and beta are given together, or both are null"); return C4_EINVAL; }
+    return alpha ? check_windows(alpha, beta, level_start[1]) : C4_OK;
+}
+
+int c4_solve_graph(int device, c4_solve_table *table, const uint64_t *color0, const uint64_t *color1, const int64_t *level_start,
+                   int n_levels, const int32_t *child, const int8_t *alpha, const int8_t *beta, int64_t node_budget,
+                   int64_t nodes_per_launch, int8_t *status, int8_t *score, int8_t *bound, int8_t *outcome, int8_t *final_age,
+                   int64_t *nodes, int64_t *table_hits, int8_t *node_lo, int8_t *node_hi, int8_t *node_state, int64_t *node_nodes,
+                   int64_t *node_table_hits)
+{
+    if (!level_start || !child || !color0 || !color1) { set_solve_err("null argument"); return C4_EINVAL; }
+    int rc = check_graph(level_start, n_levels, child, alpha, beta);
+    if (rc) return rc;
+    const int64_t n_nodes = level_start[n_levels], n0 = level_start[1], first_leaf = level_start[n_levels - 1], n_leaf = n_nodes - first_leaf;
+    const Answers out{status, outcome, final_age, nodes, table_hits};
+    rc = check_args(n0, node_budget, nodes_per_launch, out);
+    if (rc) return rc;
+    if (n0 > 0 && (!score || !bound || !table_hits)) { set_solve_err("null argument"); return C4_EINVAL; }
+    TableRef tt;
+    rc = table_ref(table, device, tt);
+    if (rc || n0 == 0) return rc;
+    rc = pick_device(device);
+    if (rc) return rc;
+
+    std::vector<int64_t> packed((size_t)n_nodes * 2);
+    for (int64_t i = 0; i < n_nodes; ++i) {
+        packed[(size_t)(2 * i)] = (int64_t)color0[i];
+        packed[(size_t)(2 * i + 1)] = (int64_t)color1[i];
+    }
+    // device memory: per node the boards, the children, window, interval, state and mark; per row of the last level the
+    // search's answers and windows; per row of level 0 its answers and the caller's windows
+    DevBuf d_boards, d_child, d_words, d_bytes, d_leaf64, d_leaf8, d_root8;
+    SOLVE_CHECK(d_boards.get((size_t)n_nodes * 16));
+    SOLVE_CHECK(d_child.get((size_t)n_nodes * WIDTH * 4));
+    SOLVE_CHECK(d_words.get((size_t)n_nodes * 4 * 4));
+    SOLVE_CHECK(d_bytes.get((size_t)n_nodes * 2));
+    SOLVE_CHECK(d_leaf64.get((size_t)n_leaf * 2 * 8));
+    SOLVE_CHECK(d_leaf8.get((size_t)n_leaf * 7));
+    SOLVE_CHECK(d_root8.get((size_t)n0 * 7));
+    SOLVE_CHECK(hipMemcpy(d_boards.p, packed.data(), (size_t)n_nodes * 16, hipMemcpyHostToDevice));
+    SOLVE_CHECK(hipMemcpy(d_child.p, child, (size_t)n_nodes * WIDTH * 4, hipMemcpyHostToDevice));
+    SOLVE_CHECK(hipMemset(d_bytes.p, 0, (size_t)n_nodes * 2));
+    SOLVE_CHECK(hipMemset(d_leaf64.p, 0, (size_t)n_leaf * 2 * 8 ? (size_t)n_leaf * 2 * 8 : 16));
+    int8_t *r8 = d_root8.as<int8_t>();
+    if (alpha) {
+        SOLVE_CHECK(hipMemcpy(r8 + 5 * n0, alpha, (size_t)n0, hipMemcpyHostToDevice));
+        SOLVE_CHECK(hipMemcpy(r8 + 6 * n0, beta, (size_t)n0, hipMemcpyHostToDevice));
+    }
+    GraphPass p;
+    p.g.boards = d_boards.as<int64_t>();
+    p.g.child = d_child.as<int32_t>();
+    p.g.wa = d_words.as<int32_t>();
+    p.g.wb = p.g.wa + n_nodes;
+    p.g.lo = p.g.wb + n_nodes;
+    p.g.hi = p.g.lo + n_nodes;
+    p.g.state = d_bytes.as<uint8_t>();
+    p.g.needed = p.g.state + n_nodes;
+    p.g.n_nodes = (int32_t)n_nodes;
+    p.g.first_leaf = (int32_t)first_leaf;
+    p.level_start = level_start;
+    p.n_levels = n_levels;
+    int8_t *l8 = d_leaf8.as<int8_t>();
+    p.leaf = Answers{l8, l8 + n_leaf, l8 + 2 * n_leaf, d_leaf64.as<int64_t>(), d_leaf64.as<int64_t>() + n_leaf};
+    p.leaf_win = Window{l8 + 3 * n_leaf, l8 + 4 * n_leaf, l8 + 5 * n_leaf, l8 + 6 * n_leaf};
+    p.status = r8;
+    p.score = r8 + n0;
+    p.bound = r8 + 2 * n0;
+    p.outcome = r8 + 3 * n0;
+    p.final_age = r8 + 4 * n0;
+    hipStream_t stream = nullptr;
+    // the static windows, top-down
+    hipLaunchKernelGGL(k_graph_window_init, graph_grid(n_nodes), dim3(256), 0, stream, p.g, (int32_t)n0, alpha ? r8 + 5 * n0 : nullptr,
+                       alpha ? r8 + 6 * n0 : nullptr);
+    for (int j = 0; j + 1 < n_levels; ++j)
+        hipLaunchKernelGGL(k_graph_windows, graph_grid((level_start[j + 1] - level_start[j]) * WIDTH), dim3(256), 0, stream, p.g,
+                           (int32_t)level_start[j], (int32_t)level_start[j + 1], (int32_t)level_start[j + 1], (int32_t)level_start[j + 2]);
+    hipLaunchKernelGGL(k_graph_leaf_windows, graph_grid(n_leaf), dim3(256), 0, stream, p.g, l8 + 3 * n_leaf, l8 + 4 * n_leaf);
+    SOLVE_CHECK(hipGetLastError());
+    if (n_leaf > 0) {
+        rc = solve_chunk(stream, p.g.boards + 2 * first_leaf, n_leaf, node_budget, nodes_per_launch, true, tt, p.leaf, p.leaf_win, &p);
+        if (rc) return rc;
+    } else {
+        rc = graph_pass(stream, p, nullptr, 0, p.g.needed);      // nothing to search: every row answers for itself
+        if (rc) return rc;
+    }
+    SOLVE_CHECK(hipStreamSynchronize(stream));
+
+    std::vector<int32_t> words((size_t)n_nodes * 2);
+    std::vector<uint8_t> state((size_t)n_nodes);
+    std::vector<int64_t> leaf64((size_t)n_leaf * 2);
+    SOLVE_CHECK(hipMemcpy(words.data(), p.g.lo, (size_t)n_nodes * 8, hipMemcpyDeviceToHost));
+    SOLVE_CHECK(hipMemcpy(state.data(), p.g.state, (size_t)n_nodes, hipMemcpyDeviceToHost));
+    if (n_leaf) SOLVE_CHECK(hipMemcpy(leaf64.data(), d_leaf64.p, (size_t)n_leaf * 16, hipMemcpyDeviceToHost));
+    int8_t *const root_out[5] = {status, score, bound, outcome, final_age};
+    for (int k = 0; k < 5; ++k) SOLVE_CHECK(hipMemcpy(root_out[k], r8 + (int64_t)k * n0, (size_t)n0, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n_nodes; ++i) {
+        if (node_lo) node_lo[i] = (int8_t)words[(size_t)i];
+        if (node_hi) node_hi[i] = (int8_t)words[(size_t)(n_nodes + i)];
+        if (node_state) node_state[i] = (int8_t)state[(size_t)i];
+        if (node_nodes) node_nodes[i] = i >= first_leaf ? leaf64[(size_t)(i - first_leaf)] : 0;
+        if (node_table_hits) node_table_hits[i] = i >= first_leaf ? leaf64[(size_t)(n_leaf + i - first_leaf)] : 0;
+    }
+    // nodes and table_hits of a row: the sums over its distinct nodes of the last level, found by walking its descendants
+    std::vector<int64_t> seen((size_t)n_nodes, -1);
+    std::vector<int64_t> walk;
+    for (int64_t r = 0; r < n0; ++r) {
+        int64_t sum_nodes = 0, sum_hits = 0;
+        walk.assign(1, r);
+        seen[(size_t)r] = r;
+        while (!walk.empty()) {
+            const int64_t i = walk.back();
+            walk.pop_back();
+            if (i >= first_leaf) {
+                sum_nodes += leaf64[(size_t)(i - first_leaf)];
+                sum_hits += leaf64[(size_t)(n_leaf + i - first_leaf)];
+                continue;
+            }
+            for (int c = 0; c < WIDTH; ++c) {
+                const int64_t ch = child[i * WIDTH + c];
+                if (ch >= 0 && seen[(size_t)ch] != r) {
+                    seen[(size_t)ch] = r;
+                    walk.push_back(ch);
+                }
+            }
+        }
+        nodes[r] = sum_nodes;
+        table_hits[r] = sum_hits;
+    }
+    return C4_OK;
 }
 
 int c4_solve_children_dev(int device, void *hip_stream, const int64_t *boards_dev, int64_t n, int64_t *children_dev, int8_t *legal_dev)

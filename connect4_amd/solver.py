@@ -38,7 +38,7 @@ from .utils import Side
 
 __all__ = ["MAX_EMPTIES", "DEEP_MAX_EMPTIES", "DEFAULT_NODE_BUDGET", "STATUS_NAMES", "Solved", "HostAnswer", "Table", "HostTable",
            "EntryFields", "entry_fields", "solve", "solve_host", "HostWindowAnswer", "Windowed", "BOUND_NAMES", "solve_window", "outcomes",
-           "label_values", "staged_labels", "grid_triple", "label", "prior_from_children", "value_from_answer", "random_playout", "random_openings"]
+           "label_values", "staged_labels", "drive_host", "drive_graph_host", "solve_graph", "Graph", "NODE_STATE_NAMES", "grid_triple", "label", "prior_from_children", "value_from_answer", "random_playout", "random_openings"]
 
 MAX_EMPTIES = L.SOLVE_MAX_EMPTIES
 DEEP_MAX_EMPTIES = L.SOLVE_DEEP_MAX_EMPTIES     # every position: c4_solve_deep and solve(deep=True / table=)
@@ -204,11 +204,13 @@ class _Search:
         self.budget = budget
         self.table = table
         self.hits = 0
+        self.clean = True
 
     def enter(self):
         if self.nodes >= self.budget:
             raise _OverBudget()
         self.nodes += 1
+        self.clean = True       # every return since the last node entered was a cut-off (drive_host's launch model)
 
     def node(self, mine, theirs, age, alpha, beta):
         """Score for the mover of a position whose mover cannot win at once (c4_solve.hip enter_node + run_lane)."""
@@ -269,6 +271,7 @@ class _Search:
             v = -self.node(theirs, mine | bit, age + 1, -beta, -alpha)
             if v >= beta:
                 return v
+            self.clean = False
             if v > alpha:
                 alpha = v
         return alpha
@@ -766,7 +769,7 @@ def _window_arrays(alpha, beta, n):
     return np.ascontiguousarray(a, dtype=np.int8), np.ascontiguousarray(b, dtype=np.int8)
 
 
-def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, device=0, table=None):
+def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, device=0, table=None, driver_plies=0, host=False):
     """The deep search (``solve(deep=True)``: every position, optionally a ``Table``) from a root window per row.  alpha, beta:
     scalars or per-row arrays on the mover's score (43 - final age for a win, final age - 43 for a loss, 0 for a draw),
     -42 <= alpha < beta <= 42; both None: the full window.  `boards` as ``solve`` takes them.  Returns ``Windowed`` of arrays:
@@ -781,11 +784,27 @@ def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, d
       nodes, table_hits  as ``solve``
 
     A narrower window never costs a table-free search more nodes than one that contains it; (-1, 1) answers who wins,
-    (v - 1, v) whether the mover's score reaches v."""
-    if table is not None:
+    (v - 1, v) whether the mover's score reaches v.
+
+    driver_plies=k (1..8): the root driver.  Every row is expanded k plies, the distinct descendants -- mirror images merged
+    -- are searched as rows of one batch from windows derived from the row's, and their bounds are folded back as intervals
+    (c4_solve_graph): a row is answered as soon as the interval decides its window, an unfinished descendant leaves it
+    UNKNOWN only where the proof needs it, and descendants no open row can still use are dropped between launches.  The kind
+    is the undriven call's wherever both answer, and so is the score where it is EXACT; a bound's score may differ, and nodes
+    and table_hits are the sums over the row's distinct descendants (node_budget bounds each).  A call is cut into graphs
+    whose last level has at most 2^20 positions; a single row with more distinct descendants than that -- an early position
+    with driver_plies of 7 or 8 -- raises ValueError: give fewer plies.  host=True (with driver_plies)
+    computes the same with ``drive_host``: no GPU, no table."""
+    if table is not None and not host:
         device = table.device
     n = int(boards.shape[0]) if _is_tensor(boards) else len(boards)
     a, b = _window_arrays(alpha, beta, n)
+    if driver_plies:
+        if host and table is not None:
+            raise ValueError("host=True drives table-free")
+        return _drive(_rows_u64(boards), a, b, driver_plies, node_budget, nodes_per_launch, device, table, host)
+    if host:
+        raise ValueError("host=True belongs to driver_plies; solve_host answers single positions")
     return _finish_window(*_solve_any(boards, node_budget, nodes_per_launch, device, table, True, (a, b)))
 
 
@@ -793,11 +812,11 @@ def _ages(rows):
     return _popcount64(rows[:, 0] | rows[:, 1]) if len(rows) else np.zeros(0, dtype=np.int64)
 
 
-def outcomes(boards, node_budget=None, nodes_per_launch=None, device=0, table=None):
+def outcomes(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, driver_plies=0, host=False):
     """Who wins each position: float64 0.0 (x) / 0.5 (draw) / 1.0 (o), NaN where the budget leaves a row unknown or the row is
     invalid; a finished position answers with its own result.  One search per row with the window (-1, +1), the narrowest
-    that separates win, draw and loss -- how fast is not asked, and not paid for."""
-    res = solve_window(boards, -1, 1, node_budget, nodes_per_launch, device, table)
+    that separates win, draw and loss -- how fast is not asked, and not paid for.  driver_plies, host: ``solve_window``'s."""
+    res = solve_window(boards, -1, 1, node_budget, nodes_per_launch, device, table, driver_plies, host)
     if _is_tensor(boards):
         rows = boards.cpu().numpy().view(np.uint64).reshape(-1, 2)
     else:
@@ -805,6 +824,404 @@ def outcomes(boards, node_budget=None, nodes_per_launch=None, device=0, table=No
     sign = np.sign(res.score.astype(np.int64))
     absolute = np.where(_ages(rows) & 1, -sign, sign)
     return np.where(res.status == L.SOLVE_SOLVED, (absolute + 1) * 0.5, np.where(res.status == L.SOLVE_TERMINAL, res.outcome, np.nan))
+
+
+# -- the root driver: alpha-beta over the split ---------------------------------------------------------------------------
+# The graph: level 0 holds the distinct (row, window) pairs of a call, level j + 1 the distinct children of level j with
+# mirror images merged; child[node][col] is the child's index among all nodes, levels concatenated, or -1.  DESIGN.md
+# section 3.13 has the rules (static windows, leaf intervals, fold up, answer, mark down) and why they are sound; the
+# functions below are those rules on flat NumPy arrays, c4_solve_graph's kernels are the same rules one lane per node.
+NODE_INTERIOR, NODE_SELF, NODE_ANSWERED, NODE_OVER_BUDGET, NODE_DROPPED = (L.SOLVE_NODE_INTERIOR, L.SOLVE_NODE_SELF, L.SOLVE_NODE_ANSWERED,
+                                                                           L.SOLVE_NODE_OVER_BUDGET, L.SOLVE_NODE_DROPPED)
+_NODE_PENDING = L.SOLVE_NODE_PENDING        # a leaf between launches; no report that is returned holds it
+NODE_STATE_NAMES = {NODE_INTERIOR: "interior", NODE_SELF: "self_answering", NODE_ANSWERED: "answered", NODE_OVER_BUDGET: "over_budget",
+                    NODE_DROPPED: "dropped"}
+GRAPH_MAX_LEAVES = 1 << 20      # the last level of one graph (c4_solve.hip CHUNK_ROWS)
+
+Graph = namedtuple("Graph", "color0 color1 level_start child alpha beta inverse")
+
+
+def _build_graph(rows, alpha, beta, plies, children_of):
+    """The graph `plies` deep below uint64 [n, 2] `rows` with windows int8 [n] (or both None: the full window): ``Graph`` of
+    color0, color1 uint64 [n_nodes], level_start int64 [plies + 2], child int32 [n_nodes, 7], alpha, beta int8 [n_0] (level
+    0's windows) and inverse int64 [n]: level-0 node ``inverse[i]`` is row i with its window."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+    n = len(rows)
+    a = np.full(n, -SCORE_MAX, dtype=np.int64) if alpha is None else np.asarray(alpha, dtype=np.int64)
+    b = np.full(n, SCORE_MAX, dtype=np.int64) if beta is None else np.asarray(beta, dtype=np.int64)
+    keyed = np.concatenate([rows, (a + 64).astype(np.uint64)[:, None], (b + 64).astype(np.uint64)[:, None]], axis=1)
+    if n:
+        uniq, inverse = np.unique(keyed, axis=0, return_inverse=True)
+        inverse = np.asarray(inverse, dtype=np.int64).reshape(-1)
+    else:
+        uniq, inverse = keyed, np.zeros(0, dtype=np.int64)
+    levels, links = [np.ascontiguousarray(uniq[:, :2])], []
+    for _ in range(plies):
+        ch, lg = children_of(levels[-1])
+        ch, lg = np.asarray(ch, dtype=np.uint64), np.asarray(lg).astype(bool)
+        nxt, inv = _unique_rows(_canonical(ch[lg]))
+        link = np.full(lg.shape, -1, dtype=np.int64)
+        link[lg] = inv
+        levels.append(nxt)
+        links.append(link)
+    start = np.concatenate([[0], np.cumsum([len(lv) for lv in levels])]).astype(np.int64)
+    child = np.full((int(start[-1]), WIDTH), -1, dtype=np.int32)
+    for j, link in enumerate(links):
+        child[start[j]:start[j + 1]] = np.where(link >= 0, link + start[j + 1], -1)
+    nodes = np.concatenate(levels)
+    return Graph(np.ascontiguousarray(nodes[:, 0]), np.ascontiguousarray(nodes[:, 1]), start, child,
+                 (uniq[:, 2].astype(np.int64) - 64).astype(np.int8), (uniq[:, 3].astype(np.int64) - 64).astype(np.int8), inverse)
+
+
+def _graph_windows(g):
+    """The static windows of every node, int64 [n_nodes] each: level 0 has the caller's, a child of (a, b) gets (-b, -a), a
+    node with several parents the union."""
+    n0 = int(g.level_start[1])
+    wa = np.full(len(g.child), SCORE_MAX, dtype=np.int64)
+    wb = np.full(len(g.child), -SCORE_MAX, dtype=np.int64)
+    wa[:n0], wb[:n0] = g.alpha, g.beta
+    for j in range(len(g.level_start) - 2):
+        lo, hi = int(g.level_start[j]), int(g.level_start[j + 1])
+        r, c = np.nonzero(g.child[lo:hi] >= 0)
+        at = g.child[lo:hi][r, c]
+        np.minimum.at(wa, at, -wb[lo + r])
+        np.maximum.at(wb, at, -wa[lo + r])
+    return wa, wb
+
+
+def _graph_fold(g, lo, hi):
+    """Fold up in place, the level above the last one first: lo = max over children of -hi_c, hi = max of -lo_c."""
+    for j in range(len(g.level_start) - 3, -1, -1):
+        s, e = int(g.level_start[j]), int(g.level_start[j + 1])
+        ch = g.child[s:e]
+        has = ch >= 0
+        at = np.where(has, ch, 0)
+        f_lo = np.where(has, -hi[at], -99).max(axis=1) if e > s else np.zeros(0, dtype=np.int64)
+        f_hi = np.where(has, -lo[at], -99).max(axis=1) if e > s else np.zeros(0, dtype=np.int64)
+        inner = has.any(axis=1)
+        lo[s:e] = np.where(inner, f_lo, lo[s:e])
+        hi[s:e] = np.where(inner, f_hi, hi[s:e])
+
+
+def _graph_decided(lo, hi, a, b):
+    return (lo == hi) | (lo >= b) | (hi <= a)
+
+
+def _graph_mark(g, lo, hi, wa, wb):
+    """Mark down: bool [n_nodes], the nodes some undecided level-0 row still needs."""
+    inner = (g.child >= 0).any(axis=1)
+    needed = np.zeros(len(g.child), dtype=bool)
+    n0 = int(g.level_start[1])
+    needed[:n0] = inner[:n0] & ~_graph_decided(lo[:n0], hi[:n0], wa[:n0], wb[:n0])
+    for j in range(len(g.level_start) - 2):
+        s, e = int(g.level_start[j]), int(g.level_start[j + 1])
+        is_open = needed[s:e] & inner[s:e] & ~_graph_decided(lo[s:e], hi[s:e], wa[s:e], wb[s:e])
+        raised = np.maximum(wa[s:e], lo[s:e])
+        ch = g.child[s:e]
+        at = np.where(ch >= 0, ch, 0)
+        want = (ch >= 0) & is_open[:, None] & (lo[at] < hi[at]) & (-lo[at] > raised[:, None])
+        needed[at[want]] = True
+    return needed
+
+
+def _mover_score_of_finished(c0, c1):
+    """The score for the side to move of a finished position: it has lost, or the board is full."""
+    age = bin(c0 | c1).count("1")
+    return age - 43 if (_wins(c0) or _wins(c1)) else 0
+
+
+def _graph_root_answers(g, lo, hi, wa, wb):
+    """The answers of level 0 from its intervals: (status, score, bound, outcome code, final_age) int8 [n_0]."""
+    n0 = int(g.level_start[1])
+    status, score, bound = (np.zeros(n0, dtype=np.int8) for _ in range(3))
+    outcome, final_age = (np.full(n0, -1, dtype=np.int8) for _ in range(2))
+    for i in range(n0):
+        c0, c1 = int(g.color0[i]), int(g.color1[i])
+        st = _classify(c0, c1, DEEP_MAX_EMPTIES)
+        status[i] = st
+        if st == L.SOLVE_TERMINAL:
+            outcome[i] = L.RESULT_OWIN if _wins(c0) else L.RESULT_XWIN if _wins(c1) else L.RESULT_DRAW
+            final_age[i] = bin(c0 | c1).count("1")
+        if st != L.SOLVE_SOLVED:
+            continue
+        l, h, a, b = int(lo[i]), int(hi[i]), int(wa[i]), int(wb[i])
+        if l == h:
+            score[i], bound[i] = l, _bound_kind(l, a, b)
+        elif l >= b:
+            score[i], bound[i] = l, L.SOLVE_BOUND_LOWER
+        elif h <= a:
+            score[i], bound[i] = h, L.SOLVE_BOUND_UPPER
+        else:
+            status[i] = L.SOLVE_UNKNOWN
+            continue
+        if bound[i] == L.SOLVE_BOUND_EXACT:
+            s = -int(score[i]) if bin(c0 | c1).count("1") & 1 else int(score[i])
+            outcome[i] = L.RESULT_OWIN if s > 0 else L.RESULT_XWIN if s < 0 else L.RESULT_DRAW
+            final_age[i] = 43 - abs(s) if s else SIZE
+    return status, score, bound, outcome, final_age
+
+
+def _graph_root_sums(g, per_node):
+    """int64 [n_0]: `per_node` (int64 [n_nodes], zero off the last level) summed over each level-0 row's distinct leaves."""
+    k = len(g.level_start) - 2
+    n_leaf = int(g.level_start[-1] - g.level_start[-2])
+    p_row, p_leaf = np.arange(n_leaf), np.arange(n_leaf)
+    for j in range(k - 1, -1, -1):
+        s, e = int(g.level_start[j]), int(g.level_start[j + 1])
+        link = np.where(g.child[s:e] >= 0, g.child[s:e].astype(np.int64) - g.level_start[j + 1], -1)
+        p_row, p_leaf = _leaf_pairs(link, p_row, p_leaf, int(g.level_start[j + 2] - g.level_start[j + 1]))
+    leaf = np.asarray(per_node, dtype=np.int64)[int(g.level_start[-2]):]
+    return np.bincount(p_row, weights=leaf[p_leaf], minlength=int(g.level_start[1])).astype(np.int64)
+
+
+def _host_leaf(c0, c1, alpha, beta, node_budget):
+    """drive_host's default leaf_solver, ``solve_host(window=)`` table-free: (status, score, bound, nodes, clean).  clean: no
+    node of the search returned without a cut-off after the last one was entered -- the lane is done in the launch that
+    enters its last node even where that node uses up the launch's quota (run_lane closes a node whose moves are used up
+    only while quota is left)."""
+    st = _classify(c0, c1, DEEP_MAX_EMPTIES)
+    if st != L.SOLVE_SOLVED:
+        return st, 0, L.SOLVE_BOUND_NONE, 0, True
+    occ = c0 | c1
+    age = bin(occ).count("1")
+    mine, theirs = (c1, c0) if age & 1 else (c0, c1)
+    if _winning_squares(mine, occ) & (occ + BOTTOM):
+        return st, 42 - age, _bound_kind(42 - age, alpha, beta), 1, True
+    s = _Search(node_budget)
+    try:
+        score = s.node(mine, theirs, age, alpha, beta)
+    except _OverBudget:
+        return L.SOLVE_UNKNOWN, 0, L.SOLVE_BOUND_NONE, s.nodes, False
+    return st, score, _bound_kind(score, alpha, beta), s.nodes, s.clean
+
+
+def _interval(score, bound):
+    return {L.SOLVE_BOUND_EXACT: (score, score), L.SOLVE_BOUND_LOWER: (score, SCORE_MAX),
+            L.SOLVE_BOUND_UPPER: (-SCORE_MAX, score)}.get(bound, (-SCORE_MAX, SCORE_MAX))
+
+
+def _check_driver_plies(driver_plies):
+    if not (float(driver_plies).is_integer() and 1 <= int(driver_plies) <= 8):
+        raise ValueError("driver_plies must be 1..8; got %r" % (driver_plies,))
+    return int(driver_plies)
+
+
+def _budgets(node_budget, nodes_per_launch):
+    budget = DEFAULT_NODE_BUDGET if not node_budget else int(node_budget)
+    quota = L.SOLVE_DEFAULT_NODES_PER_LAUNCH if not nodes_per_launch else int(nodes_per_launch)
+    if budget < 0 or quota < 0:
+        raise ValueError("node_budget and nodes_per_launch must not be negative")
+    return budget, quota
+
+
+def drive_graph_host(g, node_budget=None, nodes_per_launch=None, leaf_solver=_host_leaf, given=None):
+    """``drive_host`` on a ``Graph``: (status, score, bound, outcome code, final_age, nodes, table_hits) of level 0 and the
+    per-node report.  given: {node: (score, bound)} -- leaves answered from the start whatever the budget (a test's way to
+    hand dropped leaves their true answers)."""
+    budget, quota = _budgets(node_budget, nodes_per_launch)
+    n_nodes = len(g.child)
+    first_leaf = int(g.level_start[-2])
+    wa, wb = _graph_windows(g)
+    inner = (g.child >= 0).any(axis=1)
+    lo = np.full(n_nodes, -SCORE_MAX, dtype=np.int64)
+    hi = np.full(n_nodes, SCORE_MAX, dtype=np.int64)
+    state = np.where(inner, NODE_INTERIOR, _NODE_PENDING).astype(np.int8)
+    count = np.zeros(n_nodes, dtype=np.int64)
+    full = {}       # node -> the leaf's whole search under the budget, computed when the leaf first takes part in a launch
+
+    def leaf(i, cap):
+        return leaf_solver(int(g.color0[i]), int(g.color1[i]), int(wa[i]), int(wb[i]), cap)
+
+    def answer(i, score, bound):
+        lo[i], hi[i] = _interval(score, bound)
+        state[i] = NODE_ANSWERED
+
+    # before launch 1: what k_solve_init answers
+    for i in np.nonzero(~inner)[0]:
+        c0, c1 = int(g.color0[i]), int(g.color1[i])
+        st = _classify(c0, c1, DEEP_MAX_EMPTIES)
+        if st != L.SOLVE_SOLVED or i < first_leaf:
+            state[i] = NODE_SELF
+            if st == L.SOLVE_TERMINAL:
+                lo[i] = hi[i] = _mover_score_of_finished(c0, c1)
+            continue
+        count[i] = 1
+        if given is not None and int(i) in given:
+            answer(i, *given[int(i)])
+            continue
+        st, score, bound, nodes, _ = leaf(i, 1)
+        if st == L.SOLVE_SOLVED:
+            answer(i, score, bound)
+        elif budget <= 1:
+            state[i] = NODE_OVER_BUDGET
+    history = []
+
+    def fold_mark_filter():
+        _graph_fold(g, lo, hi)
+        needed = _graph_mark(g, lo, hi, wa, wb)
+        history.append(needed)
+        state[(state == _NODE_PENDING) & ~needed] = NODE_DROPPED
+
+    fold_mark_filter()
+    launches = 0
+    while (state == _NODE_PENDING).any():
+        launches += 1
+        for i in np.nonzero(state == _NODE_PENDING)[0]:
+            if int(i) not in full:
+                full[int(i)] = leaf(i, budget)
+            st, score, bound, nodes, clean = full[int(i)]
+            step = min(budget - int(count[i]), quota)
+            reach = int(count[i]) + step
+            if st == L.SOLVE_SOLVED and nodes <= reach:
+                count[i] = nodes
+                if nodes < reach or clean:
+                    answer(i, score, bound)
+                    continue
+            else:
+                count[i] = reach
+            if count[i] >= budget:
+                state[i] = NODE_OVER_BUDGET
+        fold_mark_filter()
+    status, score, bound, outcome, final_age = _graph_root_answers(g, lo, hi, wa, wb)
+    report = {"lo": lo.astype(np.int8), "hi": hi.astype(np.int8), "state": state, "nodes": count, "table_hits": np.zeros(n_nodes, dtype=np.int64),
+              "alpha": wa.astype(np.int8), "beta": wb.astype(np.int8), "launches": launches, "needed": history, "graph": g}
+    return (status, score, bound, outcome, final_age, _graph_root_sums(g, count), np.zeros(len(status), dtype=np.int64)), report
+
+
+def _finish_graph(g, answers):
+    status, score, bound, outcome, final_age, nodes, hits = (np.asarray(x)[g.inverse] for x in answers)
+    return _finish_window(status, outcome, final_age, nodes, hits, score, bound)
+
+
+def drive_host(rows, alpha, beta, driver_plies, node_budget=None, nodes_per_launch=None, leaf_solver=_host_leaf):
+    """The root driver without a device: ``(Windowed, report)`` for `rows` (Boards, pairs or uint64 [n, 2]) with the window
+    `alpha`, `beta` (scalars, per-row arrays, or both None), each row spread over the leaves `driver_plies` (1..8) below it.
+
+    The leaves are searched with ``solve_host(window=)`` from their static windows, table-free, and the launches of the
+    device are modelled: a leaf that needs N nodes has entered min(N, 1 + t * nodes_per_launch, node_budget) after launch
+    t; it is answered in the launch that enters its last node if quota is left then or nothing but cut-offs follows that
+    node, else in the next; it is over budget when the count reaches node_budget unanswered.  After k_solve_init's answers
+    and after every launch the intervals are folded up, the needed nodes marked down, and the leaves no undecided row needs
+    dropped -- so states, intervals and node counts are what c4_solve_graph reports table-free, bit for bit.
+
+    report: per node, levels concatenated, lo, hi int8, state int8 (NODE_*), nodes, table_hits int64, the static windows
+    alpha, beta, and launches, needed (the marks after k_solve_init and after each launch) and graph (the ``Graph``).
+    leaf_solver(c0, c1, alpha, beta, node_budget) -> (status, score, bound, nodes, clean) replaces the search."""
+    plies = _check_driver_plies(driver_plies)
+    rows = _rows_u64(rows)
+    a, b = _window_arrays(alpha, beta, len(rows))
+    g = _build_graph(rows, a, b, plies, _children_host)
+    answers, report = drive_graph_host(g, node_budget, nodes_per_launch, leaf_solver)
+    return _finish_graph(g, answers), report
+
+
+def _check_graph(g):
+    """The binding's own checks of a ``Graph``, before any device call: what c4_solve_graph checks again."""
+    start = np.asarray(g.level_start, dtype=np.int64)
+    if start.ndim != 1 or not 1 <= len(start) - 2 <= 8:
+        raise ValueError("a graph has 2..9 levels; level_start has %d entries" % start.size)
+    if start[0] != 0 or (np.diff(start) < 0).any():
+        raise ValueError("level_start must begin at 0 and not decrease")
+    n_nodes = int(start[-1])
+    child = np.asarray(g.child)
+    if child.shape != (n_nodes, WIDTH) or len(g.color0) != n_nodes or len(g.color1) != n_nodes:
+        raise ValueError("color0, color1 and child have one entry a node (%d)" % n_nodes)
+    if start[-1] - start[-2] > GRAPH_MAX_LEAVES:
+        raise ValueError("the last level has %d nodes, a graph takes %d" % (start[-1] - start[-2], GRAPH_MAX_LEAVES))
+    level = np.searchsorted(start, np.arange(n_nodes), side="right") - 1
+    nxt_lo = np.append(start, n_nodes)[level + 1][:, None]
+    nxt_hi = np.append(start, n_nodes)[level + 2][:, None]
+    bad = np.nonzero((child != -1) & ((child < nxt_lo) | (child >= nxt_hi)))
+    if len(bad[0]):
+        raise ValueError("node %d, column %d: child %d is not in the next level" % (bad[0][0], bad[1][0], child[bad[0][0], bad[1][0]]))
+    orphan = np.ones(n_nodes, dtype=bool)
+    orphan[:int(start[1])] = False
+    orphan[child[child >= 0]] = False
+    if orphan.any():
+        raise ValueError("node %d has no parent" % np.nonzero(orphan)[0][0])
+    if (g.alpha is None) != (g.beta is None):
+        raise ValueError("alpha and beta are given together, or both are None")
+    if g.alpha is not None:
+        _window_arrays(g.alpha, g.beta, int(start[1]))
+
+
+def solve_graph(g, node_budget=None, nodes_per_launch=None, device=0, table=None):
+    """c4_solve_graph on a ``Graph`` (``_build_graph``): the answers of level 0, (status, score, bound, outcome code,
+    final_age, nodes, table_hits), and the per-node report {lo, hi, state, nodes, table_hits} -- ``drive_graph_host``'s,
+    from the device.  For tests and tools; the public calls take ``driver_plies``."""
+    import ctypes as C
+    _check_graph(g)
+    if table is not None:
+        device = table.device
+    n_nodes, n0 = len(g.child), int(g.level_start[1])
+    status, score, bound, outcome, age = (np.zeros(n0, dtype=np.int8) for _ in range(5))
+    nodes, hits = (np.zeros(n0, dtype=np.int64) for _ in range(2))
+    report = {"lo": np.zeros(n_nodes, dtype=np.int8), "hi": np.zeros(n_nodes, dtype=np.int8), "state": np.zeros(n_nodes, dtype=np.int8),
+              "nodes": np.zeros(n_nodes, dtype=np.int64), "table_hits": np.zeros(n_nodes, dtype=np.int64)}
+    i8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int8)) if a is not None else None  # noqa: E731
+    i64 = lambda a: a.ctypes.data_as(L._i64p)  # noqa: E731
+    c0, c1 = (np.ascontiguousarray(x, dtype=np.uint64) for x in (g.color0, g.color1))
+    start = np.ascontiguousarray(g.level_start, dtype=np.int64)
+    child = np.ascontiguousarray(g.child, dtype=np.int32)
+    a = None if g.alpha is None else np.ascontiguousarray(g.alpha, dtype=np.int8)
+    b = None if g.beta is None else np.ascontiguousarray(g.beta, dtype=np.int8)
+    _check(L.load().c4_solve_graph(int(device), table.handle if table is not None else None, c0.ctypes.data_as(L._u64p),
+                                   c1.ctypes.data_as(L._u64p), i64(start), len(start) - 1, child.ctypes.data_as(C.POINTER(C.c_int32)),
+                                   i8(a), i8(b), int(node_budget or 0), int(nodes_per_launch or 0), i8(status), i8(score), i8(bound),
+                                   i8(outcome), i8(age), i64(nodes), i64(hits), i8(report["lo"]), i8(report["hi"]), i8(report["state"]),
+                                   i64(report["nodes"]), i64(report["table_hits"])))
+    report["graph"] = g
+    return (status, score, bound, outcome, age, nodes, hits), report
+
+
+def _split_for_graphs(n, build):
+    """``build(lo, hi)`` -> Graph for the rows [lo, hi), halved until no graph's last level passes GRAPH_MAX_LEAVES."""
+    todo, out = [(0, n)], []
+    while todo:
+        lo, hi = todo.pop()
+        g = build(lo, hi)
+        leaves = int(g.level_start[-1] - g.level_start[-2])
+        if leaves > GRAPH_MAX_LEAVES and hi - lo > 1:
+            mid = (lo + hi) // 2
+            todo += [(mid, hi), (lo, mid)]
+        elif leaves > GRAPH_MAX_LEAVES:
+            raise ValueError("row %d alone has %d distinct descendants %d plies down, a graph takes %d: give fewer driver_plies" % (
+                lo, leaves, len(g.level_start) - 2, GRAPH_MAX_LEAVES))
+        else:
+            out.append((lo, hi, g))
+    return out
+
+
+def _drive(rows, alpha, beta, driver_plies, node_budget, nodes_per_launch, device, table, host, tally=None):
+    """``Windowed`` of uint64 [n, 2] `rows` with windows int8 [n] (or None, None) through the root driver: on the device
+    (c4_solve_graph, the children listed by c4_solve_children_dev) or, host=True, ``drive_graph_host``.  tally: a dict that
+    gets the count of nodes per state name (NODE_STATE_NAMES) added."""
+    plies = _check_driver_plies(driver_plies)
+    n = len(rows)
+    if table is not None and not host:
+        device = table.device
+
+    def children_on_device(level):
+        import torch
+        children, legal = _children_dev(_packed_on_device(torch.from_numpy(np.ascontiguousarray(level).view(np.int64)), device))
+        return children.cpu().numpy().view(np.uint64).reshape(-1, WIDTH, 2), legal.cpu().numpy() != 0
+
+    children_of = _children_host if host else children_on_device
+    parts = _split_for_graphs(n, lambda lo, hi: _build_graph(rows[lo:hi], None if alpha is None else alpha[lo:hi],
+                                                             None if beta is None else beta[lo:hi], plies, children_of))
+    cols = [[] for _ in range(7)]
+    for lo, hi, g in sorted(parts, key=lambda p: p[0]):
+        if host:
+            answers, report = drive_graph_host(g, node_budget, nodes_per_launch)
+        else:
+            answers, report = solve_graph(g, node_budget, nodes_per_launch, device, table)
+        if tally is not None:
+            for code, name in NODE_STATE_NAMES.items():
+                tally[name] = tally.get(name, 0) + int((report["state"] == code).sum())
+        for col, x in zip(cols, answers):
+            col.append(np.asarray(x)[g.inverse])
+    status, score, bound, outcome, final_age, nodes, hits = (np.concatenate(c) if c else np.zeros(0, dtype=np.int8) for c in cols)
+    return _finish_window(status, outcome, final_age, nodes, hits, score, bound)
 
 
 # -- grid_search's triple --------------------------------------------------------------------------------------------------
@@ -991,9 +1408,18 @@ def _first_occurrences(rows):
     return np.ascontiguousarray(rows[np.sort(first)])
 
 
-def _window_solver(node_budget, nodes_per_launch, device, table, host):
+def _window_solver(node_budget, nodes_per_launch, device, table, host, driver_plies=0, tally=None):
     """staged_labels' window_solver on the device (c4_solve_window_dev) or, host=True, on ``solve_host`` (table: a dict or a
-    ``HostTable``)."""
+    ``HostTable``); with driver_plies the root driver on either, each stage one driven batch."""
+    if driver_plies:
+        if host and table is not None:
+            raise ValueError("host=True drives table-free")
+
+        def driven(rows, alpha, beta):
+            res = _drive(np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2), np.ascontiguousarray(alpha, dtype=np.int8),
+                         np.ascontiguousarray(beta, dtype=np.int8), driver_plies, node_budget, nodes_per_launch, device, table, host, tally)
+            return res.status, res.score, res.nodes, res.table_hits
+        return driven
     if host:
         def on_host(rows, alpha, beta):
             ans = [solve_host((int(c0), int(c1)), node_budget, table=table, window=(int(a), int(b))) for (c0, c1), a, b in zip(rows, alpha, beta)]
@@ -1010,7 +1436,7 @@ def _window_solver(node_budget, nodes_per_launch, device, table, host):
     return on_device
 
 
-def _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors):
+def _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors, driver_plies=0):
     import torch
     from .stats import LabelledSet
     t0 = time.perf_counter()
@@ -1022,7 +1448,8 @@ def _label_staged(boards, node_budget, nodes_per_launch, device, table, host, wi
         packed = _packed_on_device(boards, device)
         rows_in, out_dev = _rows_u64(packed), packed.device
     rows = _first_occurrences(rows_in)
-    solver_fn = _window_solver(node_budget, nodes_per_launch, device, table, host)
+    tally = {}
+    solver_fn = _window_solver(node_budget, nodes_per_launch, device, table, host, driver_plies, tally)
     st = staged_labels(rows, solver_fn, stage2=with_priors)
     keep = st["status"] == L.SOLVE_SOLVED
     values = torch.from_numpy((st["outcome"][keep].astype(np.float32) * np.float32(0.5)))
@@ -1037,20 +1464,26 @@ def _label_staged(boards, node_budget, nodes_per_launch, device, table, host, wi
     report = {"positions": len(rows_in), "distinct": len(rows), "labelled": len(ls), "nodes": st["stage1_nodes"] + st["stage2_nodes"],
               "exact": False, "table_log2_entries": getattr(table, "log2_entries", None),
               "table_hits": st["stage1_hits"] + st["stage2_hits"]}
+    if driver_plies:
+        report["driver_plies"] = int(driver_plies)
+        report["driver_nodes"] = tally      # the graphs' nodes by state: interior, self_answering, answered, over_budget, dropped
     report.update({k: st[k] for k in ("stage1_rows", "stage1_nodes", "stage1_unknown", "stage2_rows", "stage2_nodes", "stage2_unknown")})
     report.update({name: int(counts[code]) for code, name in STATUS_NAMES.items()})
     report["seconds"] = time.perf_counter() - t0
     return ls, report
 
 
-def label_values(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, host=False):
+def label_values(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, host=False, driver_plies=0):
     """Label positions with their outcome alone: ``(LabelledSet without priors, report)``, the kind of set the reference
     scores by value only.  This is stage 1 of ``label(exact=False)`` -- one search per distinct position with the window
-    (-1, +1), at any depth -- and nothing else; rows, order and report as there."""
-    return _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors=False)
+    (-1, +1), at any depth -- and nothing else; rows, order and report as there.  driver_plies: ``solve_window``'s."""
+    if driver_plies:
+        _check_driver_plies(driver_plies)
+    return _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors=False, driver_plies=driver_plies)
 
 
-def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, split_plies=0, exact=True, host=False, deep=False):
+def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, split_plies=0, exact=True, host=False, deep=False,
+          driver_plies=0):
     """Label positions with their exact outcome: returns ``(LabelledSet, report)``.
 
     Each distinct position is solved once, together with its up-to-seven children (c4_solve_children_dev lists them) in one
@@ -1070,11 +1503,19 @@ def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None,
     report says exact: False and, per stage, stage1_rows / stage1_nodes / stage1_unknown and stage2_rows / stage2_nodes /
     stage2_unknown (nodes = stage1_nodes + stage2_nodes; unknown = stage1_unknown + the positions a stage-2 row leaves
     open).  host=True (with exact=False) runs the same staging on ``solve_host`` -- no GPU; `table` is then a dict or a
-    ``HostTable``."""
+    ``HostTable``.  driver_plies=k (with exact=False, not with split_plies) runs each stage through the root driver
+    (``solve_window``): the same labels wherever both label a row, and a row stays unknown only where a descendant the proof
+    needs does; with host=True no table is taken."""
+    if driver_plies:
+        _check_driver_plies(driver_plies)
+        if split_plies:
+            raise ValueError("driver_plies and split_plies are two ways to spread a position: give one")
+        if exact:
+            raise ValueError("driver_plies belongs to exact=False: the driver folds bounds, not exact scores")
     if not exact:
         if split_plies:
             raise ValueError("split_plies belongs to exact=True: the staged labelling does not split")
-        return _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors=True)
+        return _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors=True, driver_plies=driver_plies)
     if host:
         raise ValueError("host=True labels with exact=False only")
     import torch

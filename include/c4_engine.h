@@ -759,6 +759,44 @@ int c4_solve_window(int device, c4_solve_table *table, const uint64_t *color0, c
                     const int8_t *beta, int64_t n, int64_t node_budget, int64_t nodes_per_launch, int8_t *status, int8_t *score,
                     int8_t *bound, int8_t *outcome, int8_t *final_age, int64_t *nodes, int64_t *table_hits);
 
+/* -- the root driver: alpha-beta over a graph of positions (c4_solve.hip) ------------------------------------------------ */
+/* c4_solve_graph answers the rows of level 0 of a layered graph from windowed searches of its last level: one hard
+ * position spread over many lanes, folded back as intervals, so that an unfinished descendant costs the answer only
+ * where the proof needs it.  (An addition: C4_ABI_VERSION stays.)  Every array is in host memory.
+ *   color0, color1  uint64 [n_nodes], the levels concatenated, level 0 first
+ *   level_start     int64 [n_levels + 1]: level j is the nodes level_start[j] .. level_start[j + 1] - 1; level_start[0] = 0,
+ *                   not decreasing; 2 <= n_levels <= C4_SOLVE_GRAPH_MAX_PLIES + 1; the last level has at most 2^20 nodes
+ *   child           int32 [n_nodes][7]: the node of the position after each column -- a node of the next level -- or -1;
+ *                   every node below level 0 is some node's child, the last level has no children
+ *   alpha, beta     int8 [n_0], the windows of level 0 as c4_solve_window takes them, or both NULL
+ * A malformed graph or window is C4_EINVAL, the message names the first offender, and no device is touched.
+ * Windows are static: a child of a node with (a, b) has (-b, -a), a node with several parents the union.  The last level
+ * is searched by c4_solve_window's kernels from those windows, with `table` (or NULL), node_budget and nodes_per_launch as
+ * there.  A node that has no child answers for itself: a finished position with its score, anything else not at all.
+ * Every node has an interval [lo, hi] that contains its exact score for its mover: [s, s] for an exact answer, [s, 42]
+ * for a lower bound, [-42, s] for an upper bound, [-42, 42] without an answer; above the leaves lo = max over children of
+ * -hi, hi = max over children of -lo.  A row of level 0 with window (a, b) is answered once lo == hi (the score, its kind
+ * against the window), lo >= b (a lower bound lo) or hi <= a (an upper bound hi).  After k_solve_init and after every
+ * launch the intervals are folded and the leaves that no unanswered row can still use are dropped: they leave the search.
+ *   status .. table_hits  [n_0], as c4_solve_window answers a row: SOLVED where the row is decided, UNKNOWN where it is not,
+ *                         TERMINAL / INVALID for a row that answers for itself; nodes and table_hits are the sums over
+ *                         the row's distinct nodes of the last level
+ *   node_lo, node_hi int8, node_state int8 (C4_SOLVE_NODE_*), node_nodes, node_table_hits int64 [n_nodes]: each may be
+ *                         NULL; nodes and table_hits are zero above the last level
+ * Table-free, every output is a function of the inputs: connect4_amd/solver.py drive_graph_host computes the same. */
+#define C4_SOLVE_GRAPH_MAX_PLIES  8
+#define C4_SOLVE_NODE_INTERIOR     0   /* has children: its interval is folded from theirs */
+#define C4_SOLVE_NODE_SELF         1   /* no child above the last level, or a finished or invalid position in it */
+#define C4_SOLVE_NODE_ANSWERED     2   /* a searched node whose root returned */
+#define C4_SOLVE_NODE_OVER_BUDGET  3   /* a searched node that reached node_budget */
+#define C4_SOLVE_NODE_DROPPED      4   /* a searched node taken out of the search: no undecided row needed it */
+#define C4_SOLVE_NODE_PENDING      5   /* between launches only: never reported */
+int c4_solve_graph(int device, c4_solve_table *table, const uint64_t *color0, const uint64_t *color1, const int64_t *level_start,
+                   int n_levels, const int32_t *child, const int8_t *alpha, const int8_t *beta, int64_t node_budget,
+                   int64_t nodes_per_launch, int8_t *status, int8_t *score, int8_t *bound, int8_t *outcome, int8_t *final_age,
+                   int64_t *nodes, int64_t *table_hits, int8_t *node_lo, int8_t *node_hi, int8_t *node_state, int64_t *node_nodes,
+                   int64_t *node_table_hits);
+
 int c4_abi_version(void);
 
 #ifdef __cplusplus

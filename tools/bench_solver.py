@@ -37,13 +37,16 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--table", action="store_true", help="measure the deep search and its transposition table instead (below)")
 ap.add_argument("--budget-log2", type=int, default=20, help="--table: the node budget of one row in the budgeted parts")
 ap.add_argument("--window", action="store_true", help="measure the labelling by outcome windows instead (below)")
+ap.add_argument("--driver", action="store_true", help="measure the root driver against the undriven labelling instead (below)")
+ap.add_argument("--driver-budgets-log2", default="20,24", help="--driver: the node budgets of one row")
+ap.add_argument("--driver-plies", default="0,2,3", help="--driver: the driver_plies to run, 0 = undriven")
 ap.add_argument("--part", default="open,seven,seven_big", help="--window: the parts to run; the others are kept from the file")
 ap.add_argument("--big-budget-log2", type=int, default=24, help="--window: the node budget of one row in seven_big")
 ap.add_argument("--big-count", type=int, default=4096, help="--window: seven_big takes the first N of the 4,096 positions")
 args = ap.parse_args()
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "solver_window.json" if args.window else "solver_table.json" if args.table else "solver.json")
-out = {"command": "python tools/bench_solver.py%s --out profiles/%s" % (" --window" if args.window else " --table" if args.table else "",
+    args.out = os.path.join(ROOT, "profiles", "solver_driver.json" if args.driver else "solver_window.json" if args.window else "solver_table.json" if args.table else "solver.json")
+out = {"command": "python tools/bench_solver.py%s --out profiles/%s" % (" --driver" if args.driver else " --window" if args.window else " --table" if args.table else "",
                                                                        os.path.basename(args.out)),
        "device": torch.cuda.get_device_name(0)}
 
@@ -204,6 +207,33 @@ def bench_window():
         dump()
 
 
+def bench_driver():
+    """--driver: writes profiles/solver_driver.json (single runs; nothing is gated on these figures)
+
+      the workload of profiles/solver_window.json's seven / seven_big: random_openings(7, 4096, seed 0) through
+      label(exact=False), Table(27) cleared before each run, at each budget of --driver-budgets-log2 and each driver_plies of
+      --driver-plies (0: the undriven labelling, the baseline of the same session): positions labelled, share unknown, nodes
+      entered, seconds, and the graphs' leaves answered, over budget and dropped.  The file is rewritten after every run."""
+    from connect4_amd.solver import Table, random_openings
+    if os.path.exists(args.out):
+        out.update({k: v for k, v in json.load(open(args.out)).items() if k.startswith("budget_")})
+    t = packed(random_openings(7, 4096, seed=0))
+    solve(packed([random_playout(np.random.RandomState(1), 30)]))        # warm
+    with Table(27) as table:
+        for log2 in [int(x) for x in args.driver_budgets_log2.split(",") if x]:
+            for k in [int(x) for x in args.driver_plies.split(",") if x]:
+                table.clear()
+                (ls, report), dt = timed(lambda: label(t, node_budget=1 << log2, table=table, exact=False, driver_plies=k))
+                run = {"labelled": report["labelled"], "share_unknown": report["unknown"] / max(1, report["distinct"]), "nodes": report["nodes"],
+                       "seconds": dt, "leaves": report.get("driver_nodes"), "report": report}
+                out.setdefault("budget_2^%d" % log2, {})["driver_plies_%d" % k] = run
+                print("2^%d nodes a row, driver_plies %d: %s" % (log2, k, json.dumps(run)), flush=True)
+                dump()
+
+
+if args.driver:
+    bench_driver()
+    sys.exit(0)
 if args.table:
     bench_table()
     sys.exit(0)

@@ -27,7 +27,10 @@ dropped and counted.
 (-1, +1) and one null-window search per child that could keep the outcome, instead of exact scores of the position and all
 its children -- the same file wherever both label a row, for a fraction of the nodes.  --values-only stops after the first
 of those searches and writes values without priors (label_values), the kind of set the reference scores by value only.
-Both take positions of any depth with or without --table-log2, from --openings or from data sources; neither splits."""
+Both take positions of any depth with or without --table-log2, from --openings or from data sources; neither splits.
+--driver-plies K (1..8) runs their searches through the root driver (solver.solve_window driver_plies): each position is
+spread over the lanes of its descendants K plies down and their bounds are folded back, so a position stays unknown only
+where a descendant its proof needs does.  The file is the same wherever both label a row."""
 import argparse
 import json
 import os
@@ -58,6 +61,7 @@ def main(argv=None):
     ap.add_argument("--count", type=int, default=4096, help="with --openings: how many distinct positions")
     ap.add_argument("--table-log2", type=int, default=None, metavar="N", help="solve with a transposition table of 2^N entries")
     ap.add_argument("--split-plies", type=int, default=0, metavar="K")
+    ap.add_argument("--driver-plies", type=int, default=0, metavar="K", help="with --outcome-only / --values-only: the root driver, K plies deep")
     ap.add_argument("--outcome-only", action="store_true", help="label from outcome windows and null windows (label(exact=False))")
     ap.add_argument("--values-only", action="store_true", help="values without priors, one outcome-window search a position (label_values)")
     ap.add_argument("--node-budget", type=int, default=None)
@@ -76,6 +80,10 @@ def main(argv=None):
     staged = a.outcome_only or a.values_only
     if staged and a.split_plies:
         ap.error("--split-plies belongs to the exact labelling")
+    if a.driver_plies and not staged:
+        ap.error("--driver-plies belongs to --outcome-only and --values-only")
+    if a.driver_plies and not 1 <= a.driver_plies <= 8:
+        ap.error("--driver-plies takes 1..8")
     if a.openings is not None and 42 - a.openings > 24 and a.table_log2 is None and not a.split_plies and not staged:
         ap.error("positions with more than 24 empty squares need --table-log2 (or --split-plies)")
     import torch
@@ -111,9 +119,9 @@ def main(argv=None):
         pick = torch.sort(torch.randperm(late, generator=g)[:a.max_positions]).values
         boards = boards[pick.to(dev)].contiguous()
     if a.values_only:
-        ls, report = label_values(boards, node_budget=a.node_budget, device=a.device, table=table)
+        ls, report = label_values(boards, node_budget=a.node_budget, device=a.device, table=table, driver_plies=a.driver_plies)
     elif a.outcome_only:
-        ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, exact=False)
+        ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, exact=False, driver_plies=a.driver_plies)
     else:
         ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, split_plies=a.split_plies)
     if table is not None:
