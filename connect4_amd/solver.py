@@ -25,6 +25,7 @@ The integer score: a game o wins at age ``a`` scores ``43 - a``, one x wins ``a 
 move inside the search.  It is strictly monotone in the reference's float, so max / min over it pick what the reference's
 max / min pick; the float itself is formed once, from outcome and age, by the division the reference performs.
 """
+import ctypes as C
 import time
 from collections import namedtuple
 from typing import Sequence
@@ -376,6 +377,23 @@ def _is_tensor(x):
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 
 
+def _rows_u64(boards):
+    """uint64 [n, 2] of a packed tensor, a uint64 / int64 [n, 2] array or a sequence of Boards or pairs."""
+    if _is_tensor(boards):
+        return boards.cpu().numpy().view(np.uint64).reshape(-1, 2)
+    if isinstance(boards, np.ndarray):
+        return np.ascontiguousarray(boards).view(np.uint64).reshape(-1, 2)
+    return np.stack(_bits(boards), axis=1) if len(boards) else np.zeros((0, 2), dtype=np.uint64)
+
+
+def _ptr(x):
+    """What the C entry points take: the address of a device tensor, or of a NumPy array typed by its dtype; None (an optional
+    argument left out) stays None."""
+    if x is None:
+        return None
+    return C.c_void_p(x.data_ptr()) if _is_tensor(x) else x.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(x.dtype)))
+
+
 def _packed_on_device(boards, device):
     """A contiguous int64 [n, 2] cuda tensor of `boards` (a packed tensor on any device, or a sequence of Boards)."""
     import torch
@@ -402,7 +420,6 @@ class Table:
     frees it (also on garbage collection and at the end of a ``with`` block)."""
 
     def __init__(self, log2_entries=24, device=0):
-        import ctypes as C
         self._h = None
         h = C.c_void_p()
         _check(L.load().c4_solve_table_create(int(device), int(log2_entries), C.byref(h)))
@@ -427,7 +444,7 @@ class Table:
         """The table's ``2 ** log2_entries`` words as a ``numpy.uint64`` array (c4_solve_table_read): every store of every
         call that has returned is in it.  ``entry_fields`` takes it apart; ``HostTable.words`` has the same layout."""
         out = np.empty(self.entries, dtype=np.uint64)
-        _check(L.load().c4_solve_table_read(self.handle, out.ctypes.data_as(L._u64p), out.size))
+        _check(L.load().c4_solve_table_read(self.handle, _ptr(out), out.size))
         return out
 
     def close(self):
@@ -453,7 +470,6 @@ def _solve_dev(packed, node_budget=None, nodes_per_launch=None, table=None, deep
     c4_solve_deep_dev; with `window` = (alpha, beta), int8 NumPy arrays or both None, c4_solve_window_dev.  Returns device
     tensors (status int8, outcome int8, final_age int8, nodes int64, table_hits int64) and, with a window, (score int8, bound
     int8) after them."""
-    import ctypes as C
     import torch
     n = int(packed.shape[0])
     dev = packed.device
@@ -466,18 +482,17 @@ def _solve_dev(packed, node_budget=None, nodes_per_launch=None, table=None, deep
         with torch.cuda.device(dev):
             a_dev, b_dev = (torch.from_numpy(x).to(dev) if x is not None else None for x in (window or (None, None)))
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
             handle = table.handle if table is not None else None
             size = (n, int(node_budget or 0), int(nodes_per_launch or 0))
             lib = L.load()
             if window is not None:
-                rc = lib.c4_solve_window_dev(idx, stream, handle, ptr(packed), ptr(a_dev), ptr(b_dev), *size, ptr(status), ptr(extra[0]),
-                                             ptr(extra[1]), ptr(outcome), ptr(age), ptr(nodes), ptr(hits))
+                rc = lib.c4_solve_window_dev(idx, stream, handle, _ptr(packed), _ptr(a_dev), _ptr(b_dev), *size, _ptr(status), _ptr(extra[0]),
+                                             _ptr(extra[1]), _ptr(outcome), _ptr(age), _ptr(nodes), _ptr(hits))
             elif deep or table is not None:
-                rc = lib.c4_solve_deep_dev(idx, stream, handle, ptr(packed), *size, ptr(status), ptr(outcome), ptr(age), ptr(nodes),
-                                           ptr(hits))
+                rc = lib.c4_solve_deep_dev(idx, stream, handle, _ptr(packed), *size, _ptr(status), _ptr(outcome), _ptr(age), _ptr(nodes),
+                                           _ptr(hits))
             else:
-                rc = lib.c4_solve_dev(idx, stream, ptr(packed), *size, ptr(status), ptr(outcome), ptr(age), ptr(nodes))
+                rc = lib.c4_solve_dev(idx, stream, _ptr(packed), *size, _ptr(status), _ptr(outcome), _ptr(age), _ptr(nodes))
             _check(rc)
     return (status, outcome, age, nodes, hits) + extra
 
@@ -485,7 +500,6 @@ def _solve_dev(packed, node_budget=None, nodes_per_launch=None, table=None, deep
 def _solve_arrays(boards, node_budget, nodes_per_launch, device, table, deep, window=None):
     """``_solve_dev`` for a sequence of Boards or pairs, through the entry points that take host arrays (c4_solve, c4_solve_deep,
     c4_solve_window): the same tuple, of NumPy arrays."""
-    import ctypes as C
     n = len(boards)
     status, outcome, age = (np.zeros(n, dtype=np.int8) for _ in range(3))
     extra = tuple(np.zeros(n, dtype=np.int8) for _ in range(2)) if window is not None else ()     # score, bound
@@ -493,19 +507,17 @@ def _solve_arrays(boards, node_budget, nodes_per_launch, device, table, deep, wi
     hits = np.zeros(n, dtype=np.int64)
     if n:
         bits = _bits(boards)
-        c0, c1 = (x.ctypes.data_as(L._u64p) for x in bits)
-        i8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int8)) if a is not None else None  # noqa: E731
-        i64 = lambda a: a.ctypes.data_as(L._i64p)  # noqa: E731
+        c0, c1 = (_ptr(x) for x in bits)
         handle = table.handle if table is not None else None
         size = (n, int(node_budget or 0), int(nodes_per_launch or 0))
         lib = L.load()
         if window is not None:
-            rc = lib.c4_solve_window(device, handle, c0, c1, i8(window[0]), i8(window[1]), *size, i8(status), i8(extra[0]), i8(extra[1]),
-                                     i8(outcome), i8(age), i64(nodes), i64(hits))
+            rc = lib.c4_solve_window(device, handle, c0, c1, _ptr(window[0]), _ptr(window[1]), *size, _ptr(status), _ptr(extra[0]), _ptr(extra[1]),
+                                     _ptr(outcome), _ptr(age), _ptr(nodes), _ptr(hits))
         elif deep:
-            rc = lib.c4_solve_deep(device, handle, c0, c1, *size, i8(status), i8(outcome), i8(age), i64(nodes), i64(hits))
+            rc = lib.c4_solve_deep(device, handle, c0, c1, *size, _ptr(status), _ptr(outcome), _ptr(age), _ptr(nodes), _ptr(hits))
         else:
-            rc = lib.c4_solve(device, c0, c1, *size, i8(status), i8(outcome), i8(age), i64(nodes))
+            rc = lib.c4_solve(device, c0, c1, *size, _ptr(status), _ptr(outcome), _ptr(age), _ptr(nodes))
         _check(rc)
     return (status, outcome, age, nodes, hits) + extra
 
@@ -519,7 +531,6 @@ def _solve_any(boards, node_budget, nodes_per_launch, device, table, deep, windo
 
 def _children_dev(packed):
     """c4_solve_children_dev: (children int64 [n, 7, 2], legal int8 [n, 7]) device tensors."""
-    import ctypes as C
     import torch
     n = int(packed.shape[0])
     dev = packed.device
@@ -529,8 +540,7 @@ def _children_dev(packed):
         idx = dev.index if dev.index is not None else torch.cuda.current_device()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(L.load().c4_solve_children_dev(idx, C.c_void_p(stream), C.c_void_p(packed.data_ptr()), n,
-                                                  C.c_void_p(children.data_ptr()), C.c_void_p(legal.data_ptr())))
+            _check(L.load().c4_solve_children_dev(idx, C.c_void_p(stream), _ptr(packed), n, _ptr(children), _ptr(legal)))
     return children, legal
 
 
@@ -562,7 +572,13 @@ def _finish_window(status, outcome, age, nodes, hits, score, bound):
                     np.asarray(hits, dtype=np.int64))
 
 
-# -- the split: one hard position over many lanes -------------------------------------------------------------------------
+# -- the graph: one hard position over many lanes -------------------------------------------------------------------------
+# Level 0 holds the distinct (row, window) pairs of a call, level j + 1 the distinct children of level j with mirror images
+# merged; child[node][col] is the child's index among all nodes, levels concatenated, or -1.  ``split_plies`` and
+# ``driver_plies`` both build it, search its last level and the nodes without a child as one batch, and sum nodes and hits
+# over each row's distinct last-level nodes.  The folds back to level 0 are two: the split's exact scores by max / min
+# (``_graph_fold_exact``), the driver's bounds as intervals (``_graph_fold``), which answer a row, and drop descendants,
+# before every descendant is known -- so the two differ, by design, in what an UNKNOWN descendant does to a row.
 def _mirror_bits(x):
     """The left-right mirror image of uint64 bitboards (any shape)."""
     out = np.zeros_like(x)
@@ -587,73 +603,8 @@ def _unique_rows(rows):
     return uniq, np.asarray(inv, dtype=np.int64).reshape(-1)
 
 
-def _abs_score(outcome_code, age):
-    """The integer score from o's side (43 - age, age - 43, 0) of answers given as C4_RESULT_* and final age."""
-    outcome_code = np.asarray(outcome_code, dtype=np.int64)
-    age = np.asarray(age, dtype=np.int64)
-    return np.where(outcome_code == L.RESULT_OWIN, 43 - age, np.where(outcome_code == L.RESULT_XWIN, age - 43, 0))
-
-
-def _fold_level(rows, link, child_score, child_known):
-    """One ply of the fold (the rule of grid_search.py:21-32 on the integer score): for each open row of `rows` (uint64
-    [m, 2]) the max (o to move) or min (x to move) of its children's scores; link int64 [m, 7] = the child's index or -1.
-    Returns (score int64 [m], known bool [m]): known where every child is."""
-    has = link >= 0
-    at = np.where(has, link, 0)
-    s = child_score[at] if len(child_score) else np.zeros(link.shape, dtype=np.int64)
-    k = child_known[at] if len(child_known) else np.zeros(link.shape, dtype=bool)
-    ages = np.array([bin(int(a | b)).count("1") for a, b in rows], dtype=np.int64)
-    o_moves = (ages & 1) == 0
-    best_o = np.where(has, s, -99).max(axis=1) if link.shape[0] else np.zeros(0, dtype=np.int64)
-    best_x = np.where(has, s, 99).min(axis=1) if link.shape[0] else np.zeros(0, dtype=np.int64)
-    return np.where(o_moves, best_o, best_x), (k | ~has).all(axis=1)
-
-
-def _leaf_pairs(link, p_row, p_leaf, n_next):
-    """(row, leaf) pairs of a level from its links and the next level's pairs (sorted by row): each row's distinct leaves."""
-    r, c = np.nonzero(link >= 0)
-    ch = link[r, c]
-    start = np.searchsorted(p_row, np.arange(n_next))
-    count = np.bincount(p_row, minlength=n_next)
-    reps = count[ch]
-    offs = np.arange(int(reps.sum())) - np.repeat(np.cumsum(reps) - reps, reps)
-    pairs = np.stack([np.repeat(r, reps), p_leaf[np.repeat(start[ch], reps) + offs]], axis=1)
-    pairs = np.unique(pairs, axis=0) if len(pairs) else pairs.reshape(0, 2)
-    return pairs[:, 0], pairs[:, 1]
-
-
-def _fold_split(levels, links, leaf, own):
-    """The host half of ``split_plies``.  levels[j]: the distinct positions j plies below the rows (uint64 [n_j, 2]);
-    links[j]: int64 [n_j, 7], the index in levels[j + 1] of the child in each column, -1 where there is none; leaf: the
-    answers (status, outcome code, final age, nodes, hits arrays) of levels[-1]; own[j]: the same for levels[j], read only
-    where a row has no child at all (a finished or invalid position answers for itself).  Returns the answers of levels[0]:
-    a row with children is SOLVED with the folded score if every child has an answer, else UNKNOWN; its nodes and hits are
-    the sums over its distinct leaves."""
-    status, outcome, age, nodes, hits = (np.asarray(a) for a in leaf)
-    score = _abs_score(outcome, age)
-    known = (status == L.SOLVE_SOLVED) | (status == L.SOLVE_TERMINAL)
-    n_leaf = len(status)
-    p_row, p_leaf = np.arange(n_leaf), np.arange(n_leaf)
-    leaf_nodes, leaf_hits = nodes.astype(np.int64), hits.astype(np.int64)
-    for j in range(len(links) - 1, -1, -1):
-        link = links[j]
-        o_status, o_outcome, o_age = (np.asarray(a) for a in own[j][:3])
-        is_open = (link >= 0).any(axis=1)
-        f_score, f_known = _fold_level(levels[j], link, score, known)
-        score = np.where(is_open, f_score, _abs_score(o_outcome, o_age))
-        known = np.where(is_open, f_known, (o_status == L.SOLVE_SOLVED) | (o_status == L.SOLVE_TERMINAL))
-        status = np.where(is_open, np.where(f_known, L.SOLVE_SOLVED, L.SOLVE_UNKNOWN), o_status).astype(np.int8)
-        p_row, p_leaf = _leaf_pairs(link, p_row, p_leaf, len(levels[j + 1]))
-    n = len(levels[0])
-    answered = known & (status != L.SOLVE_INVALID)
-    out_code = np.where(answered, np.where(score > 0, L.RESULT_OWIN, np.where(score < 0, L.RESULT_XWIN, L.RESULT_DRAW)), -1).astype(np.int8)
-    out_age = np.where(answered, np.where(score != 0, 43 - np.abs(score), SIZE), -1).astype(np.int8)
-    if links:
-        out_nodes = np.bincount(p_row, weights=leaf_nodes[p_leaf], minlength=n).astype(np.int64)
-        out_hits = np.bincount(p_row, weights=leaf_hits[p_leaf], minlength=n).astype(np.int64)
-    else:
-        out_nodes, out_hits = leaf_nodes, leaf_hits
-    return status, out_code, out_age, out_nodes, out_hits
+def _ages(rows):
+    return _popcount64(rows[:, 0] | rows[:, 1]) if len(rows) else np.zeros(0, dtype=np.int64)
 
 
 def _children_host(rows):
@@ -674,48 +625,121 @@ def _children_host(rows):
     return children, legal
 
 
-def _split_levels(rows, split_plies, children_of):
-    """The positions 0..split_plies plies below uint64 [n, 2] `rows`, each level's distinct ones with mirror images merged
-    below the rows themselves: (levels, links, childless, inverse) -- see _fold_split; childless[j]: the rows of levels[j]
-    without a child; levels[0][inverse] = rows.  children_of: _children_host, or c4_solve_children_dev's wrapper."""
-    level, inverse = _unique_rows(rows)
-    levels, links, childless = [level], [], []
-    for _ in range(split_plies):
+def _children_of(device):
+    """``_children_host`` on cuda:`device`: c4_solve_children_dev around uint64 [m, 2] rows."""
+    def children_of(rows):
+        import torch
+        children, legal = _children_dev(_packed_on_device(torch.from_numpy(np.ascontiguousarray(rows).view(np.int64)), device))
+        return children.cpu().numpy().view(np.uint64).reshape(-1, WIDTH, 2), legal.cpu().numpy() != 0
+    return children_of
+
+
+Graph = namedtuple("Graph", "color0 color1 level_start child alpha beta inverse")
+
+
+def _build_graph(rows, alpha, beta, plies, children_of):
+    """The graph `plies` deep below uint64 [n, 2] `rows` with windows int8 [n] (or both None: the full window): ``Graph`` of
+    color0, color1 uint64 [n_nodes], level_start int64 [plies + 2], child int32 [n_nodes, 7], alpha, beta int8 [n_0] (level
+    0's windows) and inverse int64 [n]: level-0 node ``inverse[i]`` is row i with its window.  children_of: ``_children_host``
+    or ``_children_of(device)``."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+    n = len(rows)
+    a = np.full(n, -SCORE_MAX, dtype=np.int64) if alpha is None else np.asarray(alpha, dtype=np.int64)
+    b = np.full(n, SCORE_MAX, dtype=np.int64) if beta is None else np.asarray(beta, dtype=np.int64)
+    keyed = np.concatenate([rows, (a + 64).astype(np.uint64)[:, None], (b + 64).astype(np.uint64)[:, None]], axis=1)
+    if n:
+        uniq, inverse = np.unique(keyed, axis=0, return_inverse=True)
+        inverse = np.asarray(inverse, dtype=np.int64).reshape(-1)
+    else:
+        uniq, inverse = keyed, np.zeros(0, dtype=np.int64)
+    levels, links = [np.ascontiguousarray(uniq[:, :2])], []
+    for _ in range(plies):
         ch, lg = children_of(levels[-1])
+        ch, lg = np.asarray(ch, dtype=np.uint64), np.asarray(lg).astype(bool)
         nxt, inv = _unique_rows(_canonical(ch[lg]))
         link = np.full(lg.shape, -1, dtype=np.int64)
         link[lg] = inv
         levels.append(nxt)
         links.append(link)
-        childless.append(~lg.any(axis=1))
-    return levels, links, childless, inverse
+    start = np.concatenate([[0], np.cumsum([len(lv) for lv in levels])]).astype(np.int64)
+    child = np.full((int(start[-1]), WIDTH), -1, dtype=np.int32)
+    for j, link in enumerate(links):
+        child[start[j]:start[j + 1]] = np.where(link >= 0, link + start[j + 1], -1)
+    nodes = np.concatenate(levels)
+    return Graph(np.ascontiguousarray(nodes[:, 0]), np.ascontiguousarray(nodes[:, 1]), start, child,
+                 (uniq[:, 2].astype(np.int64) - 64).astype(np.int8), (uniq[:, 3].astype(np.int64) - 64).astype(np.int8), inverse)
+
+
+def _graph_root_sums(g, *per_node):
+    """int64 [n_0] for each of `per_node` (int64 [n_nodes], read on the last level): its sum over each level-0 row's distinct
+    last-level nodes.  The walk keeps (row, leaf) pairs sorted by row and lifts them one level at a time: a row's leaves are
+    its children's, each once."""
+    first_leaf = int(g.level_start[-2])
+    p_row = p_leaf = np.arange(len(g.child) - first_leaf)
+    for j in range(len(g.level_start) - 3, -1, -1):
+        s, e, n_next = int(g.level_start[j]), int(g.level_start[j + 1]), int(g.level_start[j + 2] - g.level_start[j + 1])
+        r, c = np.nonzero(g.child[s:e] >= 0)
+        ch = g.child[s:e][r, c].astype(np.int64) - e
+        start = np.searchsorted(p_row, np.arange(n_next))
+        reps = np.bincount(p_row, minlength=n_next)[ch]
+        offs = np.arange(int(reps.sum())) - np.repeat(np.cumsum(reps) - reps, reps)
+        pairs = np.stack([np.repeat(r, reps), p_leaf[np.repeat(start[ch], reps) + offs]], axis=1)
+        pairs = np.unique(pairs, axis=0) if len(pairs) else pairs.reshape(0, 2)
+        p_row, p_leaf = pairs[:, 0], pairs[:, 1]
+    weights = (np.asarray(a, dtype=np.int64)[first_leaf:][p_leaf] for a in per_node)
+    return tuple(np.bincount(p_row, weights=w, minlength=int(g.level_start[1])).astype(np.int64) for w in weights)
+
+
+# -- the split: exact answers folded by max / min -------------------------------------------------------------------------
+def _abs_score(outcome_code, age):
+    """The integer score from o's side (43 - age, age - 43, 0) of answers given as C4_RESULT_* and final age."""
+    outcome_code = np.asarray(outcome_code, dtype=np.int64)
+    age = np.asarray(age, dtype=np.int64)
+    return np.where(outcome_code == L.RESULT_OWIN, 43 - age, np.where(outcome_code == L.RESULT_XWIN, age - 43, 0))
+
+
+def _graph_fold_exact(g, status, outcome, final_age, nodes, hits):
+    """The host half of ``split_plies``: level 0's (status, outcome code, final_age int8, nodes, hits int64) from the exact
+    answers of the searched nodes -- those without a child, and the last level -- as arrays of one entry a node, read nowhere
+    else.  The rule of grid_search.py:21-32 on the integer score, the level above the last one first: a node with children is
+    SOLVED with the max (o to move) or min (x to move) of its children's scores if every child has an answer (is SOLVED or
+    TERMINAL), else UNKNOWN; a node without children answers for itself.  Unlike ``_graph_fold`` no node is answered by a
+    bound: one UNKNOWN descendant leaves a row UNKNOWN.  nodes and hits are ``_graph_root_sums``."""
+    status = np.array(status, dtype=np.int8)
+    score = _abs_score(outcome, final_age)
+    known = (status == L.SOLVE_SOLVED) | (status == L.SOLVE_TERMINAL)
+    o_moves = (_popcount64(g.color0 | g.color1) & 1) == 0
+    for j in range(len(g.level_start) - 3, -1, -1):
+        s, e = int(g.level_start[j]), int(g.level_start[j + 1])
+        has = g.child[s:e] >= 0
+        inner = has.any(axis=1)
+        at = np.where(has, g.child[s:e], 0)
+        best = np.where(o_moves[s:e], np.where(has, score[at], -99).max(axis=1), np.where(has, score[at], 99).min(axis=1))
+        all_known = (known[at] | ~has).all(axis=1)
+        score[s:e] = np.where(inner, best, score[s:e])
+        known[s:e] = np.where(inner, all_known, known[s:e])
+        status[s:e] = np.where(inner, np.where(all_known, L.SOLVE_SOLVED, L.SOLVE_UNKNOWN), status[s:e])
+    n0 = int(g.level_start[1])
+    status, score, known = status[:n0], score[:n0], known[:n0]
+    out_code = np.where(known, np.where(score > 0, L.RESULT_OWIN, np.where(score < 0, L.RESULT_XWIN, L.RESULT_DRAW)), -1).astype(np.int8)
+    out_age = np.where(known, np.where(score != 0, 43 - np.abs(score), SIZE), -1).astype(np.int8)
+    return (status, out_code, out_age) + _graph_root_sums(g, nodes, hits)
 
 
 def _solve_split(packed, split_plies, node_budget, nodes_per_launch, table):
     import torch
-    dev = packed.device
-
-    def children_of(rows):
-        children, legal = _children_dev(torch.from_numpy(np.ascontiguousarray(rows).view(np.int64)).to(dev).contiguous())
-        return children.cpu().numpy().view(np.uint64).reshape(-1, WIDTH, 2), legal.cpu().numpy() != 0
-
-    levels, links, childless, inv0 = _split_levels(packed.cpu().numpy().view(np.uint64).reshape(-1, 2), split_plies, children_of)
-    # one batch: the last level, and above it the rows without children (they answer for themselves and cost no node)
-    parts = [lv[cl] for lv, cl in zip(levels, childless)] + [levels[-1]]
-    batch = torch.from_numpy(np.ascontiguousarray(np.concatenate(parts)).view(np.int64)).to(dev).contiguous()
-    res = [t.cpu().numpy() for t in _solve_dev(batch, node_budget, nodes_per_launch, table, deep=True)]
-    own, at = [], 0
-    for lv, cl in zip(levels, childless):
-        m = int(cl.sum())
-        filled = []
-        for a in res[:3]:
-            full = np.full(len(lv), -1, dtype=a.dtype)
-            full[cl] = a[at:at + m]
-            filled.append(full)
-        own.append(filled)
-        at += m
-    status, outcome, age, nodes, hits = _fold_split(levels, links, [a[at:] for a in res], own)
-    return _finish(status[inv0], outcome[inv0], age[inv0], nodes[inv0], hits[inv0])
+    g = _build_graph(_rows_u64(packed), None, None, split_plies, _children_of(packed.device.index))
+    # one batch, in the order of the nodes: the last level, and above it the nodes without a child (they answer for
+    # themselves and cost no node)
+    searched = ~(g.child >= 0).any(axis=1)
+    searched[int(g.level_start[-2]):] = True
+    batch = torch.from_numpy(np.stack([g.color0[searched], g.color1[searched]], axis=1).view(np.int64)).to(packed.device).contiguous()
+    answers = []
+    for t in _solve_dev(batch, node_budget, nodes_per_launch, table, deep=True):
+        a = t.cpu().numpy()
+        answers.append(np.full(len(searched), -1, dtype=a.dtype))
+        answers[-1][searched] = a
+    return _finish(*(a[g.inverse] for a in _graph_fold_exact(g, *answers)))
 
 
 def solve(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, deep=False, split_plies=0):
@@ -808,69 +832,26 @@ def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, d
     return _finish_window(*_solve_any(boards, node_budget, nodes_per_launch, device, table, True, (a, b)))
 
 
-def _ages(rows):
-    return _popcount64(rows[:, 0] | rows[:, 1]) if len(rows) else np.zeros(0, dtype=np.int64)
-
-
 def outcomes(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, driver_plies=0, host=False):
     """Who wins each position: float64 0.0 (x) / 0.5 (draw) / 1.0 (o), NaN where the budget leaves a row unknown or the row is
     invalid; a finished position answers with its own result.  One search per row with the window (-1, +1), the narrowest
     that separates win, draw and loss -- how fast is not asked, and not paid for.  driver_plies, host: ``solve_window``'s."""
     res = solve_window(boards, -1, 1, node_budget, nodes_per_launch, device, table, driver_plies, host)
-    if _is_tensor(boards):
-        rows = boards.cpu().numpy().view(np.uint64).reshape(-1, 2)
-    else:
-        rows = np.stack(_bits(boards), axis=1) if len(boards) else np.zeros((0, 2), dtype=np.uint64)
     sign = np.sign(res.score.astype(np.int64))
-    absolute = np.where(_ages(rows) & 1, -sign, sign)
+    absolute = np.where(_ages(_rows_u64(boards)) & 1, -sign, sign)
     return np.where(res.status == L.SOLVE_SOLVED, (absolute + 1) * 0.5, np.where(res.status == L.SOLVE_TERMINAL, res.outcome, np.nan))
 
 
-# -- the root driver: alpha-beta over the split ---------------------------------------------------------------------------
-# The graph: level 0 holds the distinct (row, window) pairs of a call, level j + 1 the distinct children of level j with
-# mirror images merged; child[node][col] is the child's index among all nodes, levels concatenated, or -1.  DESIGN.md
-# section 3.13 has the rules (static windows, leaf intervals, fold up, answer, mark down) and why they are sound; the
-# functions below are those rules on flat NumPy arrays, c4_solve_graph's kernels are the same rules one lane per node.
+# -- the root driver: intervals folded by alpha-beta over the same graph ----------------------------------------------------
+# DESIGN.md section 3.13 has the rules (static windows, leaf intervals, fold up, answer, mark down) and why they are sound;
+# the functions below are those rules on the ``Graph``'s flat NumPy arrays, c4_solve_graph's kernels are the same rules one
+# lane per node.
 NODE_INTERIOR, NODE_SELF, NODE_ANSWERED, NODE_OVER_BUDGET, NODE_DROPPED = (L.SOLVE_NODE_INTERIOR, L.SOLVE_NODE_SELF, L.SOLVE_NODE_ANSWERED,
                                                                            L.SOLVE_NODE_OVER_BUDGET, L.SOLVE_NODE_DROPPED)
 _NODE_PENDING = L.SOLVE_NODE_PENDING        # a leaf between launches; no report that is returned holds it
 NODE_STATE_NAMES = {NODE_INTERIOR: "interior", NODE_SELF: "self_answering", NODE_ANSWERED: "answered", NODE_OVER_BUDGET: "over_budget",
                     NODE_DROPPED: "dropped"}
 GRAPH_MAX_LEAVES = 1 << 20      # the last level of one graph (c4_solve.hip CHUNK_ROWS)
-
-Graph = namedtuple("Graph", "color0 color1 level_start child alpha beta inverse")
-
-
-def _build_graph(rows, alpha, beta, plies, children_of):
-    """The graph `plies` deep below uint64 [n, 2] `rows` with windows int8 [n] (or both None: the full window): ``Graph`` of
-    color0, color1 uint64 [n_nodes], level_start int64 [plies + 2], child int32 [n_nodes, 7], alpha, beta int8 [n_0] (level
-    0's windows) and inverse int64 [n]: level-0 node ``inverse[i]`` is row i with its window."""
-    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
-    n = len(rows)
-    a = np.full(n, -SCORE_MAX, dtype=np.int64) if alpha is None else np.asarray(alpha, dtype=np.int64)
-    b = np.full(n, SCORE_MAX, dtype=np.int64) if beta is None else np.asarray(beta, dtype=np.int64)
-    keyed = np.concatenate([rows, (a + 64).astype(np.uint64)[:, None], (b + 64).astype(np.uint64)[:, None]], axis=1)
-    if n:
-        uniq, inverse = np.unique(keyed, axis=0, return_inverse=True)
-        inverse = np.asarray(inverse, dtype=np.int64).reshape(-1)
-    else:
-        uniq, inverse = keyed, np.zeros(0, dtype=np.int64)
-    levels, links = [np.ascontiguousarray(uniq[:, :2])], []
-    for _ in range(plies):
-        ch, lg = children_of(levels[-1])
-        ch, lg = np.asarray(ch, dtype=np.uint64), np.asarray(lg).astype(bool)
-        nxt, inv = _unique_rows(_canonical(ch[lg]))
-        link = np.full(lg.shape, -1, dtype=np.int64)
-        link[lg] = inv
-        levels.append(nxt)
-        links.append(link)
-    start = np.concatenate([[0], np.cumsum([len(lv) for lv in levels])]).astype(np.int64)
-    child = np.full((int(start[-1]), WIDTH), -1, dtype=np.int32)
-    for j, link in enumerate(links):
-        child[start[j]:start[j + 1]] = np.where(link >= 0, link + start[j + 1], -1)
-    nodes = np.concatenate(levels)
-    return Graph(np.ascontiguousarray(nodes[:, 0]), np.ascontiguousarray(nodes[:, 1]), start, child,
-                 (uniq[:, 2].astype(np.int64) - 64).astype(np.int8), (uniq[:, 3].astype(np.int64) - 64).astype(np.int8), inverse)
 
 
 def _graph_windows(g):
@@ -959,19 +940,6 @@ def _graph_root_answers(g, lo, hi, wa, wb):
             outcome[i] = L.RESULT_OWIN if s > 0 else L.RESULT_XWIN if s < 0 else L.RESULT_DRAW
             final_age[i] = 43 - abs(s) if s else SIZE
     return status, score, bound, outcome, final_age
-
-
-def _graph_root_sums(g, per_node):
-    """int64 [n_0]: `per_node` (int64 [n_nodes], zero off the last level) summed over each level-0 row's distinct leaves."""
-    k = len(g.level_start) - 2
-    n_leaf = int(g.level_start[-1] - g.level_start[-2])
-    p_row, p_leaf = np.arange(n_leaf), np.arange(n_leaf)
-    for j in range(k - 1, -1, -1):
-        s, e = int(g.level_start[j]), int(g.level_start[j + 1])
-        link = np.where(g.child[s:e] >= 0, g.child[s:e].astype(np.int64) - g.level_start[j + 1], -1)
-        p_row, p_leaf = _leaf_pairs(link, p_row, p_leaf, int(g.level_start[j + 2] - g.level_start[j + 1]))
-    leaf = np.asarray(per_node, dtype=np.int64)[int(g.level_start[-2]):]
-    return np.bincount(p_row, weights=leaf[p_leaf], minlength=int(g.level_start[1])).astype(np.int64)
 
 
 def _host_leaf(c0, c1, alpha, beta, node_budget):
@@ -1085,11 +1053,14 @@ def drive_graph_host(g, node_budget=None, nodes_per_launch=None, leaf_solver=_ho
     status, score, bound, outcome, final_age = _graph_root_answers(g, lo, hi, wa, wb)
     report = {"lo": lo.astype(np.int8), "hi": hi.astype(np.int8), "state": state, "nodes": count, "table_hits": np.zeros(n_nodes, dtype=np.int64),
               "alpha": wa.astype(np.int8), "beta": wb.astype(np.int8), "launches": launches, "needed": history, "graph": g}
-    return (status, score, bound, outcome, final_age, _graph_root_sums(g, count), np.zeros(len(status), dtype=np.int64)), report
+    return (status, score, bound, outcome, final_age, _graph_root_sums(g, count)[0], np.zeros(len(status), dtype=np.int64)), report
 
 
-def _finish_graph(g, answers):
-    status, score, bound, outcome, final_age, nodes, hits = (np.asarray(x)[g.inverse] for x in answers)
+def _finish_graph(parts):
+    """``Windowed`` of a call's rows from [(Graph, level 0's answers)], one pair for each run of rows in turn: a row's answer
+    is its level-0 node's."""
+    status, score, bound, outcome, final_age, nodes, hits = (
+        np.concatenate(col) for col in zip(*([np.asarray(x)[g.inverse] for x in answers] for g, answers in parts)))
     return _finish_window(status, outcome, final_age, nodes, hits, score, bound)
 
 
@@ -1112,7 +1083,7 @@ def drive_host(rows, alpha, beta, driver_plies, node_budget=None, nodes_per_laun
     a, b = _window_arrays(alpha, beta, len(rows))
     g = _build_graph(rows, a, b, plies, _children_host)
     answers, report = drive_graph_host(g, node_budget, nodes_per_launch, leaf_solver)
-    return _finish_graph(g, answers), report
+    return _finish_graph([(g, answers)]), report
 
 
 def _check_graph(g):
@@ -1149,7 +1120,6 @@ def solve_graph(g, node_budget=None, nodes_per_launch=None, device=0, table=None
     """c4_solve_graph on a ``Graph`` (``_build_graph``): the answers of level 0, (status, score, bound, outcome code,
     final_age, nodes, table_hits), and the per-node report {lo, hi, state, nodes, table_hits} -- ``drive_graph_host``'s,
     from the device.  For tests and tools; the public calls take ``driver_plies``."""
-    import ctypes as C
     _check_graph(g)
     if table is not None:
         device = table.device
@@ -1158,18 +1128,16 @@ def solve_graph(g, node_budget=None, nodes_per_launch=None, device=0, table=None
     nodes, hits = (np.zeros(n0, dtype=np.int64) for _ in range(2))
     report = {"lo": np.zeros(n_nodes, dtype=np.int8), "hi": np.zeros(n_nodes, dtype=np.int8), "state": np.zeros(n_nodes, dtype=np.int8),
               "nodes": np.zeros(n_nodes, dtype=np.int64), "table_hits": np.zeros(n_nodes, dtype=np.int64)}
-    i8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int8)) if a is not None else None  # noqa: E731
-    i64 = lambda a: a.ctypes.data_as(L._i64p)  # noqa: E731
     c0, c1 = (np.ascontiguousarray(x, dtype=np.uint64) for x in (g.color0, g.color1))
     start = np.ascontiguousarray(g.level_start, dtype=np.int64)
     child = np.ascontiguousarray(g.child, dtype=np.int32)
     a = None if g.alpha is None else np.ascontiguousarray(g.alpha, dtype=np.int8)
     b = None if g.beta is None else np.ascontiguousarray(g.beta, dtype=np.int8)
-    _check(L.load().c4_solve_graph(int(device), table.handle if table is not None else None, c0.ctypes.data_as(L._u64p),
-                                   c1.ctypes.data_as(L._u64p), i64(start), len(start) - 1, child.ctypes.data_as(C.POINTER(C.c_int32)),
-                                   i8(a), i8(b), int(node_budget or 0), int(nodes_per_launch or 0), i8(status), i8(score), i8(bound),
-                                   i8(outcome), i8(age), i64(nodes), i64(hits), i8(report["lo"]), i8(report["hi"]), i8(report["state"]),
-                                   i64(report["nodes"]), i64(report["table_hits"])))
+    _check(L.load().c4_solve_graph(int(device), table.handle if table is not None else None, _ptr(c0), _ptr(c1), _ptr(start),
+                                   len(start) - 1, _ptr(child), _ptr(a), _ptr(b), int(node_budget or 0),
+                                   int(nodes_per_launch or 0), _ptr(status), _ptr(score), _ptr(bound), _ptr(outcome), _ptr(age), _ptr(nodes),
+                                   _ptr(hits), _ptr(report["lo"]), _ptr(report["hi"]), _ptr(report["state"]), _ptr(report["nodes"]),
+                                   _ptr(report["table_hits"])))
     report["graph"] = g
     return (status, score, bound, outcome, age, nodes, hits), report
 
@@ -1200,16 +1168,10 @@ def _drive(rows, alpha, beta, driver_plies, node_budget, nodes_per_launch, devic
     n = len(rows)
     if table is not None and not host:
         device = table.device
-
-    def children_on_device(level):
-        import torch
-        children, legal = _children_dev(_packed_on_device(torch.from_numpy(np.ascontiguousarray(level).view(np.int64)), device))
-        return children.cpu().numpy().view(np.uint64).reshape(-1, WIDTH, 2), legal.cpu().numpy() != 0
-
-    children_of = _children_host if host else children_on_device
+    children_of = _children_host if host else _children_of(device)
     parts = _split_for_graphs(n, lambda lo, hi: _build_graph(rows[lo:hi], None if alpha is None else alpha[lo:hi],
                                                              None if beta is None else beta[lo:hi], plies, children_of))
-    cols = [[] for _ in range(7)]
+    answered = []
     for lo, hi, g in sorted(parts, key=lambda p: p[0]):
         if host:
             answers, report = drive_graph_host(g, node_budget, nodes_per_launch)
@@ -1218,10 +1180,8 @@ def _drive(rows, alpha, beta, driver_plies, node_budget, nodes_per_launch, devic
         if tally is not None:
             for code, name in NODE_STATE_NAMES.items():
                 tally[name] = tally.get(name, 0) + int((report["state"] == code).sum())
-        for col, x in zip(cols, answers):
-            col.append(np.asarray(x)[g.inverse])
-    status, score, bound, outcome, final_age, nodes, hits = (np.concatenate(c) if c else np.zeros(0, dtype=np.int8) for c in cols)
-    return _finish_window(status, outcome, final_age, nodes, hits, score, bound)
+        answered.append((g, answers))
+    return _finish_graph(answered)
 
 
 # -- grid_search's triple --------------------------------------------------------------------------------------------------
@@ -1389,15 +1349,6 @@ def staged_labels(rows, window_solver, children_of=None, stage2=True):
             "stage1_hits": int(hits1.sum()),
             "stage2_rows": len(uniq), "stage2_nodes": int(nodes2.sum()), "stage2_unknown": int((status2 == L.SOLVE_UNKNOWN).sum()),
             "stage2_hits": int(hits2.sum())}
-
-
-def _rows_u64(boards):
-    """uint64 [n, 2] of a packed tensor, a uint64 / int64 [n, 2] array or a sequence of Boards or pairs."""
-    if _is_tensor(boards):
-        return boards.cpu().numpy().view(np.uint64).reshape(-1, 2)
-    if isinstance(boards, np.ndarray):
-        return np.ascontiguousarray(boards).view(np.uint64).reshape(-1, 2)
-    return np.stack(_bits(boards), axis=1) if len(boards) else np.zeros((0, 2), dtype=np.uint64)
 
 
 def _first_occurrences(rows):

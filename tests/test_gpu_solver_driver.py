@@ -30,9 +30,8 @@ def z():
 
 
 def device_children(level):
-    from connect4_amd.solver import _children_dev
-    children, legal = _children_dev(packed(level))
-    return children.cpu().numpy().view(np.uint64).reshape(-1, 7, 2), legal.cpu().numpy() != 0
+    from connect4_amd.solver import _children_of
+    return _children_of(0)(level)
 
 
 def graph_of(case):

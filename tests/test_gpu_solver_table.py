@@ -98,6 +98,33 @@ def test_split_gives_the_answers_of_no_split(fx, split_plies):
             assert is_fixture(solve(boards, split_plies=1), z)              # table-free, from Boards
 
 
+def test_split_nodes_are_the_sums_over_the_graphs_last_level(fx):
+    """Table-free node counts are deterministic: two plies below the fixture's 12 cheapest rows a row's nodes are the nodes of
+    solve(deep=True) summed over its distinct last-level nodes of the graph -- the batch and the way back are the graph's."""
+    from connect4_amd import _lib as L
+    from connect4_amd.solver import _build_graph, _children_of, solve
+    z = fx[0]
+    cost = z["nodes"] + z["child_nodes"].sum(axis=1)
+    pick = np.argsort(cost, kind="stable")[:12]
+    assert cost[pick].max() <= 4096
+    rows = np.stack([z["c0"], z["c1"]], axis=1)[pick]
+    res = solve(packed(rows), split_plies=2)
+    g = _build_graph(rows, None, None, 2, _children_of(0))
+    first_leaf = int(g.level_start[-2])
+    per_node = np.zeros(len(g.child), dtype=np.int64)
+    per_node[first_leaf:] = solve(packed(np.stack([g.color0[first_leaf:], g.color1[first_leaf:]], axis=1)), deep=True).nodes
+
+    def leaves_below(node):
+        if node >= first_leaf:
+            return {node}
+        return set().union(*[leaves_below(int(c)) for c in g.child[node] if c >= 0])
+
+    want = [int(per_node[sorted(leaves_below(int(i)))].sum()) for i in g.inverse]
+    assert min(want) > 0 and res.nodes.tolist() == want
+    assert (res.status == L.SOLVE_SOLVED).all() and (res.table_hits == 0).all()
+    assert same_bits(res.outcome, z["outcome"][pick]) and np.array_equal(res.final_age, z["final_age"][pick])
+
+
 # -- 6. grid_triple and label -------------------------------------------------------------------------------------------------
 def test_grid_triple_and_label_with_a_table(fx):
     from connect4_amd import _lib as L

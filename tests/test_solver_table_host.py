@@ -160,30 +160,30 @@ def fixture_answers(z):
     return known
 
 
-def fold(levels, links, childless, answer_of):
-    """_fold_split with the last level answered by `answer_of(c0, c1)` and the childless rows above it by solve_host."""
-    from connect4_amd.solver import _fold_split, solve_host
-    leaf = [np.array(col) for col in zip(*[answer_of(int(a), int(b)) + (0,) for a, b in levels[-1]])]
-    own = []
-    for lv, cl in zip(levels, childless):
-        cols = [np.full(len(lv), -1, dtype=np.int64) for _ in range(3)]
-        for i in np.nonzero(cl)[0]:
-            h = solve_host((int(lv[i, 0]), int(lv[i, 1])), deep=True)
-            cols[0][i], cols[1][i], cols[2][i] = h.status, -1 if h.outcome is None else int(h.outcome * 2), h.final_age
-        own.append(cols)
-    return _fold_split(levels, links, leaf, own)
+def fold(g, answer_of):
+    """_graph_fold_exact with the last level answered by `answer_of(c0, c1)` and the childless nodes above it by solve_host."""
+    from connect4_amd.solver import _graph_fold_exact, solve_host
+    first_leaf = int(g.level_start[-2])
+    cols = [np.full(len(g.child), -1, dtype=np.int64) for _ in range(5)]
+    for i in range(first_leaf, len(g.child)):
+        cols[0][i], cols[1][i], cols[2][i], cols[3][i], cols[4][i] = answer_of(int(g.color0[i]), int(g.color1[i])) + (0,)
+    for i in np.nonzero(~(g.child[:first_leaf] >= 0).any(axis=1))[0]:
+        h = solve_host((int(g.color0[i]), int(g.color1[i])), deep=True)
+        cols[0][i], cols[1][i], cols[2][i] = h.status, -1 if h.outcome is None else int(h.outcome * 2), h.final_age
+    return _graph_fold_exact(g, *cols)
 
 
 def test_split_one_ply_folds_the_fixture_children(open_set):
     from connect4_amd import _lib as L
-    from connect4_amd.solver import _children_host, _mirror_bits, _split_levels, value_from_answer
+    from connect4_amd.solver import _build_graph, _children_host, _mirror_bits, value_from_answer
     z = open_set
     known = fixture_answers(z)
     roots = np.stack([z["c0"], z["c1"]], axis=1)
     both = np.concatenate([roots, roots[:5]])                     # duplicates fold like their originals
-    levels, links, childless, inverse = _split_levels(both, 1, _children_host)
-    assert len(levels[0]) == len(roots) and len(levels[1]) <= int((z["child_legal"] != 0).sum()) and not childless[0].any()
-    status, outcome, age, nodes, hits = fold(levels, links, childless, lambda a, b: known[(a, b)])
+    g = _build_graph(both, None, None, 1, _children_host)
+    sizes, inverse = np.diff(g.level_start), g.inverse
+    assert sizes[0] == len(roots) and sizes[1] <= int((z["child_legal"] != 0).sum()) and (g.child[:sizes[0]] >= 0).any(axis=1).all()
+    status, outcome, age, nodes, hits = fold(g, lambda a, b: known[(a, b)])
     status, outcome, age, nodes = status[inverse], outcome[inverse], age[inverse], nodes[inverse]
     want = np.concatenate([np.arange(len(roots)), np.arange(5)])
     assert (status == L.SOLVE_SOLVED).all() and np.array_equal(age, z["final_age"][want])
@@ -197,9 +197,10 @@ def test_split_one_ply_folds_the_fixture_children(open_set):
                 kids[min((int(a), int(b)), (int(m[0]), int(m[1])))] = int(n)
         assert nodes[i] == sum(kids.values())
     # a child without an answer leaves its parents UNKNOWN and nobody else
-    victim = tuple(int(x) for x in levels[1][0])
-    status2 = fold(levels, links, childless, lambda a, b: (L.SOLVE_UNKNOWN, -1, -1, 64) if (a, b) == victim else known[(a, b)])[0]
-    parents = (links[0] == 0).any(axis=1)
+    leaf0 = int(g.level_start[1])
+    victim = (int(g.color0[leaf0]), int(g.color1[leaf0]))
+    status2 = fold(g, lambda a, b: (L.SOLVE_UNKNOWN, -1, -1, 64) if (a, b) == victim else known[(a, b)])[0]
+    parents = (g.child[:leaf0] == leaf0).any(axis=1)
     assert parents.any() and (status2[parents] == L.SOLVE_UNKNOWN).all() and (status2[~parents] == L.SOLVE_SOLVED).all()
 
 
@@ -207,14 +208,14 @@ def test_split_two_plies_on_the_host(open_set):
     """Two plies below the fixture's cheapest rows, the grandchildren answered by solve_host: finished descendants (a child
     that ends the game) answer for themselves, and the fold gives the fixture's answers."""
     from connect4_amd import _lib as L
-    from connect4_amd.solver import _children_host, _split_levels, solve_host
+    from connect4_amd.solver import _build_graph, _children_host, solve_host
     z = open_set
     cost = z["nodes"] + z["child_nodes"].sum(axis=1)
     pick = np.argsort(cost, kind="stable")[:12]
     assert cost[pick].max() <= 4096
     roots = np.stack([z["c0"], z["c1"]], axis=1)[pick]
-    levels, links, childless, inverse = _split_levels(roots, 2, _children_host)
-    assert childless[1].any()                                     # some child has already won the game
+    g = _build_graph(roots, None, None, 2, _children_host)
+    assert not (g.child[g.level_start[1]:g.level_start[2]] >= 0).any(axis=1).all()     # some child has already won the game
 
     shared = {}
 
@@ -222,5 +223,22 @@ def test_split_two_plies_on_the_host(open_set):
         h = solve_host((a, b), table=shared)
         return (h.status, int(h.outcome * 2), h.final_age, h.nodes)
 
-    status, outcome, age, _, _ = (a[inverse] for a in fold(levels, links, childless, answer))
+    status, outcome, age, _, _ = (a[g.inverse] for a in fold(g, answer))
     assert (status == L.SOLVE_SOLVED).all() and np.array_equal(age, z["final_age"][pick]) and same_bits(outcome * 0.5, z["outcome"][pick])
+
+
+def test_split_fold_is_the_pinned_fold():
+    """_graph_fold_exact on drawn answers (tests/golden/solver_split_fold.npz, written by the fold over per-level arrays that
+    it replaced: tests/golden/gen_solver_split_fold_golden.py) -- the five arrays bit for bit, rows that share a node,
+    UNKNOWN leaves, levels that thin out to nothing."""
+    from connect4_amd.solver import _build_graph, _children_host, _graph_fold_exact
+    z = load_npz("solver_split_fold.npz")
+    fields = ("status", "outcome", "final_age", "nodes", "hits")
+    assert len(z["names"]) == 6
+    for name in z["names"]:
+        g = _build_graph(z[name + "__rows"], None, None, int(z[name + "__k"]), _children_host)
+        answers = [z["%s__node_%s" % (name, f)] for f in fields]
+        assert all(len(a) == len(g.child) for a in answers), name
+        for f, got in zip(fields, _graph_fold_exact(g, *answers)):
+            want = z["%s__%s" % (name, f)]
+            assert got.dtype == want.dtype and np.array_equal(got[g.inverse], want), (name, f)
