@@ -220,6 +220,10 @@ SIGNATURES = {
     "c4_solve_table_destroy": (C.c_int, [C.c_void_p]),
     "c4_solve_table_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
     "c4_solve_table_read": (C.c_int, [C.c_void_p, _u64p, C.c_int64]),
+    "c4_solve_book_create": (C.c_int, [C.c_int, _u64p, C.c_int64, C.c_int, _P(C.c_void_p)]),
+    "c4_solve_book_destroy": (C.c_int, [C.c_void_p]),
+    "c4_solve_table_attach_book": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "c4_solve_table_create_entryless": (C.c_int, [C.c_int, _P(C.c_void_p)]),
     "c4_solve_deep_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 5),
     "c4_solve_deep": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, C.c_int64, C.c_int64, C.c_int64, _P(C.c_int8), _P(C.c_int8),
                                 _P(C.c_int8), _i64p, _i64p]),

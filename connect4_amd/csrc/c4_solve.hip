@@ -58,6 +58,24 @@
 //   * Answers are exact and do not depend on the table (alpha-beta returns the same root value for every sound set of
 //     bounds).  NODE COUNTS WITH A TABLE ARE NOT DETERMINISTIC: they depend on what other lanes stored first.
 //
+// The book (c4_solve_book_*, carried by the TableRef).
+//   * A read-only set of table-format words, all of positions with one stone count: solved once, kept in a file, and
+//     probed where the search reaches that ply -- in run_lane after enter_node says interior and in k_solve_init for the
+//     root, exactly where the table is probed, but whatever TT_MIN_EMPTIES says and whether or not there is a table
+//     (e == nullptr).  NoTable compiles none of it.
+//   * One entry serves a position and its mirror image: the key stored and looked up is the smaller of the key and the
+//     key with its seven column fields reversed (tt_mirror_key).
+//   * The device image is open-addressed with linear probing, a power-of-two capacity of at least twice the entries;
+//     the host lays it out and records the longest probe sequence, and book_probe's loop runs at most that many steps:
+//     plain loads, no atomics, no writes, no LDS.  The termination argument above holds word for word: every loop is
+//     bounded, no lane waits for another.
+//   * The book is probed first and feeds the same Probe into the same code.  An entry that closes the node returns and
+//     the table is not probed; one that narrows the window hands the narrowed window to the table probe.  A node the book
+//     closes stores nothing; a node it narrowed closes against the alpha its moves were entered with, like any node.
+//   * A book hit (returned or narrowed) counts into the row's table_hits like a table hit.
+//   * Every entry is a true bound of its position's value, so answers do not depend on the book; node counts do, and
+//     table-free they stay deterministic: solver._Search with a HostBook enters the same nodes.
+//
 // The root window.  Fail-hard alpha-beta from the caller's window, the search every node below a root already is.  A
 // row answers with the score its root returns and that score's kind against the caller's window (C4_SOLVE_BOUND_*):
 // exact inside it, else a lower bound at or above beta or an upper bound at or below alpha.  The root's table probe and
@@ -213,6 +231,12 @@ struct TableRef {       // k_solve_search<DEEP_MAX_PLY, TableRef>: e == nullptr 
     static constexpr bool compiled = true;
     uint64_t *e;
     int shift;          // 64 - log2(entries)
+    // the book (c4_solve_book): a read-only open-addressed image of table-format words, all of positions with book_age
+    // stones; book == nullptr: none.  Kernel arguments, so uniform.
+    const uint64_t *book;
+    uint32_t book_mask; // capacity - 1, the capacity a power of two
+    int book_age;
+    int book_steps;     // the longest probe sequence of any entry: what bounds book_probe's loop
 };
 
 // The parked word: the top frame of a lane that has stopped at its quota, Work::misc[row].  alpha | beta << 8 | third << 16
@@ -258,9 +282,9 @@ struct Probe {
     int hit, alpha, beta, value;
 };
 
-__device__ __forceinline__ Probe tt_probe(const TableRef t, uint64_t key, int alpha, int beta)
+// what the entry word `w` says about the position `key` under the window (alpha, beta)
+C4_HD Probe probe_word(uint64_t w, uint64_t key, int alpha, int beta)
 {
-    const uint64_t w = __hip_atomic_load(t.e + tt_slot(t, key), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const bool match = (w & TT_KEY_MASK) == key;
     const int s = (int)((w >> 49) & 0x7f) - 64, kind = (int)((w >> 56) & 3);
     const bool closes = kind == TT_EXACT || (kind == TT_LOWER && s >= beta) || (kind == TT_UPPER && s <= alpha);
@@ -271,6 +295,39 @@ __device__ __forceinline__ Probe tt_probe(const TableRef t, uint64_t key, int al
     p.beta = p.hit == 1 && down ? s : beta;
     p.value = s;
     return p;
+}
+
+__device__ __forceinline__ Probe tt_probe(const TableRef t, uint64_t key, int alpha, int beta)
+{
+    return probe_word(__hip_atomic_load(t.e + tt_slot(t, key), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), key, alpha, beta);
+}
+
+// The book.  No 7-bit column field of a key carries into the next (a column of height h holds 2^h + the mover's stones in
+// it, at most 127), so the key of the mirror image is the key with its seven fields reversed, and the book stores, and a
+// probe looks up, the smaller of the two: no board is mirrored.
+C4_HD uint64_t tt_mirror_key(uint64_t k)
+{
+    constexpr uint64_t F = (1ULL << H1) - 1;
+    return ((k & F) << (6 * H1)) | ((k >> (6 * H1)) & F) | ((k & (F << H1)) << (4 * H1)) | ((k >> (4 * H1)) & (F << H1)) |
+           ((k & (F << (2 * H1))) << (2 * H1)) | ((k >> (2 * H1)) & (F << (2 * H1))) | (k & (F << (3 * H1)));
+}
+C4_HD uint64_t book_key(uint64_t key) { const uint64_t m = tt_mirror_key(key); return m < key ? m : key; }
+C4_HD uint32_t book_home(uint64_t key) { return (uint32_t)((key * 0x9E3779B97F4A7C15ULL) >> 32); }
+C4_HD bool book_covers(const TableRef t, int age) { return t.book != nullptr && age == t.book_age; }
+
+// Linear probing from the key's home slot, plain loads: the loop ends at the key, at an empty word or after book_steps
+// slots -- the host laid no entry further from its home -- so it is bounded by a kernel argument.
+__device__ __forceinline__ Probe book_probe(const TableRef t, uint64_t key, int alpha, int beta)
+{
+    const uint64_t k = book_key(key);
+    const uint32_t home = book_home(k);
+    uint64_t w = 0;
+    for (int i = 0; i < t.book_steps; ++i) {
+        const uint64_t x = t.book[(home + (uint32_t)i) & t.book_mask];
+        if ((x & TT_KEY_MASK) == k) w = x;
+        if ((x & TT_KEY_MASK) == k || x == 0) break;
+    }
+    return probe_word(w, k, alpha, beta);
 }
 
 __device__ __forceinline__ void tt_store(const TableRef t, uint64_t key, int score, int kind)
@@ -403,8 +460,18 @@ C4_HD int64_t run_lane(Lane &L, S &stk, const T tt, int64_t quota)
                     L.beta = b;
                     L.moves = moves;
                     if constexpr (T::compiled) {
-                        if (tt_covers(tt, age)) {
-                            const Probe p = tt_probe(tt, tt_key(mine, occ), a, b);
+                        if (book_covers(tt, age)) {             // the book first: whatever TT_MIN_EMPTIES and tt.e are
+                            const Probe p = book_probe(tt, tt_key(mine, occ), a, b);
+                            L.hits += p.hit ? 1 : 0;
+                            L.alpha = p.alpha;
+                            L.beta = p.beta;
+                            if (p.hit == 2) {
+                                L.ret = p.value;
+                                L.pending = true;
+                            }
+                        }
+                        if (!L.pending && tt_covers(tt, age)) {  // the table sees the window the book left
+                            const Probe p = tt_probe(tt, tt_key(mine, occ), L.alpha, L.beta);
                             L.hits += p.hit ? 1 : 0;
                             L.alpha = p.alpha;
                             L.beta = p.beta;
@@ -530,12 +597,22 @@ __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict_
         if (deep && !L.done) {
             const uint64_t occ = c0 | c1;
             const int age = popc64(occ);
-            if (tt_covers(tt, age)) {
-                const Probe p = tt_probe(tt, tt_key((age & 1) ? c1 : c0, occ), L.alpha, L.beta);
-                hit = p.hit;
+            if (book_covers(tt, age)) {
+                const Probe p = book_probe(tt, tt_key((age & 1) ? c1 : c0, occ), L.alpha, L.beta);
+                hit = p.hit ? 1 : 0;
                 L.alpha = p.alpha;
                 L.beta = p.beta;
-                if (hit == 2) {
+                if (p.hit == 2) {
+                    L.ret = p.value;
+                    L.done = true;
+                }
+            }
+            if (!L.done && tt_covers(tt, age)) {
+                const Probe p = tt_probe(tt, tt_key((age & 1) ? c1 : c0, occ), L.alpha, L.beta);
+                hit += p.hit ? 1 : 0;
+                L.alpha = p.alpha;
+                L.beta = p.beta;
+                if (p.hit == 2) {
                     L.ret = p.value;
                     L.done = true;
                 }
@@ -558,7 +635,7 @@ __global__ void __launch_bounds__(BLOCK) k_solve_init(const int64_t *__restrict_
     final_age[row] = (int8_t)fa;
     nodes[row] = nd;
     unfinished[row] = more;
-    if (hits) hits[row] = hit ? 1 : 0;
+    if (hits) hits[row] = hit;
 }
 
 // One lane per unfinished row, through the dense list `active`: unpark, search up to the quota, answer or park again.
@@ -1003,10 +1080,20 @@ int check_windows(const int8_t *alpha, const int8_t *beta, int64_t n)
 
 }  // namespace
 
+struct c4_solve_book {
+    int device;
+    int age;
+    int64_t n;              // entries
+    uint64_t *image;        // device: `mask + 1` words, open-addressed by book_home, linear probing, 0 = empty
+    uint32_t mask;
+    int steps;              // the longest probe sequence of any entry (0 for an empty book)
+};
+
 struct c4_solve_table {
     int device;
-    int log2_entries;
+    int log2_entries;       // 0 with entries == nullptr: c4_solve_table_create_entryless
     uint64_t *entries;
+    const c4_solve_book *book;      // c4_solve_table_attach_book, or nullptr
 };
 
 namespace {
@@ -1014,9 +1101,10 @@ namespace {
 // the table's reference for a call on `device`: C4_EINVAL for a table of another device
 int table_ref(const c4_solve_table *table, int device, TableRef &tt)
 {
-    tt = TableRef{nullptr, 0};
+    tt = TableRef{nullptr, 0, nullptr, 0, 0, 0};
     if (!table) return C4_OK;
-    if (!table->entries || table->log2_entries < TT_MIN_LOG2 || table->log2_entries > TT_MAX_LOG2) {
+    const bool entryless = !table->entries && table->log2_entries == 0;
+    if (!entryless && (!table->entries || table->log2_entries < TT_MIN_LOG2 || table->log2_entries > TT_MAX_LOG2)) {
         set_solve_err("not a table of c4_solve_table_create");
         return C4_EINVAL;
     }
@@ -1024,7 +1112,16 @@ int table_ref(const c4_solve_table *table, int device, TableRef &tt)
         set_solve_err("the table lives on device %d, the call is for device %d", table->device, device);
         return C4_EINVAL;
     }
-    tt = TableRef{table->entries, 64 - table->log2_entries};
+    if (!entryless) {
+        tt.e = table->entries;
+        tt.shift = 64 - table->log2_entries;
+    }
+    if (const c4_solve_book *b = table->book) {
+        tt.book = b->image;
+        tt.book_mask = b->mask;
+        tt.book_age = b->age;
+        tt.book_steps = b->steps;
+    }
     return C4_OK;
 }
 
@@ -1182,6 +1279,96 @@ int c4_solve_table_read(c4_solve_table *table, uint64_t *entries_host, int64_t n
     if (rc) return rc;
     SOLVE_CHECK(hipDeviceSynchronize());
     SOLVE_CHECK(hipMemcpy(entries_host, table->entries, (size_t)entries * 8, hipMemcpyDeviceToHost));
+    return C4_OK;
+}
+
+int c4_solve_table_create_entryless(int device, c4_solve_table **out)
+{
+    if (!out) { set_solve_err("null argument"); return C4_EINVAL; }
+    *out = nullptr;
+    int rc = pick_device(device);
+    if (rc) return rc;
+    *out = new c4_solve_table{device, 0, nullptr, nullptr};
+    return C4_OK;
+}
+
+int c4_solve_table_attach_book(c4_solve_table *table, const c4_solve_book *book)
+{
+    if (!table) { set_solve_err("null argument"); return C4_EINVAL; }
+    if (book && book->device != table->device) {
+        set_solve_err("the book lives on device %d, the table on device %d", book->device, table->device);
+        return C4_EINVAL;
+    }
+    table->book = book;
+    return C4_OK;
+}
+
+// The image is laid out on the host, entry by entry in the order given: home slot, then the next free one.  Checked here,
+// whatever built the words: no bits above the kind, a kind of 1..3, a score within +-42, a canonical key whose seven
+// column fields are each 2^h + stones (h <= 6) with the heights adding up to `age`, and no key twice.  Not checked: that
+// the two sides' stone counts fit the mover, and -- it cannot be -- that the score is a true bound of the position.
+int c4_solve_book_create(int device, const uint64_t *words, int64_t n, int age, c4_solve_book **out)
+{
+    if (!out) { set_solve_err("null argument"); return C4_EINVAL; }
+    *out = nullptr;
+    if (n < 0 || (n > 0 && !words)) { set_solve_err(n < 0 ? "n < 0" : "null argument"); return C4_EINVAL; }
+    if (age < 0 || age > CELLS - 1) { set_solve_err("age %d outside 0..%d", age, CELLS - 1); return C4_EINVAL; }
+    if (n > (int64_t)1 << 28) { set_solve_err("%lld entries: a book takes 2^28", (long long)n); return C4_EINVAL; }
+    uint64_t cap = 16;
+    while (cap < 2 * (uint64_t)n) cap <<= 1;
+    const uint32_t mask = (uint32_t)(cap - 1);
+    std::vector<uint64_t> image((size_t)cap, 0);
+    int steps = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint64_t w = words[i], key = w & TT_KEY_MASK;
+        const int kind = (int)((w >> 56) & 3), score = (int)((w >> 49) & 0x7f) - 64;
+        if (key == 0 || (w >> 58) != 0 || kind == 0 || score < -SCORE_MAX || score > SCORE_MAX || book_key(key) != key) {
+            set_solve_err("entry %lld (%#llx) is not a canonical table entry", (long long)i, (unsigned long long)w);
+            return C4_EINVAL;
+        }
+        int stones = 0;
+        bool fields_ok = true;
+        for (int c = 0; c < WIDTH; ++c) {
+            const unsigned f = (unsigned)((key >> (H1 * c)) & 0x7f);
+            if (f == 0) { fields_ok = false; break; }
+            stones += 31 - __builtin_clz(f);       // the column's height: floor(log2 f) <= 6
+        }
+        if (!fields_ok || stones != age) {
+            set_solve_err("entry %lld: the key %#llx is not a position with %d stones", (long long)i, (unsigned long long)key, age);
+            return C4_EINVAL;
+        }
+        const uint32_t home = book_home(key);
+        int d = 0;
+        for (;; ++d) {       // ends: the image is at most half full
+            uint64_t &x = image[(size_t)((home + (uint32_t)d) & mask)];
+            if (x == 0) { x = w; break; }
+            if ((x & TT_KEY_MASK) == key) { set_solve_err("entry %lld: the key %#llx occurs twice", (long long)i, (unsigned long long)key); return C4_EINVAL; }
+        }
+        steps = d + 1 > steps ? d + 1 : steps;
+    }
+    int rc = pick_device(device);
+    if (rc) return rc;
+    void *p = nullptr;
+    if (hipMalloc(&p, (size_t)cap * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        set_solve_err("no device memory for a book of %lld entries", (long long)n);
+        return C4_ENOMEM;
+    }
+    hipError_t r = hipMemcpy(p, image.data(), (size_t)cap * 8, hipMemcpyHostToDevice);
+    if (r != hipSuccess) {
+        (void)hipFree(p);
+        set_solve_err("copying the book failed: %s", hipGetErrorString(r));
+        return C4_EDEVICE;
+    }
+    *out = new c4_solve_book{device, age, n, (uint64_t *)p, mask, steps};
+    return C4_OK;
+}
+
+int c4_solve_book_destroy(c4_solve_book *book)
+{
+    if (!book) return C4_OK;
+    if (pick_device(book->device) == C4_OK && book->image) (void)hipFree(book->image);
+    delete book;
     return C4_OK;
 }
 

@@ -25,7 +25,9 @@ The integer score: a game o wins at age ``a`` scores ``43 - a``, one x wins ``a 
 move inside the search.  It is strictly monotone in the reference's float, so max / min over it pick what the reference's
 max / min pick; the float itself is formed once, from outcome and age, by the division the reference performs.
 """
+import contextlib
 import ctypes as C
+import functools
 import time
 from collections import namedtuple
 from typing import Sequence
@@ -37,7 +39,7 @@ from .board import BOTTOM, H1, HEIGHT, SIZE, WIDTH, Board, _wins
 from .grid_search import GridTree, _terminal_value
 from .utils import Side
 
-__all__ = ["MAX_EMPTIES", "DEEP_MAX_EMPTIES", "DEFAULT_NODE_BUDGET", "STATUS_NAMES", "Solved", "HostAnswer", "Table", "HostTable",
+__all__ = ["Book", "HostBook", "enumerate_ply", "MAX_EMPTIES", "DEEP_MAX_EMPTIES", "DEFAULT_NODE_BUDGET", "STATUS_NAMES", "Solved", "HostAnswer", "Table", "HostTable",
            "EntryFields", "entry_fields", "solve", "solve_host", "HostWindowAnswer", "Windowed", "BOUND_NAMES", "solve_window", "outcomes",
            "label_values", "staged_labels", "drive_host", "drive_graph_host", "solve_graph", "Graph", "NODE_STATE_NAMES", "grid_triple", "label", "prior_from_children", "value_from_answer", "random_playout", "random_openings"]
 
@@ -48,8 +50,21 @@ STATUS_NAMES = {L.SOLVE_SOLVED: "solved", L.SOLVE_TERMINAL: "terminal", L.SOLVE_
                 L.SOLVE_TOO_DEEP: "too_deep", L.SOLVE_INVALID: "invalid"}
 
 Solved = namedtuple("Solved", "status outcome final_age value nodes table_hits")
-HostAnswer = namedtuple("HostAnswer", "status outcome final_age value nodes")
-HostWindowAnswer = namedtuple("HostWindowAnswer", "status score bound outcome final_age value nodes")
+class HostAnswer(namedtuple("HostAnswer", "status outcome final_age value nodes")):
+    """``solve_host``'s answer.  Beside the tuple's fields -- they alone take part in comparisons -- it carries hits, what the
+    kernel counts into table_hits (table and book probes that returned or narrowed), and book_probes, the nodes at which
+    the book was looked up.  The two are plain attributes set on the answer ``solve_host`` returns: they are in neither the
+    repr nor a comparison, and a copy made by a tuple operation (``_replace``, slicing, pickling) has the class defaults, 0."""
+    hits = 0
+    book_probes = 0
+
+
+class HostWindowAnswer(namedtuple("HostWindowAnswer", "status score bound outcome final_age value nodes")):
+    """``solve_host(window=)``'s answer; hits and book_probes as ``HostAnswer`` has them."""
+    hits = 0
+    book_probes = 0
+
+
 Windowed = namedtuple("Windowed", "status score bound outcome final_age nodes table_hits")
 BOUND_NAMES = {L.SOLVE_BOUND_NONE: "none", L.SOLVE_BOUND_LOWER: "lower", L.SOLVE_BOUND_UPPER: "upper", L.SOLVE_BOUND_EXACT: "exact"}
 SCORE_MAX = 42      # beyond every score: (-SCORE_MAX, SCORE_MAX) is the full window
@@ -196,16 +211,46 @@ def entry_fields(words):
     return EntryFields(index, key, score, kind, mine, occ, np.where(odd, theirs, mine), np.where(odd, mine, theirs), age)
 
 
+def _mirror_key(key):
+    """The key of the mirror image: no 7-bit column field of ``mine + occ + BOTTOM`` carries into the next, so it is the
+    key with its seven fields reversed (c4_solve.hip tt_mirror_key).  An int or a uint64 array."""
+    if isinstance(key, np.ndarray):
+        out = np.zeros_like(key)
+        for c in range(WIDTH):
+            out |= ((key >> np.uint64(H1 * c)) & np.uint64((1 << H1) - 1)) << np.uint64(H1 * (WIDTH - 1 - c))
+        return out
+    return sum(((key >> (H1 * c)) & ((1 << H1) - 1)) << (H1 * (WIDTH - 1 - c)) for c in range(WIDTH))
+
+
+def _probe_entry(hit, alpha, beta):
+    """c4_solve.hip probe_word on a ``(kind, score)`` entry: (0 nothing / 1 narrowed / 2 closes, alpha, beta, score)."""
+    kind, s = hit
+    if kind == _EXACT or (kind == _LOWER and s >= beta) or (kind == _UPPER and s <= alpha):
+        return 2, alpha, beta, s
+    if kind == _LOWER and s > alpha:
+        return 1, s, beta, s
+    if kind == _UPPER and s < beta:
+        return 1, alpha, s, s
+    return 0, alpha, beta, s
+
+
 class _Search:
     """`table`: None, a dict ``key -> (kind, score)`` -- the kernel's transposition table without its replacement -- or a
-    ``HostTable``, the kernel's table with it."""
+    ``HostTable``, the kernel's table with it.  `book`: None or a ``Book``, probed before the table at nodes of its age."""
 
-    def __init__(self, budget, table=None):
+    def __init__(self, budget, table=None, book=None):
         self.nodes = 0
         self.budget = budget
         self.table = table
+        self.book = book
         self.hits = 0
+        self.book_probes = 0
+        self.hit_at = []        # the node count at every hit: the hits of a search stopped after c nodes are those <= c
         self.clean = True
+
+    def _hit(self):
+        self.hits += 1
+        self.hit_at.append(self.nodes)
 
     def enter(self):
         if self.nodes >= self.budget:
@@ -239,22 +284,28 @@ class _Search:
             alpha = lo
             if alpha >= beta:
                 return alpha
+        if self.book is not None and age == self.book.age:
+            # the book first (c4_solve.hip book_probe), whatever _TT_MIN_EMPTIES and the table are: an entry that closes
+            # the node returns, one that narrows hands the narrowed window on
+            self.book_probes += 1
+            hit = self.book.get(mine + occ + BOTTOM)
+            if hit is not None:
+                how, alpha, beta, s = _probe_entry(hit, alpha, beta)
+                if how:
+                    self._hit()
+                if how == 2:
+                    return s
         if self.table is not None and SIZE - age >= _TT_MIN_EMPTIES:
             # probe (c4_solve.hip tt_probe): the key is the position, the score its mover's, so an entry is a true bound
             # wherever and whenever it was written
             key = mine + occ + BOTTOM
             hit = self.table.get(key)
             if hit is not None:
-                kind, s = hit
-                if kind == _EXACT or (kind == _LOWER and s >= beta) or (kind == _UPPER and s <= alpha):
-                    self.hits += 1
+                how, alpha, beta, s = _probe_entry(hit, alpha, beta)
+                if how:
+                    self._hit()
+                if how == 2:
                     return s
-                if kind == _LOWER and s > alpha:
-                    alpha = s
-                    self.hits += 1
-                elif kind == _UPPER and s < beta:
-                    beta = s
-                    self.hits += 1
             ret = self._moves(mine, theirs, occ, possible, age, alpha, beta)
             # store (tt_store): against the window the moves were searched with
             self.table[key] = (_UPPER if ret <= alpha else _LOWER if ret >= beta else _EXACT, ret)
@@ -301,7 +352,7 @@ def _bound_kind(score, alpha, beta):
     return L.SOLVE_BOUND_LOWER if score >= beta else L.SOLVE_BOUND_UPPER if score <= alpha else L.SOLVE_BOUND_EXACT
 
 
-def solve_host(board, node_budget=None, table=None, deep=False, window=None):
+def solve_host(board, node_budget=None, table=None, deep=False, window=None, book=None):
     """The kernel's answer for one position, computed in plain Python: ``HostAnswer(status, outcome, final_age, value,
     nodes)``.  `board`: a Board or a ``(color0, color1)`` pair.  outcome / value are None where the status has none.
 
@@ -314,7 +365,10 @@ def solve_host(board, node_budget=None, table=None, deep=False, window=None):
     root is entered with that window instead of (-42, 42), and the answer is a ``HostWindowAnswer`` that also has the score
     the root returns and its kind against the window (_lib.SOLVE_BOUND_*): exact inside it, a lower bound at or above beta,
     an upper bound at or below alpha.  outcome, final_age and value are None / -1 unless the bound is exact; rows that are
-    not searched have score 0 and bound SOLVE_BOUND_NONE."""
+    not searched have score 0 and bound SOLVE_BOUND_NONE.
+
+    book: a ``Book`` (implies deep), probed like the kernel probes it: before the table, at every node of the book's age,
+    the root included.  Table-free the node count is the kernel's, and the answer's ``hits`` are its table_hits."""
     c0, c1 = (board.color if isinstance(board, Board) else board)
     c0, c1 = int(c0), int(c1)
     budget = DEFAULT_NODE_BUDGET if node_budget is None else int(node_budget)
@@ -322,12 +376,15 @@ def solve_host(board, node_budget=None, table=None, deep=False, window=None):
         w_alpha, w_beta = _check_window(*window)
     else:
         w_alpha, w_beta = -SCORE_MAX, SCORE_MAX
-    st = _classify(c0, c1, DEEP_MAX_EMPTIES if deep or table is not None or window is not None else MAX_EMPTIES)
+    st = _classify(c0, c1, DEEP_MAX_EMPTIES if deep or table is not None or window is not None or book is not None else MAX_EMPTIES)
+    s = None
 
     def answer(status, outcome, final_age, value, nodes, score=0, bound=L.SOLVE_BOUND_NONE):
-        if window is None:
-            return HostAnswer(status, outcome, final_age, value, nodes)
-        return HostWindowAnswer(status, score, bound, outcome, final_age, value, nodes)
+        ans = HostAnswer(status, outcome, final_age, value, nodes) if window is None else \
+            HostWindowAnswer(status, score, bound, outcome, final_age, value, nodes)
+        if s is not None:
+            ans.hits, ans.book_probes = s.hits, s.book_probes
+        return ans
 
     if st == L.SOLVE_TERMINAL:
         outcome = 1.0 if _wins(c0) else 0.0 if _wins(c1) else 0.5
@@ -338,7 +395,7 @@ def solve_host(board, node_budget=None, table=None, deep=False, window=None):
     occ = c0 | c1
     age = bin(occ).count("1")
     mine, theirs = (c1, c0) if age & 1 else (c0, c1)
-    s = _Search(budget, table)
+    s = _Search(budget, table, book)
     if _winning_squares(mine, occ) & (occ + BOTTOM):
         score, nodes = 42 - age, 1
     else:
@@ -422,14 +479,29 @@ class Table:
     def __init__(self, log2_entries=24, device=0):
         self._h = None
         h = C.c_void_p()
-        _check(L.load().c4_solve_table_create(int(device), int(log2_entries), C.byref(h)))
+        if log2_entries is None:        # Table.entryless
+            _check(L.load().c4_solve_table_create_entryless(int(device), C.byref(h)))
+        else:
+            _check(L.load().c4_solve_table_create(int(device), int(log2_entries), C.byref(h)))
         self._h = h
-        self.log2_entries = int(log2_entries)
+        self.log2_entries = None if log2_entries is None else int(log2_entries)
         self.device = int(device)
+        self.book = None        # attach_book
+
+    @classmethod
+    def entryless(cls, device=0):
+        """A handle without entries (c4_solve_table_create_entryless): the table-free search, there to carry a book."""
+        return cls(None, device)
+
+    def attach_book(self, book):
+        """Every later call given this table probes `book` (a ``Book``, or None: no book) at the book's ply.  The book must
+        stay open for as long as it is attached; ``book=`` of the solving calls attaches and detaches for one call."""
+        _check(L.load().c4_solve_table_attach_book(self.handle, None if book is None else book.handle(self.device)))
+        self.book = book        # keeps the device image alive
 
     @property
     def entries(self):
-        return 1 << self.log2_entries
+        return 0 if self.log2_entries is None else 1 << self.log2_entries
 
     @property
     def handle(self):
@@ -634,6 +706,284 @@ def _children_of(device):
     return children_of
 
 
+# -- a whole ply, and the book that keeps it solved -----------------------------------------------------------------------
+def _winning_squares_np(p, occ):
+    """``_winning_squares`` on uint64 arrays."""
+    u = np.uint64
+    r = (p << u(1)) & (p << u(2)) & (p << u(3))
+    for s in (H1, HEIGHT, H1 + 1):
+        q = (p << u(s)) & (p << u(2 * s))
+        r |= q & (p << u(3 * s))
+        r |= q & (p >> u(s))
+        q = (p >> u(s)) & (p >> u(2 * s))
+        r |= q & (p << u(s))
+        r |= q & (p >> u(3 * s))
+    return r & (u(_BOARD) ^ occ)
+
+
+def _next_ply_host(rows):
+    """The undecided children of undecided uint64 [m, 2] rows of one age: ``_children_host``'s, vectorised, without the
+    positions the move just won and without the full board."""
+    occ = rows[:, 0] | rows[:, 1]
+    age = int(_popcount64(occ[:1])[0])
+    if age + 1 >= SIZE:
+        return np.zeros((0, 2), dtype=np.uint64)
+    side = age & 1
+    out = []
+    for c in range(WIDTH):
+        bit = (occ + np.uint64(BOTTOM)) & np.uint64(_COL << (H1 * c))
+        ch = rows[bit != 0].copy()
+        ch[:, side] |= bit[bit != 0]
+        out.append(ch[~_wins_bits(ch[:, side])])
+    return np.concatenate(out)
+
+
+def _next_ply_dev(packed):
+    """``_next_ply_host`` on the device: c4_solve_children_dev lists the children, torch drops the won ones, mirrors and
+    takes the unique rows.  int64 [m, 2] cuda tensor in and out."""
+    import torch
+    children, legal = _children_dev(packed)
+    ch = children[legal != 0]
+    if ch.shape[0] == 0:
+        return ch.reshape(0, 2)
+    occ = ch[:, 0] | ch[:, 1]
+    age = int(_popcount64(np.array([int(occ[0].item())], dtype=np.uint64))[0])
+    if age >= SIZE:
+        return ch[:0]
+    moved = ch[:, (age - 1) & 1]
+    won = torch.zeros_like(moved, dtype=torch.bool)
+    for s in (1, HEIGHT, H1, H1 + 1):
+        y = moved & (moved >> s)
+        won |= (y & (y >> (2 * s))) != 0
+    ch = ch[~won]
+    m = torch.zeros_like(ch)
+    for c in range(WIDTH):
+        m |= ((ch >> (H1 * c)) & ((1 << H1) - 1)) << (H1 * (WIDTH - 1 - c))
+    swap = (m[:, 0] < ch[:, 0]) | ((m[:, 0] == ch[:, 0]) & (m[:, 1] < ch[:, 1]))
+    return torch.unique(torch.where(swap[:, None], m, ch), dim=0).contiguous()
+
+
+def enumerate_ply(plies, unforced=False, device=None):
+    """Every undecided position with exactly `plies` stones that legal play reaches from the empty board -- no game goes on
+    past a win -- one row per mirror pair (``_canonical``'s choice), uint64 [n, 2] sorted as ``np.unique(axis=0)`` sorts.
+    unforced=True keeps the rows where neither the mover nor the opponent has a playable square that completes four: at 8
+    plies the 67,557 positions of the UCI connect-4 dataset ("neither player has won yet, and the next move is not forced").
+    device=None enumerates in NumPy; a device index lists the children with c4_solve_children_dev and merges on the
+    device.  Both give the same rows, bit for bit."""
+    if not (float(plies).is_integer() and 0 <= int(plies) <= SIZE):
+        raise ValueError("plies must be 0..%d; got %r" % (SIZE, plies))
+    rows = np.zeros((1, 2), dtype=np.uint64)
+    if device is None:
+        for _ in range(int(plies)):
+            if len(rows) == 0:
+                break
+            rows = _unique_rows(_canonical(_next_ply_host(rows)))[0]
+    else:
+        import torch
+        t = _packed_on_device(torch.from_numpy(rows.view(np.int64)), device)
+        with torch.cuda.device(t.device):
+            for _ in range(int(plies)):
+                if t.shape[0] == 0:
+                    break
+                t = _next_ply_dev(t)
+        rows = np.ascontiguousarray(t.cpu().numpy().view(np.uint64).reshape(-1, 2))
+    if int(plies) == SIZE:
+        rows = rows[:0]
+    if unforced and len(rows):
+        occ = rows[:, 0] | rows[:, 1]
+        playable = (occ + np.uint64(BOTTOM)) & np.uint64(_BOARD)
+        rows = rows[((_winning_squares_np(rows[:, 0], occ) | _winning_squares_np(rows[:, 1], occ)) & playable) == 0]
+    return np.ascontiguousarray(rows)
+
+
+def _book_keys(rows):
+    """The book's key of uint64 [n, 2] rows: the smaller of ``mine + occ + BOTTOM`` and its mirror image's."""
+    occ = rows[:, 0] | rows[:, 1]
+    mine = np.where((_popcount64(occ) & 1) == 1, rows[:, 1], rows[:, 0])
+    key = mine + occ + np.uint64(BOTTOM)
+    return np.minimum(key, _mirror_key(key))
+
+
+def _interior_rows(rows):
+    """bool [n]: the undecided uint64 [n, 2] rows the search enters as interior nodes under the full window -- the mover
+    cannot win at once, and enter_node finds a move that does not lose at once.  Only these are ever probed: every other
+    position is answered by the node that meets it."""
+    occ = rows[:, 0] | rows[:, 1]
+    odd = (_popcount64(occ) & 1) == 1
+    mine, theirs = np.where(odd, rows[:, 1], rows[:, 0]), np.where(odd, rows[:, 0], rows[:, 1])
+    possible = (occ + np.uint64(BOTTOM)) & np.uint64(_BOARD)
+    at_once = (_winning_squares_np(mine, occ) & possible) != 0
+    opp_win = _winning_squares_np(theirs, occ)
+    forced = possible & opp_win
+    two = (forced & (forced - np.uint64(1))) != 0
+    left = np.where(forced != 0, forced, possible) & ~(opp_win >> np.uint64(1))
+    return ~at_once & ~two & (left != 0) & (_popcount64(occ) < SIZE - 1)
+
+
+def _merge_words(words):
+    """Sorted entry words with one entry a key: an exact entry before a lower bound before an upper bound, the tighter of
+    two bounds of a kind."""
+    words = np.asarray(words, dtype=np.uint64).reshape(-1)
+    if len(words) == 0:
+        return words
+    key = words & np.uint64(_TT_KEY_MASK)
+    score = ((words >> np.uint64(_TT_SCORE_SHIFT)) & np.uint64(0x7f)).astype(np.int64) - 64
+    kind = ((words >> np.uint64(_TT_KIND_SHIFT)) & np.uint64(3)).astype(np.int64)
+    prio = np.where(kind == _EXACT, 3 << 8, np.where(kind == _LOWER, (2 << 8) + score + 64, (1 << 8) + 64 - score))
+    order = np.lexsort((-prio, key))
+    first = np.ones(len(order), dtype=bool)
+    first[1:] = key[order][1:] != key[order][:-1]
+    return np.ascontiguousarray(words[order][first])
+
+
+class Book:
+    """One ply solved once: a sorted ``uint64`` array of table-format entries (``entry_fields``' layout: key in bits 0..48,
+    score + 64 in bits 49..55, kind 1..3 in bits 56..57), every key of a position with `age` stones.  The key is the
+    canonical one of a mirror pair, the smaller of ``mine + occ + BOTTOM`` and that key with its seven column fields
+    reversed, so one entry serves both images and no board is mirrored.  Every entry is a true bound of its position's
+    value -- the invariant a ``Table``'s entries obey -- so a book never changes an answer, whatever windows found its
+    entries and however many positions it lacks: a missing entry means the search goes on.
+
+    ``book=`` of ``solve`` / ``solve_window`` / ``outcomes`` / ``grid_triple`` / ``label`` / ``label_values`` probes it on
+    the device wherever a search reaches the book's ply (c4_solve_book_create; the image is built on first use and freed
+    by ``close()``); ``solve_host`` / ``drive_host`` probe the same object in Python (``get``).  `unknown`: uint64 [k, 2]
+    rows still to be solved, kept with the entries by ``save`` so that a later sitting goes on with them.
+
+    Raises ValueError unless the keys are sorted, unique, canonical and well formed for `age`, every kind is 1..3 and
+    every score within +-42."""
+
+    def __init__(self, age, words, unknown=None):
+        if not (float(age).is_integer() and 0 <= int(age) <= SIZE - 1):
+            raise ValueError("age %r outside 0..%d" % (age, SIZE - 1))
+        self.age = int(age)
+        self.words = np.ascontiguousarray(np.asarray(words, dtype=np.uint64).reshape(-1))
+        self.unknown = np.zeros((0, 2), dtype=np.uint64) if unknown is None else np.ascontiguousarray(unknown, dtype=np.uint64).reshape(-1, 2)
+        self._entries = None
+        self._dev = {}
+        w = self.words
+        if (w >> np.uint64(_TT_KIND_SHIFT + 2)).any():
+            raise ValueError("an entry has bits above the kind")
+        f = entry_fields(w)
+        if len(f.key) != len(w) or (f.kind == 0).any():
+            raise ValueError("every entry has a kind in 1..3")
+        if (np.abs(f.score) > SCORE_MAX).any():
+            raise ValueError("a score lies outside +-%d" % SCORE_MAX)
+        if (f.key[1:] <= f.key[:-1]).any():
+            raise ValueError("the keys are not sorted and unique")
+        if (f.mine + f.occ + np.uint64(BOTTOM) != f.key).any() or (f.mine & ~f.occ).any() or (f.occ & ~np.uint64(_BOARD)).any() or (f.age != self.age).any():
+            raise ValueError("a key is not the key of a position with %d stones" % self.age)
+        if (_mirror_key(f.key) < f.key).any():
+            raise ValueError("a key is not the canonical one of its mirror pair")
+
+    def __len__(self):
+        return len(self.words)
+
+    @property
+    def keys(self):
+        return self.words & np.uint64(_TT_KEY_MASK)
+
+    @classmethod
+    def empty(cls, age):
+        return cls(age, np.zeros(0, dtype=np.uint64))
+
+    @classmethod
+    def from_answers(cls, rows, answers, age=None):
+        """The book of uint64 [n, 2] `rows` (Boards or pairs) of one age and their `answers`: a ``Windowed``
+        (``solve_window``: an exact score becomes an exact entry, a fail-high a lower bound, a fail-low an upper bound) or
+        a ``Solved`` (``solve``: exact entries).  Only SOLVED rows give entries; UNKNOWN rows go to ``unknown``; rows of
+        any other status are left out, and so are the rows the search never looks up (``_interior_rows``: the node that
+        meets them answers them).  Mirror images give one entry.  age: needed only where there are no rows."""
+        rows = _rows_u64(rows)
+        ages = _ages(rows)
+        if len(rows) == 0 and age is None:
+            raise ValueError("no rows: give the age")
+        age = int(ages[0]) if age is None else int(age)
+        if (ages != age).any():
+            raise ValueError("a book holds one ply: the rows have %s stones" % sorted(set(ages.tolist())))
+        status = np.asarray(answers.status)
+        if hasattr(answers, "bound"):
+            score, kind = np.asarray(answers.score, dtype=np.int64), np.asarray(answers.bound, dtype=np.int64)
+        else:
+            out = np.nan_to_num(np.asarray(answers.outcome, dtype=np.float64), nan=0.5)
+            s = np.where(out == 0.5, 0, np.where(out == 1.0, 1, -1) * (43 - np.asarray(answers.final_age, dtype=np.int64)))
+            score, kind = np.where(ages & 1, -s, s), np.full(len(rows), _EXACT, dtype=np.int64)
+        ok = (status == L.SOLVE_SOLVED) & (kind != L.SOLVE_BOUND_NONE) & _interior_rows(rows)
+        words = _book_keys(rows[ok]) | ((score[ok] + 64).astype(np.uint64) << np.uint64(_TT_SCORE_SHIFT)) | (kind[ok].astype(np.uint64) << np.uint64(_TT_KIND_SHIFT))
+        return cls(age, _merge_words(words), rows[status == L.SOLVE_UNKNOWN])._without_known()
+
+    def _without_known(self):
+        """The unknown rows that have no entry yet, one a mirror pair."""
+        u = _unique_rows(_canonical(self.unknown))[0] if len(self.unknown) else self.unknown
+        self.unknown = np.ascontiguousarray(u[~np.isin(_book_keys(u), self.keys)]) if len(u) else u
+        return self
+
+    def merge(self, other):
+        """A book with the entries of both (``_merge_words`` where both have a key) and the rows neither has solved."""
+        if other.age != self.age:
+            raise ValueError("books of %d and %d stones do not merge" % (self.age, other.age))
+        return Book(self.age, _merge_words(np.concatenate([self.words, other.words])), np.concatenate([self.unknown, other.unknown]))._without_known()
+
+    def save(self, path):
+        """One ``.npz``: age, words, unknown."""
+        with open(path, "wb") as f:
+            np.savez_compressed(f, age=np.int64(self.age), words=self.words, unknown=self.unknown)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(int(z["age"]), z["words"], z["unknown"])
+
+    # probed in Python
+    def get(self, key, default=None):
+        """``(kind, score)`` of the position with the key ``mine + occ + BOTTOM``, or of its mirror image."""
+        if self._entries is None:
+            f = entry_fields(self.words)
+            self._entries = dict(zip(f.key.tolist(), zip(f.kind.tolist(), f.score.tolist())))
+        return self._entries.get(min(key, _mirror_key(key)), default)
+
+    # probed on the device
+    def handle(self, device=0):
+        """The c4_solve_book of this book on cuda:`device`, created on first use."""
+        if int(device) not in self._dev:
+            h = C.c_void_p()
+            _check(L.load().c4_solve_book_create(int(device), _ptr(self.words), len(self.words), self.age, C.byref(h)))
+            self._dev[int(device)] = h
+        return self._dev[int(device)]
+
+    def close(self):
+        """Free the device images.  No ``Table`` may still have the book attached."""
+        while self._dev:
+            L.load().c4_solve_book_destroy(self._dev.popitem()[1])
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+HostBook = Book     # probed in Python it is the same object: solve_host(book=), drive_host(book=)
+
+
+@contextlib.contextmanager
+def _carrying(table, book, device):
+    """The ``Table`` a device call passes so that it probes `book`: `table` with the book attached for the duration, or
+    without a table an entryless handle (the table-free search) that lives as long.  The attachment is a property of the
+    handle: calls that pass different books through one ``Table`` must not overlap (give each thread its own ``Table`` or
+    attach once with ``Table.attach_book``)."""
+    own = table is None
+    t = Table.entryless(device) if own else table
+    before = t.book
+    t.attach_book(book)
+    try:
+        yield t
+    finally:
+        if own:
+            t.close()
+        else:
+            t.attach_book(before)       # what the caller had attached stays attached
+
+
 Graph = namedtuple("Graph", "color0 color1 level_start child alpha beta inverse")
 
 
@@ -742,7 +1092,7 @@ def _solve_split(packed, split_plies, node_budget, nodes_per_launch, table):
     return _finish(*(a[g.inverse] for a in _graph_fold_exact(g, *answers)))
 
 
-def solve(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, deep=False, split_plies=0):
+def solve(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, deep=False, split_plies=0, book=None):
     """Solve every row on the GPU.  `boards`: a sequence of Boards (host arrays through c4_solve) or a packed int64 [n, 2]
     tensor (c4_solve_dev; a CPU tensor is moved to cuda:`device`).  Returns ``Solved`` of NumPy arrays:
 
@@ -762,7 +1112,15 @@ def solve(boards, node_budget=None, nodes_per_launch=None, device=0, table=None,
     split_plies=k (implies deep): every row is expanded k plies (c4_solve_children_dev), the distinct descendants -- mirror
     images merged -- are solved as rows of one batch, so one hard position occupies many lanes and they share the table,
     and the answers are folded back by max / min over the integer score; a row is UNKNOWN if any of its descendants is, and
-    its nodes and table_hits are the sums over its distinct descendants (so node_budget bounds each descendant)."""
+    its nodes and table_hits are the sums over its distinct descendants (so node_budget bounds each descendant).
+    book: a ``Book`` (implies deep): the search probes it wherever it reaches the book's ply, with or without a table; the
+    answers stay the same, the node counts fall -- table-free they stay deterministic -- and a book hit counts into
+    table_hits.  With a `table` the book is attached to that handle for the duration of the call (what
+    ``Table.attach_book`` had attached comes back afterwards), so calls that pass different books through one ``Table``
+    must not overlap: give each thread its own ``Table``."""
+    if book is not None:
+        with _carrying(table, book, device) as carrier:
+            return solve(boards, node_budget, nodes_per_launch, device, carrier, True, split_plies)
     deep = bool(deep or table is not None or split_plies)
     if table is not None:
         device = table.device
@@ -793,7 +1151,7 @@ def _window_arrays(alpha, beta, n):
     return np.ascontiguousarray(a, dtype=np.int8), np.ascontiguousarray(b, dtype=np.int8)
 
 
-def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, device=0, table=None, driver_plies=0, host=False):
+def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, device=0, table=None, driver_plies=0, host=False, book=None):
     """The deep search (``solve(deep=True)``: every position, optionally a ``Table``) from a root window per row.  alpha, beta:
     scalars or per-row arrays on the mover's score (43 - final age for a win, final age - 43 for a loss, 0 for a draw),
     -42 <= alpha < beta <= 42; both None: the full window.  `boards` as ``solve`` takes them.  Returns ``Windowed`` of arrays:
@@ -818,7 +1176,10 @@ def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, d
     and table_hits are the sums over the row's distinct descendants (node_budget bounds each).  A call is cut into graphs
     whose last level has at most 2^20 positions; a single row with more distinct descendants than that -- an early position
     with driver_plies of 7 or 8 -- raises ValueError: give fewer plies.  host=True (with driver_plies)
-    computes the same with ``drive_host``: no GPU, no table."""
+    computes the same with ``drive_host``: no GPU, no table.  book: ``solve``'s, on the device and with host=True."""
+    if book is not None and not host:
+        with _carrying(table, book, device) as carrier:
+            return solve_window(boards, alpha, beta, node_budget, nodes_per_launch, device, carrier, driver_plies)
     if table is not None and not host:
         device = table.device
     n = int(boards.shape[0]) if _is_tensor(boards) else len(boards)
@@ -826,17 +1187,17 @@ def solve_window(boards, alpha, beta, node_budget=None, nodes_per_launch=None, d
     if driver_plies:
         if host and table is not None:
             raise ValueError("host=True drives table-free")
-        return _drive(_rows_u64(boards), a, b, driver_plies, node_budget, nodes_per_launch, device, table, host)
+        return _drive(_rows_u64(boards), a, b, driver_plies, node_budget, nodes_per_launch, device, table, host, book=book)
     if host:
         raise ValueError("host=True belongs to driver_plies; solve_host answers single positions")
     return _finish_window(*_solve_any(boards, node_budget, nodes_per_launch, device, table, True, (a, b)))
 
 
-def outcomes(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, driver_plies=0, host=False):
+def outcomes(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, driver_plies=0, host=False, book=None):
     """Who wins each position: float64 0.0 (x) / 0.5 (draw) / 1.0 (o), NaN where the budget leaves a row unknown or the row is
     invalid; a finished position answers with its own result.  One search per row with the window (-1, +1), the narrowest
     that separates win, draw and loss -- how fast is not asked, and not paid for.  driver_plies, host: ``solve_window``'s."""
-    res = solve_window(boards, -1, 1, node_budget, nodes_per_launch, device, table, driver_plies, host)
+    res = solve_window(boards, -1, 1, node_budget, nodes_per_launch, device, table, driver_plies, host, book)
     sign = np.sign(res.score.astype(np.int64))
     absolute = np.where(_ages(_rows_u64(boards)) & 1, -sign, sign)
     return np.where(res.status == L.SOLVE_SOLVED, (absolute + 1) * 0.5, np.where(res.status == L.SOLVE_TERMINAL, res.outcome, np.nan))
@@ -942,25 +1303,26 @@ def _graph_root_answers(g, lo, hi, wa, wb):
     return status, score, bound, outcome, final_age
 
 
-def _host_leaf(c0, c1, alpha, beta, node_budget):
-    """drive_host's default leaf_solver, ``solve_host(window=)`` table-free: (status, score, bound, nodes, clean).  clean: no
+def _host_leaf(c0, c1, alpha, beta, node_budget, book=None):
+    """drive_host's default leaf_solver, ``solve_host(window=)`` table-free: (status, score, bound, nodes, clean) and, with a
+    sixth entry, the node counts at which the search hit the `book` (``_Search.hit_at``; empty without one).  clean: no
     node of the search returned without a cut-off after the last one was entered -- the lane is done in the launch that
     enters its last node even where that node uses up the launch's quota (run_lane closes a node whose moves are used up
     only while quota is left)."""
     st = _classify(c0, c1, DEEP_MAX_EMPTIES)
     if st != L.SOLVE_SOLVED:
-        return st, 0, L.SOLVE_BOUND_NONE, 0, True
+        return st, 0, L.SOLVE_BOUND_NONE, 0, True, []
     occ = c0 | c1
     age = bin(occ).count("1")
     mine, theirs = (c1, c0) if age & 1 else (c0, c1)
     if _winning_squares(mine, occ) & (occ + BOTTOM):
-        return st, 42 - age, _bound_kind(42 - age, alpha, beta), 1, True
-    s = _Search(node_budget)
+        return st, 42 - age, _bound_kind(42 - age, alpha, beta), 1, True, []
+    s = _Search(node_budget, None, book)
     try:
         score = s.node(mine, theirs, age, alpha, beta)
     except _OverBudget:
-        return L.SOLVE_UNKNOWN, 0, L.SOLVE_BOUND_NONE, s.nodes, False
-    return st, score, _bound_kind(score, alpha, beta), s.nodes, s.clean
+        return L.SOLVE_UNKNOWN, 0, L.SOLVE_BOUND_NONE, s.nodes, False, s.hit_at
+    return st, score, _bound_kind(score, alpha, beta), s.nodes, s.clean, s.hit_at
 
 
 def _interval(score, bound):
@@ -997,8 +1359,9 @@ def drive_graph_host(g, node_budget=None, nodes_per_launch=None, leaf_solver=_ho
     count = np.zeros(n_nodes, dtype=np.int64)
     full = {}       # node -> the leaf's whole search under the budget, computed when the leaf first takes part in a launch
 
-    def leaf(i, cap):
-        return leaf_solver(int(g.color0[i]), int(g.color1[i]), int(wa[i]), int(wb[i]), cap)
+    def leaf(i, cap):       # (status, score, bound, nodes, clean, hit_at); a leaf_solver may leave the last one out
+        ans = tuple(leaf_solver(int(g.color0[i]), int(g.color1[i]), int(wa[i]), int(wb[i]), cap))
+        return ans if len(ans) > 5 else ans + ((),)
 
     def answer(i, score, bound):
         lo[i], hi[i] = _interval(score, bound)
@@ -1017,7 +1380,7 @@ def drive_graph_host(g, node_budget=None, nodes_per_launch=None, leaf_solver=_ho
         if given is not None and int(i) in given:
             answer(i, *given[int(i)])
             continue
-        st, score, bound, nodes, _ = leaf(i, 1)
+        st, score, bound, nodes, _, _ = leaf(i, 1)
         if st == L.SOLVE_SOLVED:
             answer(i, score, bound)
         elif budget <= 1:
@@ -1037,7 +1400,7 @@ def drive_graph_host(g, node_budget=None, nodes_per_launch=None, leaf_solver=_ho
         for i in np.nonzero(state == _NODE_PENDING)[0]:
             if int(i) not in full:
                 full[int(i)] = leaf(i, budget)
-            st, score, bound, nodes, clean = full[int(i)]
+            st, score, bound, nodes, clean, _ = full[int(i)]
             step = min(budget - int(count[i]), quota)
             reach = int(count[i]) + step
             if st == L.SOLVE_SOLVED and nodes <= reach:
@@ -1051,9 +1414,16 @@ def drive_graph_host(g, node_budget=None, nodes_per_launch=None, leaf_solver=_ho
                 state[i] = NODE_OVER_BUDGET
         fold_mark_filter()
     status, score, bound, outcome, final_age = _graph_root_answers(g, lo, hi, wa, wb)
-    report = {"lo": lo.astype(np.int8), "hi": hi.astype(np.int8), "state": state, "nodes": count, "table_hits": np.zeros(n_nodes, dtype=np.int64),
+    # the hits among the nodes a leaf entered: those its search made up to that node count
+    hits = np.zeros(n_nodes, dtype=np.int64)
+    for i in np.nonzero(count > 0)[0]:
+        if given is not None and int(i) in given:
+            continue
+        hit_at = (full[int(i)] if int(i) in full else leaf(i, 1))[5]
+        hits[i] = int((np.asarray(hit_at, dtype=np.int64) <= count[i]).sum())
+    report = {"lo": lo.astype(np.int8), "hi": hi.astype(np.int8), "state": state, "nodes": count, "table_hits": hits,
               "alpha": wa.astype(np.int8), "beta": wb.astype(np.int8), "launches": launches, "needed": history, "graph": g}
-    return (status, score, bound, outcome, final_age, _graph_root_sums(g, count)[0], np.zeros(len(status), dtype=np.int64)), report
+    return (status, score, bound, outcome, final_age) + _graph_root_sums(g, count, hits), report
 
 
 def _finish_graph(parts):
@@ -1064,7 +1434,7 @@ def _finish_graph(parts):
     return _finish_window(status, outcome, final_age, nodes, hits, score, bound)
 
 
-def drive_host(rows, alpha, beta, driver_plies, node_budget=None, nodes_per_launch=None, leaf_solver=_host_leaf):
+def drive_host(rows, alpha, beta, driver_plies, node_budget=None, nodes_per_launch=None, leaf_solver=_host_leaf, book=None):
     """The root driver without a device: ``(Windowed, report)`` for `rows` (Boards, pairs or uint64 [n, 2]) with the window
     `alpha`, `beta` (scalars, per-row arrays, or both None), each row spread over the leaves `driver_plies` (1..8) below it.
 
@@ -1077,8 +1447,11 @@ def drive_host(rows, alpha, beta, driver_plies, node_budget=None, nodes_per_laun
 
     report: per node, levels concatenated, lo, hi int8, state int8 (NODE_*), nodes, table_hits int64, the static windows
     alpha, beta, and launches, needed (the marks after k_solve_init and after each launch) and graph (the ``Graph``).
-    leaf_solver(c0, c1, alpha, beta, node_budget) -> (status, score, bound, nodes, clean) replaces the search."""
+    leaf_solver(c0, c1, alpha, beta, node_budget) -> (status, score, bound, nodes, clean) replaces the search.  book: a
+    ``Book`` the default leaf search probes as the kernel does; table_hits then counts its hits, as c4_solve_graph does."""
     plies = _check_driver_plies(driver_plies)
+    if book is not None:
+        leaf_solver = functools.partial(leaf_solver, book=book)
     rows = _rows_u64(rows)
     a, b = _window_arrays(alpha, beta, len(rows))
     g = _build_graph(rows, a, b, plies, _children_host)
@@ -1160,7 +1533,7 @@ def _split_for_graphs(n, build):
     return out
 
 
-def _drive(rows, alpha, beta, driver_plies, node_budget, nodes_per_launch, device, table, host, tally=None):
+def _drive(rows, alpha, beta, driver_plies, node_budget, nodes_per_launch, device, table, host, tally=None, book=None):
     """``Windowed`` of uint64 [n, 2] `rows` with windows int8 [n] (or None, None) through the root driver: on the device
     (c4_solve_graph, the children listed by c4_solve_children_dev) or, host=True, ``drive_graph_host``.  tally: a dict that
     gets the count of nodes per state name (NODE_STATE_NAMES) added."""
@@ -1174,7 +1547,7 @@ def _drive(rows, alpha, beta, driver_plies, node_budget, nodes_per_launch, devic
     answered = []
     for lo, hi, g in sorted(parts, key=lambda p: p[0]):
         if host:
-            answers, report = drive_graph_host(g, node_budget, nodes_per_launch)
+            answers, report = drive_graph_host(g, node_budget, nodes_per_launch, functools.partial(_host_leaf, book=book) if book is not None else _host_leaf)
         else:
             answers, report = solve_graph(g, node_budget, nodes_per_launch, device, table)
         if tally is not None:
@@ -1219,23 +1592,23 @@ def _child_boards(board):
     return out
 
 
-def grid_triple(boards: Sequence[Board], device=0, node_budget=None, nodes_per_launch=None, host=False, table=None, split_plies=0):
+def grid_triple(boards: Sequence[Board], device=0, node_budget=None, nodes_per_launch=None, host=False, table=None, split_plies=0, book=None):
     """``[(move, value, tree)]``, what ``grid_search.grid_search(boards, plies=empties, evaluate_centre)`` returns for
     undecided boards with at most MAX_EMPTIES empty squares: GridTree's root and children with their ``absolute_value``s,
     Tree.best_move's tie to the higher column.  Every child of every root is solved as a row of its own in one batch;
     host=True solves them with ``solve_host`` instead (no GPU).  A child the budget leaves UNKNOWN raises RuntimeError.
-    table (a ``Table``; with host=True a dict) and split_plies are ``solve``'s: with either, boards of any depth are taken."""
-    deep = table is not None or bool(split_plies)
+    table (a ``Table``; with host=True a dict), split_plies and book are ``solve``'s: with any, boards of any depth are taken."""
+    deep = table is not None or bool(split_plies) or book is not None
     for b in boards:
         _check_root(b, deep)
     kids = [_child_boards(b) for b in boards]
     flat = [cb for ks in kids for _, cb in ks if cb.result is None]
     if host:
-        answers = [solve_host(cb, node_budget, table=table, deep=deep) for cb in flat]
+        answers = [solve_host(cb, node_budget, table=table, deep=deep, book=book) for cb in flat]
         status = [a.status for a in answers]
         values = [a.value for a in answers]
     elif flat:
-        res = solve(flat, node_budget, nodes_per_launch, device, table=table, split_plies=split_plies)
+        res = solve(flat, node_budget, nodes_per_launch, device, table=table, split_plies=split_plies, book=book)
         status, values = res.status.tolist(), res.value.tolist()
     else:
         status, values = [], []
@@ -1359,7 +1732,7 @@ def _first_occurrences(rows):
     return np.ascontiguousarray(rows[np.sort(first)])
 
 
-def _window_solver(node_budget, nodes_per_launch, device, table, host, driver_plies=0, tally=None):
+def _window_solver(node_budget, nodes_per_launch, device, table, host, driver_plies=0, tally=None, book=None):
     """staged_labels' window_solver on the device (c4_solve_window_dev) or, host=True, on ``solve_host`` (table: a dict or a
     ``HostTable``); with driver_plies the root driver on either, each stage one driven batch."""
     if driver_plies:
@@ -1368,14 +1741,17 @@ def _window_solver(node_budget, nodes_per_launch, device, table, host, driver_pl
 
         def driven(rows, alpha, beta):
             res = _drive(np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2), np.ascontiguousarray(alpha, dtype=np.int8),
-                         np.ascontiguousarray(beta, dtype=np.int8), driver_plies, node_budget, nodes_per_launch, device, table, host, tally)
+                         np.ascontiguousarray(beta, dtype=np.int8), driver_plies, node_budget, nodes_per_launch, device, table, host, tally, book if host else None)
             return res.status, res.score, res.nodes, res.table_hits
         return driven
     if host:
         def on_host(rows, alpha, beta):
-            ans = [solve_host((int(c0), int(c1)), node_budget, table=table, window=(int(a), int(b))) for (c0, c1), a, b in zip(rows, alpha, beta)]
+            ans, hits = [], []
+            for (c0, c1), a, b in zip(rows, alpha, beta):
+                ans.append(solve_host((int(c0), int(c1)), node_budget, table=table, window=(int(a), int(b)), book=book))
+                hits.append(ans[-1].hits if book is not None else 0)
             return (np.array([a.status for a in ans], dtype=np.int8), np.array([a.score for a in ans], dtype=np.int8),
-                    np.array([a.nodes for a in ans], dtype=np.int64), np.zeros(len(ans), dtype=np.int64))
+                    np.array([a.nodes for a in ans], dtype=np.int64), np.array(hits, dtype=np.int64))
         return on_host
 
     def on_device(rows, alpha, beta):
@@ -1387,9 +1763,14 @@ def _window_solver(node_budget, nodes_per_launch, device, table, host, driver_pl
     return on_device
 
 
-def _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors, driver_plies=0):
+def _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors, driver_plies=0, book=None):
     import torch
     from .stats import LabelledSet
+    if book is not None and not host:
+        with _carrying(table, book, device) as carrier:
+            ls, report = _label_staged(boards, node_budget, nodes_per_launch, device, carrier, host, with_priors, driver_plies)
+        report["book_age"], report["book_entries"] = book.age, len(book)
+        return ls, report
     t0 = time.perf_counter()
     if table is not None and not host:
         device = table.device
@@ -1400,7 +1781,7 @@ def _label_staged(boards, node_budget, nodes_per_launch, device, table, host, wi
         rows_in, out_dev = _rows_u64(packed), packed.device
     rows = _first_occurrences(rows_in)
     tally = {}
-    solver_fn = _window_solver(node_budget, nodes_per_launch, device, table, host, driver_plies, tally)
+    solver_fn = _window_solver(node_budget, nodes_per_launch, device, table, host, driver_plies, tally, book)
     st = staged_labels(rows, solver_fn, stage2=with_priors)
     keep = st["status"] == L.SOLVE_SOLVED
     values = torch.from_numpy((st["outcome"][keep].astype(np.float32) * np.float32(0.5)))
@@ -1424,17 +1805,18 @@ def _label_staged(boards, node_budget, nodes_per_launch, device, table, host, wi
     return ls, report
 
 
-def label_values(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, host=False, driver_plies=0):
+def label_values(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, host=False, driver_plies=0, book=None):
     """Label positions with their outcome alone: ``(LabelledSet without priors, report)``, the kind of set the reference
     scores by value only.  This is stage 1 of ``label(exact=False)`` -- one search per distinct position with the window
-    (-1, +1), at any depth -- and nothing else; rows, order and report as there.  driver_plies: ``solve_window``'s."""
+    (-1, +1), at any depth -- and nothing else; rows, order and report as there.  driver_plies: ``solve_window``'s; book:
+    ``solve``'s (the report then says book_age and book_entries)."""
     if driver_plies:
         _check_driver_plies(driver_plies)
-    return _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors=False, driver_plies=driver_plies)
+    return _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors=False, driver_plies=driver_plies, book=book)
 
 
 def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None, split_plies=0, exact=True, host=False, deep=False,
-          driver_plies=0):
+          driver_plies=0, book=None):
     """Label positions with their exact outcome: returns ``(LabelledSet, report)``.
 
     Each distinct position is solved once, together with its up-to-seven children (c4_solve_children_dev lists them) in one
@@ -1456,7 +1838,15 @@ def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None,
     open).  host=True (with exact=False) runs the same staging on ``solve_host`` -- no GPU; `table` is then a dict or a
     ``HostTable``.  driver_plies=k (with exact=False, not with split_plies) runs each stage through the root driver
     (``solve_window``): the same labels wherever both label a row, and a row stays unknown only where a descendant the proof
-    needs does; with host=True no table is taken."""
+    needs does; with host=True no table is taken.  book: ``solve``'s, on every path (the report then says book_age and
+    book_entries): with a book of the children's ply a position is labelled by lookups alone."""
+    if book is not None and exact:
+        if host:
+            raise ValueError("host=True labels with exact=False only")
+        with _carrying(table, book, device) as carrier:
+            ls, report = label(boards, node_budget, nodes_per_launch, device, carrier, split_plies, True, False, True, driver_plies)
+        report["book_age"], report["book_entries"] = book.age, len(book)
+        return ls, report
     if driver_plies:
         _check_driver_plies(driver_plies)
         if split_plies:
@@ -1466,7 +1856,7 @@ def label(boards, node_budget=None, nodes_per_launch=None, device=0, table=None,
     if not exact:
         if split_plies:
             raise ValueError("split_plies belongs to exact=True: the staged labelling does not split")
-        return _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors=True, driver_plies=driver_plies)
+        return _label_staged(boards, node_budget, nodes_per_launch, device, table, host, with_priors=True, driver_plies=driver_plies, book=book)
     if host:
         raise ValueError("host=True labels with exact=False only")
     import torch

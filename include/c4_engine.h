@@ -722,6 +722,23 @@ int c4_solve_table_create(int device, int log2_entries, c4_solve_table **out);
 int c4_solve_table_destroy(c4_solve_table *table);
 int c4_solve_table_clear(c4_solve_table *table, void *hip_stream);
 int c4_solve_table_read(c4_solve_table *table, uint64_t *entries_host, int64_t n);
+/* The book: one ply solved once (an addition: C4_ABI_VERSION stays).  c4_solve_book_create copies n entry words from host
+ * memory -- the table's layout: key in bits 0..48, score + 64 in bits 49..55, kind 1..3 in bits 56..57 -- of positions
+ * that all have `age` stones into a read-only image on `device`.  A key is the canonical one of its mirror pair: the
+ * smaller of the key and the key with its seven 7-bit column fields reversed; every entry must be a true bound of its
+ * position's value -- that, and whether the two sides' stone counts fit the mover, is the caller's to ensure; everything
+ * else is checked.  C4_EINVAL: a null argument, n < 0, an age outside 0..41, bits above the kind, a kind of 0, a score
+ * outside +-42, a key that is not canonical or whose column fields do not decode to a position with `age` stones, a key
+ * that occurs twice.  c4_solve_table_attach_book makes every later call that is given `table` probe the book (NULL: none)
+ * wherever it reaches a position of the book's age, root included; a hit counts into table_hits.  The book must live on the
+ * table's device (else C4_EINVAL) and outlive the attachment; it is never written, so any number of tables and concurrent
+ * calls may share it.  c4_solve_table_create_entryless: a handle without entries -- the table-free search, deterministic
+ * node counts -- whose only use is to carry a book; c4_solve_table_clear / _read refuse it.  Answers never depend on a book. */
+typedef struct c4_solve_book c4_solve_book;
+int c4_solve_book_create(int device, const uint64_t *words, int64_t n, int age, c4_solve_book **out);
+int c4_solve_book_destroy(c4_solve_book *book);
+int c4_solve_table_attach_book(c4_solve_table *table, const c4_solve_book *book);
+int c4_solve_table_create_entryless(int device, c4_solve_table **out);
 int c4_solve_deep_dev(int device, void *hip_stream, c4_solve_table *table, const int64_t *boards_dev, int64_t n, int64_t node_budget,
                       int64_t nodes_per_launch, int8_t *status_dev, int8_t *outcome_dev, int8_t *final_age_dev, int64_t *nodes_dev,
                       int64_t *table_hits_dev);

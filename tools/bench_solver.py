@@ -40,13 +40,15 @@ ap.add_argument("--window", action="store_true", help="measure the labelling by 
 ap.add_argument("--driver", action="store_true", help="measure the root driver against the undriven labelling instead (below)")
 ap.add_argument("--driver-budgets-log2", default="20,24", help="--driver: the node budgets of one row")
 ap.add_argument("--driver-plies", default="0,2,3", help="--driver: the driver_plies to run, 0 = undriven")
+ap.add_argument("--book", default=None, metavar="FILE", help="measure the cost and the gain of carrying a book (tools/make_book.py; 'empty': an empty one) instead (below)")
+ap.add_argument("--repeats", type=int, default=7, help="--book: repeats per arm, the median is reported")
 ap.add_argument("--part", default="open,seven,seven_big", help="--window: the parts to run; the others are kept from the file")
 ap.add_argument("--big-budget-log2", type=int, default=24, help="--window: the node budget of one row in seven_big")
 ap.add_argument("--big-count", type=int, default=4096, help="--window: seven_big takes the first N of the 4,096 positions")
 args = ap.parse_args()
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "solver_driver.json" if args.driver else "solver_window.json" if args.window else "solver_table.json" if args.table else "solver.json")
-out = {"command": "python tools/bench_solver.py%s --out profiles/%s" % (" --driver" if args.driver else " --window" if args.window else " --table" if args.table else "",
+    args.out = os.path.join(ROOT, "profiles", "solver_book.json" if args.book else "solver_driver.json" if args.driver else "solver_window.json" if args.window else "solver_table.json" if args.table else "solver.json")
+out = {"command": "python tools/bench_solver.py%s --out profiles/%s" % (" --book %s" % args.book if args.book else " --driver" if args.driver else " --window" if args.window else " --table" if args.table else "",
                                                                        os.path.basename(args.out)),
        "device": torch.cuda.get_device_name(0)}
 
@@ -151,6 +153,35 @@ def bench_table():
     dump()
 
 
+def bench_book():
+    """--book FILE: writes profiles/solver_book.json (nothing is gated on these figures)
+
+      overhead      the 512 positions with 24 empty squares of profiles/solver_table.json's `late` part (same seed, same
+                    draws), Table(24) cleared before every run, with the book attached and with none, interleaved in one
+                    process after a warm-up: seconds and nodes of every repeat, the medians, and the spread of each arm"""
+    from connect4_amd.solver import Book, Table
+    rng = np.random.RandomState(2024)
+    solve(packed([random_playout(rng, 30)]))
+    for e in range(12, 25):
+        boards = [random_playout(rng, 42 - e) for _ in range(512)]
+    t = packed(boards)
+    book = Book.empty(20) if args.book == "empty" else Book.load(args.book)
+    runs = {"none": [], "book": []}
+    with Table(24) as table:
+        solve(t, table=table)       # warm
+        for _ in range(args.repeats):
+            for arm in ("none", "book"):
+                table.clear()
+                r, dt = timed(lambda: solve(t, table=table, book=book if arm == "book" else None))
+                runs[arm].append({"seconds": dt, "nodes": int(r.nodes.sum()), "table_hits": int(r.table_hits.sum()), "unknown": int((r.status == L.SOLVE_UNKNOWN).sum())})
+    book.close()
+    out["book"] = {"file": args.book, "age": book.age, "entries": len(book)}
+    out["overhead"] = {arm: {"runs": rs, "median_seconds": float(np.median([x["seconds"] for x in rs])),
+                             "min_seconds": min(x["seconds"] for x in rs), "max_seconds": max(x["seconds"] for x in rs)} for arm, rs in runs.items()}
+    print(json.dumps({arm: {k: v for k, v in o.items() if k != "runs"} for arm, o in out["overhead"].items()}), flush=True)
+    dump()
+
+
 def bench_window():
     """--window: writes profiles/solver_window.json (single runs; nothing is gated on these figures)
 
@@ -231,6 +262,9 @@ def bench_driver():
                 dump()
 
 
+if args.book:
+    bench_book()
+    sys.exit(0)
 if args.driver:
     bench_driver()
     sys.exit(0)

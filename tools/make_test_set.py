@@ -30,7 +30,15 @@ of those searches and writes values without priors (label_values), the kind of s
 Both take positions of any depth with or without --table-log2, from --openings or from data sources; neither splits.
 --driver-plies K (1..8) runs their searches through the root driver (solver.solve_window driver_plies): each position is
 spread over the lanes of its descendants K plies down and their bounds are folded back, so a position stays unknown only
-where a descendant its proof needs does.  The file is the same wherever both label a row."""
+where a descendant its proof needs does.  The file is the same wherever both label a row.
+
+    python tools/make_test_set.py --all-positions 8 --unforced --values-only --table-log2 27 -o 8ply.pth
+    python tools/make_test_set.py --all-positions 7 --outcome-only --book 8ply.npz -o 7ply.pth
+
+--all-positions PLIES is a third source: every undecided position of that ply, one a mirror pair (solver.enumerate_ply);
+with --unforced only those where neither side completes four by a playable square -- at 8 plies the 67,557 positions of
+the reference's 8-ply set.  --book FILE (tools/make_book.py) is probed by every search wherever it reaches the book's ply:
+with an 8-ply book a 7-ply position is labelled by lookups alone."""
 import argparse
 import json
 import os
@@ -59,6 +67,9 @@ def main(argv=None):
     ap.add_argument("sources", nargs="*", metavar="SAVE_DIR_OR_DATA_PTH")
     ap.add_argument("--openings", type=int, default=None, metavar="PLIES", help="random positions after PLIES moves, not self-play data")
     ap.add_argument("--count", type=int, default=4096, help="with --openings: how many distinct positions")
+    ap.add_argument("--all-positions", type=int, default=None, metavar="PLIES", help="every undecided position of that ply, mirror images merged")
+    ap.add_argument("--unforced", action="store_true", help="with --all-positions: only positions where no playable square completes four")
+    ap.add_argument("--book", default=None, metavar="FILE", help="a solved ply (tools/make_book.py) the searches probe")
     ap.add_argument("--table-log2", type=int, default=None, metavar="N", help="solve with a transposition table of 2^N entries")
     ap.add_argument("--split-plies", type=int, default=0, metavar="K")
     ap.add_argument("--driver-plies", type=int, default=0, metavar="K", help="with --outcome-only / --values-only: the root driver, K plies deep")
@@ -71,8 +82,12 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-o", "--output", required=True)
     a = ap.parse_args(argv)
-    if (a.openings is None) == (not a.sources):
-        ap.error("give either sources or --openings")
+    if sum([a.openings is not None, a.all_positions is not None, bool(a.sources)]) != 1:
+        ap.error("give either sources, --openings or --all-positions")
+    if a.all_positions is not None and not 0 <= a.all_positions <= 12:
+        ap.error("--all-positions takes 0..12 plies")
+    if a.unforced and a.all_positions is None:
+        ap.error("--unforced belongs to --all-positions")
     if a.openings is not None and not 0 <= a.openings <= 41:
         ap.error("--openings takes 0..41 plies")
     if a.outcome_only and a.values_only:
@@ -84,20 +99,26 @@ def main(argv=None):
         ap.error("--driver-plies belongs to --outcome-only and --values-only")
     if a.driver_plies and not 1 <= a.driver_plies <= 8:
         ap.error("--driver-plies takes 1..8")
-    if a.openings is not None and 42 - a.openings > 24 and a.table_log2 is None and not a.split_plies and not staged:
+    plies = a.openings if a.openings is not None else a.all_positions
+    if plies is not None and 42 - plies > 24 and a.table_log2 is None and not a.split_plies and not staged and not a.book:
         ap.error("positions with more than 24 empty squares need --table-log2 (or --split-plies)")
     import torch
     import __graft_entry__ as entry
     entry.build()
     from connect4_amd import engine
-    from connect4_amd.solver import Table, label, label_values, random_openings
+    from connect4_amd.solver import Book, Table, enumerate_ply, label, label_values, random_openings
     dev = torch.device("cuda", a.device)
     table = Table(a.table_log2, a.device) if a.table_log2 is not None else None
+    book = Book.load(a.book) if a.book else None
     parts, rows = [], 0
     if a.openings is not None:
         boards = random_openings(a.openings, a.count, a.seed)
         rows = len(boards)
         bits = np.array([b.color for b in boards], dtype=np.uint64).reshape(rows, 2)
+        parts.append(torch.from_numpy(bits.view(np.int64)).to(dev))
+    if a.all_positions is not None:
+        bits = enumerate_ply(a.all_positions, a.unforced, device=a.device)
+        rows = len(bits)
         parts.append(torch.from_numpy(bits.view(np.int64)).to(dev))
     for src in a.sources:
         for path in data_files(src):
@@ -119,15 +140,17 @@ def main(argv=None):
         pick = torch.sort(torch.randperm(late, generator=g)[:a.max_positions]).values
         boards = boards[pick.to(dev)].contiguous()
     if a.values_only:
-        ls, report = label_values(boards, node_budget=a.node_budget, device=a.device, table=table, driver_plies=a.driver_plies)
+        ls, report = label_values(boards, node_budget=a.node_budget, device=a.device, table=table, driver_plies=a.driver_plies, book=book)
     elif a.outcome_only:
-        ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, exact=False, driver_plies=a.driver_plies)
+        ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, exact=False, driver_plies=a.driver_plies, book=book)
     else:
-        ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, split_plies=a.split_plies)
+        ls, report = label(boards, node_budget=a.node_budget, device=a.device, table=table, split_plies=a.split_plies, book=book)
     if table is not None:
         table.close()
+    if book is not None:
+        book.close()
     ls.save(a.output)
-    report = dict(report, rows_read=rows, distinct_late=late, min_age=a.min_age, output=a.output, openings=a.openings,
+    report = dict(report, rows_read=rows, distinct_late=late, min_age=a.min_age, output=a.output, openings=a.openings, all_positions=a.all_positions, unforced=a.unforced, book=a.book,
                   mode="values-only" if a.values_only else "outcome-only" if a.outcome_only else "exact")
     print(json.dumps(report))
     hist = {k: int((ls.values == k).sum().item()) for k in (0.0, 0.5, 1.0)}
