@@ -32,6 +32,8 @@ SOLVE_BOUND_NONE, SOLVE_BOUND_LOWER, SOLVE_BOUND_UPPER, SOLVE_BOUND_EXACT = 0, 1
 SOLVE_NODE_INTERIOR, SOLVE_NODE_SELF, SOLVE_NODE_ANSWERED, SOLVE_NODE_OVER_BUDGET, SOLVE_NODE_DROPPED, SOLVE_NODE_PENDING = 0, 1, 2, 3, 4, 5
 SOLVE_GRAPH_MAX_PLIES = 8
 SOLVE_DEFAULT_NODES_PER_LAUNCH = 1 << 14
+REVIEW_COLUMNS = ("late", "outcome_known", "kept_known", "kept", "blunders", "target_agrees", "contradictions")     # C4_REVIEW_*
+REVIEW_GAME_COLUMNS = ("n_late", "n_kept_known", "n_blunders", "last_blunder_age")                                  # C4_REVIEW_GAME_*
 
 
 class EngineError(RuntimeError):
@@ -233,6 +235,9 @@ SIGNATURES = {
                         [_P(C.c_int8)] * 5 + [_i64p, _i64p]),
     "c4_solve_graph": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, _i64p, C.c_int, _P(C.c_int32), _P(C.c_int8), _P(C.c_int8), C.c_int64,
                                  C.c_int64] + [_P(C.c_int8)] * 5 + [_i64p, _i64p] + [_P(C.c_int8)] * 3 + [_i64p, _i64p]),
+    "c4_review_select_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "c4_review_outcomes_dev": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3),
+    "c4_review_fold_dev": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64] + [C.c_void_p] * 14),
 }
 
 _lib = None

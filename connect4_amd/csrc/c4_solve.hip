@@ -1,5 +1,5 @@
 // c4_solve.hip -- exact values of positions by alpha-beta on gfx950, behind c4_solve / c4_solve_deep / c4_solve_window, their
-// _dev twins, the c4_solve_table_* calls and c4_solve_children_dev of include/c4_engine.h.
+// _dev twins, the c4_solve_table_* calls, c4_solve_children_dev and the c4_review_*_dev calls of include/c4_engine.h.
 //
 // The answer is the one the reference's GridSearch(plies >= empty squares) computes exhaustively
 // (oinkoink/grid_search.py:38-71: no evaluator is reached, the terminal scoring prefers faster wins and
@@ -721,6 +721,162 @@ __global__ void __launch_bounds__(256) k_solve_children(const int64_t *__restric
         children[(row * WIDTH + c) * 2] = (int64_t)n0;
         children[(row * WIDTH + c) * 2 + 1] = (int64_t)n1;
         legal[row * WIDTH + c] = ok ? 1 : 0;
+    }
+}
+
+// -- the review of finished games against exact play (c4_review_*_dev) ------------------------------------------------------
+// Book-keeping around c4_solve_window_dev, which searches the distinct late positions of a batch of games from the window
+// (-1, +1): one lane a position, straight-line, every index checked, no LDS, no scratch, no lane waits for another, the
+// only loop the seven columns of legal_mask / col_count.  The counters are 64- and 32-bit integer atomics (atomicAdd,
+// atomicMax, atomicMin), so every output is a function of the inputs whatever the dispatch order.
+constexpr int REVIEW_PLIES = C4_REVIEW_PLIES, REVIEW_COLUMNS = C4_REVIEW_COLUMNS, REVIEW_GAME_COLUMNS = C4_REVIEW_GAME_COLUMNS;
+
+// late[row] = 1 for an undecided position with at most max_empties empty squares: the rows that are searched
+__global__ void __launch_bounds__(256) k_review_select(const int64_t *__restrict__ boards, int64_t n, int max_empties, uint8_t *__restrict__ late)
+{
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n) return;
+    int o, fa;
+    late[row] = classify((uint64_t)boards[2 * row], (uint64_t)boards[2 * row + 1], o, fa, max_empties) == C4_SOLVE_SOLVED ? 1 : 0;
+}
+
+// the searched rows' answers spread over the positions: status, outcome (absolute, from the sign of the mover's score and
+// the parity of the age -- solver.outcomes) and nodes of row_of[row]; a position that is not late is TOO_DEEP, -1, 0
+__global__ void __launch_bounds__(256) k_review_outcomes(const int64_t *__restrict__ boards, const uint8_t *__restrict__ late,
+                                                         const int64_t *__restrict__ row_of, int64_t n, const int8_t *__restrict__ s_status,
+                                                         const int8_t *__restrict__ s_score, const int64_t *__restrict__ s_nodes, int64_t m,
+                                                         int8_t *__restrict__ status, int8_t *__restrict__ outcome, int64_t *__restrict__ nodes)
+{
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n) return;
+    int st = C4_SOLVE_TOO_DEEP, o = -1;
+    int64_t nd = 0;
+    if (late[row]) {
+        const int64_t r = row_of[row];
+        st = C4_SOLVE_UNKNOWN;      // an index outside the searched rows answers nothing
+        if (r >= 0 && r < m) {
+            st = s_status[r];
+            nd = s_nodes ? s_nodes[r] : 0;
+            if (st == C4_SOLVE_SOLVED) {
+                const int age = popc64((uint64_t)boards[2 * row] | (uint64_t)boards[2 * row + 1]);
+                const int score = s_score[r];
+                const int sign = score > 0 ? 1 : score < 0 ? -1 : 0;
+                o = ((age & 1) ? -sign : sign) + 1;     // o moves at even ages
+            }
+        }
+    }
+    status[row] = (int8_t)st;
+    outcome[row] = (int8_t)o;
+    if (nodes) nodes[row] = nd;
+}
+
+// the aggregates before a fold: zeros, and -1 for every game's last_blunder_age
+__global__ void __launch_bounds__(256) k_review_clear(int64_t *__restrict__ by_ply, int32_t *__restrict__ per_game, int64_t n_games,
+                                                      int32_t *__restrict__ chain_errors, int32_t *__restrict__ first_error)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < REVIEW_PLIES * REVIEW_COLUMNS) by_ply[i] = 0;
+    if (i < n_games * REVIEW_GAME_COLUMNS) per_game[i] = (i % REVIEW_GAME_COLUMNS) == C4_REVIEW_GAME_LAST_BLUNDER_AGE ? -1 : 0;
+    if (i == 0) {
+        *chain_errors = 0;
+        if (first_error) *first_error = INT32_MAX;
+    }
+}
+
+struct ReviewFold {
+    const int64_t *boards;          // [n][2]
+    const uint8_t *moves;           // [n]
+    const int32_t *game_index;      // [n]
+    const int8_t *results;          // [n_games]
+    const int8_t *outcome;          // [n], k_review_outcomes'
+    const uint8_t *late;            // [n], k_review_select's
+    const float *targets_in;        // [n], with exact_targets
+    int8_t *kept, *target_agrees;   // [n]
+    int64_t *by_ply;                // [42][7]
+    int32_t *per_game;              // [n_games][4]
+    int32_t *chain_errors, *first_error;
+    float *exact_targets;           // [n] or nullptr
+    const uint8_t *keep;            // [n][7], the moves that keep the outcome; with exact_priors
+    const uint8_t *keep_known;      // [n], 1 where the row's keep mask is known
+    const float *policy_in;         // [n][7]
+    float *exact_priors;            // [n][7] or nullptr
+    int64_t n, n_games;
+};
+
+// The rule of the review (c4_engine.h) for one position: the chain to the next row -- row + 1 is read by a plain load,
+// every input is complete before this launch --, kept / target_agrees, the counters, the exact target.
+__global__ void __launch_bounds__(256) k_review_fold(ReviewFold f)
+{
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= f.n) return;
+    const uint64_t c0 = (uint64_t)f.boards[2 * row], c1 = (uint64_t)f.boards[2 * row + 1];
+    const int g = f.game_index[row];
+    const int mv = f.moves[row];
+    int o_self, fa;
+    const int st = classify(c0, c1, o_self, fa, DEEP_MAX_EMPTIES);
+    const uint64_t occ = c0 | c1;
+    const int age = popc64(occ);
+    // the chain: a row is an undecided position of a game of the batch, its move is playable, and the position after the
+    // move is the next row of the game or, behind the last row, finished with the game's result
+    bool ok = st == C4_SOLVE_SOLVED && g >= 0 && g < f.n_games && mv < WIDTH;
+    int result = -1;
+    bool has_next = false;
+    if (ok) {
+        result = f.results[g];
+        ok = result >= -1 && result <= C4_RESULT_OWIN && col_count(occ, mv) < HEIGHT;
+    }
+    if (ok) {
+        uint64_t n0 = c0, n1 = c1;
+        const uint32_t after = make_move(n0, n1, mv);
+        has_next = row + 1 < f.n && f.game_index[row + 1] == g;
+        if (has_next)
+            ok = after == ST_FRESH && (uint64_t)f.boards[2 * row + 2] == n0 && (uint64_t)f.boards[2 * row + 3] == n1;
+        else
+            ok = after != ST_FRESH && (result < 0 || result == (int)after - (int)ST_XWIN);
+    }
+    int kept = -1, agrees = 0;
+    float target = f.exact_targets ? f.targets_in[row] : 0.0f;
+    if (!ok) {
+        atomicAdd(f.chain_errors, 1);
+        if (f.first_error) atomicMin(f.first_error, (int32_t)row);
+    } else if (f.late[row]) {
+        const int o = f.outcome[row];
+        const int next = has_next ? (int)f.outcome[row + 1] : result;
+        if (o >= 0 && next >= 0) kept = o == next ? 1 : 0;
+        agrees = (o >= 0 && o == result) ? 1 : 0;
+        // o, who moves at even ages, gains by a larger code; a known gain for the mover contradicts the solver
+        const bool contradiction = kept == 0 && ((age & 1) ? next < o : next > o);
+        if (o >= 0) target = 0.5f * (float)o;
+        int64_t *ply = f.by_ply + age * REVIEW_COLUMNS;
+        atomicAdd((unsigned long long *)&ply[C4_REVIEW_LATE], 1ULL);
+        if (o >= 0) atomicAdd((unsigned long long *)&ply[C4_REVIEW_OUTCOME_KNOWN], 1ULL);
+        if (kept >= 0) atomicAdd((unsigned long long *)&ply[C4_REVIEW_KEPT_KNOWN], 1ULL);
+        if (kept == 1) atomicAdd((unsigned long long *)&ply[C4_REVIEW_KEPT], 1ULL);
+        if (kept == 0) atomicAdd((unsigned long long *)&ply[C4_REVIEW_BLUNDERS], 1ULL);
+        if (agrees) atomicAdd((unsigned long long *)&ply[C4_REVIEW_TARGET_AGREES], 1ULL);
+        if (contradiction) atomicAdd((unsigned long long *)&ply[C4_REVIEW_CONTRADICTIONS], 1ULL);
+        int32_t *game = f.per_game + (int64_t)g * REVIEW_GAME_COLUMNS;
+        atomicAdd(&game[C4_REVIEW_GAME_LATE], 1);
+        if (kept >= 0) atomicAdd(&game[C4_REVIEW_GAME_KEPT_KNOWN], 1);
+        if (kept == 0) {
+            atomicAdd(&game[C4_REVIEW_GAME_BLUNDERS], 1);
+            atomicMax(&game[C4_REVIEW_GAME_LAST_BLUNDER_AGE], age);
+        }
+    }
+    f.kept[row] = (int8_t)kept;
+    f.target_agrees[row] = (int8_t)agrees;
+    if (f.exact_targets) f.exact_targets[row] = target;
+    if (f.exact_priors) {
+        // uniform over the keeping moves where the mask is known (and the chain holds), the input policy elsewhere
+        int count = 0;
+        if (ok && f.late[row] && f.keep_known[row]) {
+#pragma unroll
+            for (int c = 0; c < WIDTH; ++c) count += f.keep[row * WIDTH + c] ? 1 : 0;
+        }
+        const float share = count ? 1.0f / (float)count : 0.0f;
+#pragma unroll
+        for (int c = 0; c < WIDTH; ++c)
+            f.exact_priors[row * WIDTH + c] = count ? (f.keep[row * WIDTH + c] ? share : 0.0f) : f.policy_in[row * WIDTH + c];
     }
 }
 
@@ -1602,6 +1758,68 @@ int c4_solve_children_dev(int device, void *hip_stream, const int64_t *boards_de
     if (rc) return rc;
     hipLaunchKernelGGL(k_solve_children, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, boards_dev, n,
                        children_dev, legal_dev);
+    SOLVE_CHECK(hipGetLastError());
+    return C4_OK;
+}
+
+int c4_review_select_dev(int device, void *hip_stream, const int64_t *boards_dev, int64_t n, int max_empties, uint8_t *late_dev)
+{
+    if (n < 0) { set_solve_err("n < 0"); return C4_EINVAL; }
+    if (max_empties < 0 || max_empties > CELLS) { set_solve_err("max_empties %d outside 0..%d", max_empties, CELLS); return C4_EINVAL; }
+    if (n == 0) return C4_OK;
+    if (!boards_dev || !late_dev) { set_solve_err("null argument"); return C4_EINVAL; }
+    int rc = pick_device(device);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_review_select, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, boards_dev, n, max_empties,
+                       late_dev);
+    SOLVE_CHECK(hipGetLastError());
+    return C4_OK;
+}
+
+int c4_review_outcomes_dev(int device, void *hip_stream, const int64_t *boards_dev, const uint8_t *late_dev, const int64_t *row_of_dev, int64_t n,
+                           const int8_t *searched_status_dev, const int8_t *searched_score_dev, const int64_t *searched_nodes_dev, int64_t m,
+                           int8_t *status_dev, int8_t *outcome_dev, int64_t *nodes_dev)
+{
+    if (n < 0 || m < 0) { set_solve_err("n < 0 or m < 0"); return C4_EINVAL; }
+    if (n == 0) return C4_OK;
+    if (!boards_dev || !late_dev || !row_of_dev || !status_dev || !outcome_dev || (m > 0 && (!searched_status_dev || !searched_score_dev)) ||
+        (nodes_dev && m > 0 && !searched_nodes_dev)) {
+        set_solve_err("null argument");
+        return C4_EINVAL;
+    }
+    int rc = pick_device(device);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_review_outcomes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, boards_dev, late_dev,
+                       row_of_dev, n, searched_status_dev, searched_score_dev, searched_nodes_dev, m, status_dev, outcome_dev, nodes_dev);
+    SOLVE_CHECK(hipGetLastError());
+    return C4_OK;
+}
+
+int c4_review_fold_dev(int device, void *hip_stream, const int64_t *boards_dev, const uint8_t *moves_dev, const int32_t *game_index_dev,
+                       const int8_t *results_dev, int64_t n, int64_t n_games, const int8_t *outcome_dev, const uint8_t *late_dev,
+                       const float *targets_in_dev, int8_t *kept_dev, int8_t *target_agrees_dev, int64_t *by_ply_dev, int32_t *per_game_dev,
+                       int32_t *chain_errors_dev, int32_t *first_error_dev, float *exact_targets_dev, const uint8_t *keep_dev,
+                       const uint8_t *keep_known_dev, const float *policy_in_dev, float *exact_priors_dev)
+{
+    if (n < 0 || n_games < 0) { set_solve_err("n < 0 or n_games < 0"); return C4_EINVAL; }
+    if (n > INT32_MAX || n_games > INT32_MAX / REVIEW_GAME_COLUMNS) { set_solve_err("more rows or games than 32-bit indices hold"); return C4_EINVAL; }
+    if (!by_ply_dev || !chain_errors_dev || (n_games > 0 && (!per_game_dev || !results_dev)) ||
+        (n > 0 && (!boards_dev || !moves_dev || !game_index_dev || !outcome_dev || !late_dev || !kept_dev || !target_agrees_dev)) ||
+        (n > 0 && exact_targets_dev && !targets_in_dev) || (n > 0 && exact_priors_dev && (!keep_dev || !keep_known_dev || !policy_in_dev))) {
+        set_solve_err("null argument");
+        return C4_EINVAL;
+    }
+    int rc = pick_device(device);
+    if (rc) return rc;
+    const int64_t cells = n_games * REVIEW_GAME_COLUMNS > REVIEW_PLIES * REVIEW_COLUMNS ? n_games * REVIEW_GAME_COLUMNS : REVIEW_PLIES * REVIEW_COLUMNS;
+    hipLaunchKernelGGL(k_review_clear, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, by_ply_dev, per_game_dev,
+                       n_games, chain_errors_dev, first_error_dev);
+    SOLVE_CHECK(hipGetLastError());
+    if (n == 0) return C4_OK;
+    const ReviewFold f{boards_dev, moves_dev, game_index_dev, results_dev, outcome_dev, late_dev, targets_in_dev, kept_dev, target_agrees_dev,
+                       by_ply_dev, per_game_dev, chain_errors_dev, first_error_dev, exact_targets_dev, keep_dev, keep_known_dev, policy_in_dev,
+                       exact_priors_dev, n, n_games};
+    hipLaunchKernelGGL(k_review_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, f);
     SOLVE_CHECK(hipGetLastError());
     return C4_OK;
 }

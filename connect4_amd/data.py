@@ -73,6 +73,14 @@ class GameStorage:
             pickle.dump(objs, f)
         self.last_game = objs[-1] if objs else None
 
+    def load(self, folder_path: str) -> List[GameData]:
+        """The games.pkl that ``save`` wrote into `folder_path` (or that file itself): the list of GameData."""
+        path = folder_path if os.path.isfile(folder_path) else os.path.join(folder_path, "games.pkl")
+        with open(path, "rb") as f:
+            objs = pickle.load(f)
+        self.last_game = objs[-1] if objs else None
+        return objs
+
     def last_game_str(self):
         return game_str(self.last_game.moves, self.last_game.values, self.last_game.priors)
 

@@ -9,7 +9,9 @@ appended to save_dir/<name>.pkl; `train_stats` keeps the reference's per-epoch t
 TrainingLoop._match (training.py:176-207) is here as well: with `match_every`, rank 0 plays the freshly trained net against
 the net of ten generations ago -- inside the fused kernel (connect4_amd.match.DeviceMatch) -- or, while gen <= 10, against
 evaluate_centre_with_prior on the host lock-step Match, and appends the result to save_dir/match_results.pkl.  Visdom
-stays with the reference's loop.
+stays with the reference's loop.  Not in the reference: with `review_empties` rank 0 reviews the generation's games against
+exact play (connect4_amd/review.py) before the training tensors are built, appends the summary to save_dir/review.pkl and,
+with `exact_targets`, trains on the exact value of every solved late position instead of the game's result (opt-in).
 """
 import os
 import pickle
@@ -34,7 +36,8 @@ def existing_window(save_dir: str, gen: int):
 def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir: Optional[str] = None, gen: int = 0,
                    seed: int = 0, device: int = 0, n_slots: Optional[int] = None, write_games_pkl: bool = False,
                    timings: Optional[dict] = None, precision: Optional[str] = None, test_sets: Optional[dict] = None,
-                   train_stats: bool = False, match_every: Optional[int] = None, match_plies: int = 1):
+                   train_stats: bool = False, match_every: Optional[int] = None, match_plies: int = 1,
+                   review_empties: Optional[int] = None, review_table=None, exact_targets: bool = False):
     """Returns (PackedGames of all ranks, last_loss).  With torch.distributed initialised every rank plays its shard and
     all ranks receive all games.  There is ONE model, as in the reference (training.py:147-153, model.py:143-147): rank 0
     writes save_dir/<gen>/{data.pth, games.pkl} (storage.py:15-16, data.py:47-64), trains on `trainer.device` over the
@@ -44,8 +47,11 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
     `test_sets` (name -> stats.LabelledSet or the path of a Connect4Dataset file) and `train_stats`: see score_test_sets and
     Trainer.train(stats=True); both are rank 0's work and add no collective.  A path is loaded on every call: a caller that
     loops over run_generation passes LabelledSets (load_test_sets once); run_generations loads each path once.
-    `match_every` / `match_plies`: see generation_match (rank 0, after the checkpoint, when gen % match_every == 0)."""
+    `match_every` / `match_plies`: see generation_match (rank 0, after the checkpoint, when gen % match_every == 0).
+    `review_empties` / `review_table` / `exact_targets`: see review_generation (rank 0, after the games are gathered and
+    before the training tensors are built; no collective).  The games returned are the games as played."""
     import torch
+    _check_review_args(review_empties, exact_targets)
     multi, rank = _ranks()
     test_sets = load_test_sets(test_sets, trainer.device) if rank == 0 else None
     earlier = existing_window(save_dir, gen) if (save_dir is not None and rank == 0) else []
@@ -54,8 +60,10 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
     t1 = time.perf_counter()
     loss, rows = None, 0
     t2 = t1
+    review = None
     if rank == 0:
-        boards, values, priors = games.training_tensors(add_fliplr=True)       # on the device
+        trained, review = review_generation(games, review_empties, review_table, exact_targets, save_dir, gen)
+        boards, values, priors = trained.training_tensors(add_fliplr=True)       # on the device
         if save_dir is not None:
             _write_generation(games, (boards, values, priors), save_dir, gen, write_games_pkl)
             if earlier:   # data.py:66-75: this generation first, then the earlier ones, newest first
@@ -74,6 +82,8 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
     if timings is not None:
         timings.update(selfplay_and_gather_s=t1 - t0, tensors_and_write_s=t2 - t1, train_s=t3 - t2,
                        positions=int(games.n_positions), training_rows=rows)
+        if review is not None:
+            timings.update(review)
     if rank == 0:
         _report(trainer, test_sets, train_stats, save_dir, gen, timings)
         if match_every and gen % match_every == 0:
@@ -99,6 +109,32 @@ def _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision):
             net.close()
     torch.cuda.synchronize(device)
     return games
+
+
+def _check_review_args(review_empties, exact_targets):
+    if exact_targets and review_empties is None:
+        raise ValueError("exact_targets=True trains on the review's answers: give review_empties")
+
+
+def review_generation(games, review_empties, review_table, exact_targets, save_dir, gen):
+    """The generation's games reviewed against exact play (connect4_amd.review.review_games with max_empties =
+    `review_empties`, table = `review_table`); nothing at all with review_empties=None.  Returns (the games to train on,
+    None or {"review": the review's summary(), "review_s": seconds} for the generation's timings / report dict); with a
+    save_dir the summary and review_s are also appended to save_dir/review.pkl (append_history).  The games to train on are
+    `games` themselves unless `exact_targets`: then ``games.with_exact_targets(review)`` -- data.pth, the replay window's
+    segment and the training rows carry the exact value of every solved late position; games.pkl keeps the games as played.
+    Opt-in: whether exact targets train a stronger net has not been measured."""
+    if review_empties is None:
+        return games, None
+    from .review import review_games
+    t0 = time.perf_counter()
+    review = review_games(games, max_empties=review_empties, table=review_table)
+    summary = review.summary()
+    seconds = time.perf_counter() - t0
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        append_history(os.path.join(save_dir, "review.pkl"), gen, dict(summary, review_s=seconds))
+    return (games.with_exact_targets(review) if exact_targets else games), {"review": summary, "review_s": seconds}
 
 
 def _write_generation(games, tensors, save_dir, gen, write_games_pkl):
@@ -250,7 +286,7 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
                     first_gen: Optional[int] = None, seed: int = 0, device: int = 0, n_slots: Optional[int] = None,
                     precision: Optional[str] = None, write_games_pkl: bool = False, timings: Optional[list] = None,
                     test_sets: Optional[dict] = None, train_stats: bool = False, match_every: Optional[int] = None,
-                    match_plies: int = 1):
+                    match_plies: int = 1, review_empties: Optional[int] = None, review_table=None, exact_targets: bool = False):
     """n_generations generations of run_generation -- same seeds (seed + 1000 * gen), same files (data.pth, net.pth,
     optional games.pkl), same broadcast of the trained state -- with the sliding window (data.py:66-75) kept on rank 0's GPU
     as packed positions (replay.ReplayWindow): each generation's games are appended to it and trained with
@@ -264,10 +300,12 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
     holds.  `timings`: a list that receives one dict per generation -- run_generation's keys, plus window_rows and
     window_bytes, and with `test_sets` / `train_stats` (as run_generation: scored on rank 0 after each checkpoint, appended
     to save_dir/<name>.pkl) the sets' names and train_stats, and with `match_every` (generation_match on rank 0 after the
-    checkpoint of every generation with gen % match_every == 0; save_dir/match_results.pkl) "match".  Returns (the window --
-    None on other ranks --, [last loss of each generation])."""
+    checkpoint of every generation with gen % match_every == 0; save_dir/match_results.pkl) "match", and with `review_empties`
+    (review_generation, as run_generation; with `exact_targets` the window's segment carries the exact targets) "review" and
+    "review_s".  Returns (the window -- None on other ranks --, [last loss of each generation])."""
     import torch
     from .replay import ReplayWindow
+    _check_review_args(review_empties, exact_targets)
     multi, rank = _ranks()
     os.makedirs(save_dir, exist_ok=True)
     test_sets = load_test_sets(test_sets, trainer.device) if rank == 0 else None
@@ -288,9 +326,11 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
         t1 = time.perf_counter()
         loss, rows, nbytes = None, 0, 0
         t2 = t1
+        review = None
         if rank == 0:
-            _write_generation(games, games.training_tensors(add_fliplr=True), save_dir, gen, write_games_pkl)
-            window.append(gen, tuple(t.to(window.device) for t in (games.boards, games.targets, games.policy)))
+            trained, review = review_generation(games, review_empties, review_table, exact_targets, save_dir, gen)
+            _write_generation(games, trained.training_tensors(add_fliplr=True), save_dir, gen, write_games_pkl)
+            window.append(gen, tuple(t.to(window.device) for t in (trained.boards, trained.targets, trained.policy)))
             window.select(gen)
             torch.cuda.synchronize(device)
             t2 = time.perf_counter()
@@ -303,6 +343,8 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
         losses.append(loss)
         report = dict(generation=gen, selfplay_and_gather_s=t1 - t0, tensors_and_write_s=t2 - t1, train_s=t3 - t2,
                       positions=int(games.n_positions), training_rows=rows, window_rows=rows, window_bytes=nbytes)
+        if review is not None:
+            report.update(review)
         if rank == 0:
             _report(trainer, test_sets, train_stats, save_dir, gen, report)
             if match_every and gen % match_every == 0:

@@ -136,6 +136,23 @@ class PackedGames:
                            t(np.array([CODE_FROM_RESULT[g.result] for g in games], dtype=np.int8)),
                            t(np.array([g.game_id + id_offset for g in games], dtype=np.int64)))
 
+    # -- exact targets -----------------------------------------------------------------------
+    def with_exact_targets(self, review, priors: bool = False):
+        """The games with the targets of `review` (``review.review_games`` of these games): a late row whose outcome the
+        review knows carries its exact value -- Result's 1.0 / 0.5 / 0.0 --, every other row the game's result as before.
+        A new PackedGames; every other field is shared, and ``results`` keeps the games' own results.  priors=True asks
+        for the exact priors too -- ``policy`` uniform over the moves that keep the outcome wherever the review knows them --
+        and needs a review made with moves=True: ValueError without its keep mask."""
+        if priors and getattr(review, "keep", None) is None:
+            raise ValueError("priors=True needs a review with a keep mask, and this review has none")
+        if int(review.exact_targets.shape[0]) != self.n_positions:
+            raise ValueError("the review has %d positions, the games %d" % (int(review.exact_targets.shape[0]), self.n_positions))
+        fields = {k: getattr(self, k) for k in _PER_POS + _PER_GAME}
+        fields["targets"] = review.exact_targets.to(self.targets.device)
+        if priors:
+            fields["policy"] = review.exact_priors.to(self.policy.device)
+        return PackedGames(**fields)
+
     # -- training tensors --------------------------------------------------------------------
     def training_tensors(self, add_fliplr: bool = True):
         """(boards F32[m,3,6,7], values F32[m], priors F32[m,7]) = native_to_pytorch(...) of data.py:78-105, built

@@ -814,6 +814,73 @@ int c4_solve_graph(int device, c4_solve_table *table, const uint64_t *color0, co
                    int64_t *nodes, int64_t *table_hits, int8_t *node_lo, int8_t *node_hi, int8_t *node_state, int64_t *node_nodes,
                    int64_t *node_table_hits);
 
+/* -- the review of finished games against exact play (c4_solve.hip) ------------------------------------------------------ */
+/* A batch of finished games in the layout c4_export_games_dev writes: a game is a run of consecutive rows with one
+ * game_index, plies ascending; row i + 1 of a game is the position after moves[i] on row i, and after the last row's move the
+ * game is over with results[g] (C4_RESULT_*, or -1: the game carries no result).  A position is late when it is undecided and
+ * has at most max_empties empty squares.  The three calls are the book-keeping around one c4_solve_window_dev call on the
+ * distinct late rows with alpha = -1, beta = +1, which the caller makes between the first and the second.  All pointers are
+ * device pointers; each call is one launch (the fold: two) on hip_stream and waits for nothing.  Every kernel is one lane a
+ * position and straight-line: no LDS, no scratch, no lane waits for another; the counters are integer atomics, so every
+ * output is a function of the inputs.  A null pointer that is not marked optional, a negative count, max_empties outside
+ * 0..42: C4_EINVAL.  Messages: c4_solve_last_error().  (Additions: C4_ABI_VERSION stays.)
+ *
+ * c4_review_select_dev: late_dev uint8 [n] = 1 for a late row, 0 for every other -- one with more empty squares, a finished
+ * position, a row that is no position (C4_SOLVE_INVALID); the fold counts the last two as chain errors.
+ *
+ * c4_review_outcomes_dev: the answers of the m searched rows (searched_status_dev, searched_score_dev int8 [m] and, optional
+ * together with nodes_dev, searched_nodes_dev int64 [m]: c4_solve_window_dev's status, score and nodes) spread over the
+ * positions through row_of_dev int64 [n], the searched row of every late position (read for late rows only).  status_dev
+ * int8 [n]: the searched row's C4_SOLVE_SOLVED or C4_SOLVE_UNKNOWN (also for an index outside 0..m-1), C4_SOLVE_TOO_DEEP for
+ * a row that is not late -- here: more empty squares than asked for.  outcome_dev int8 [n]: C4_RESULT_* under best play,
+ * absolute, from the sign of the mover's score and the parity of the age; -1 unless the status is C4_SOLVE_SOLVED.
+ * nodes_dev int64 [n] (optional): the searched row's count, 0 for a row that is not late.
+ *
+ * c4_review_fold_dev: the rule.  With next[i] = outcome[i + 1] if row i + 1 belongs to the same game, else results[g]:
+ *   kept_dev           int8 [n]: 1 if outcome[i] and next[i] are both known and equal, 0 if both are known and differ -- a
+ *                      blunder of the side to move at i --, -1 otherwise and for every row that is not late
+ *   target_agrees_dev  int8 [n]: 1 if the row is late, outcome[i] is known and equals results[g]; else 0
+ *   by_ply_dev         int64 [42][7], indexed by the position's age, columns C4_REVIEW_*: late rows, rows with a known outcome,
+ *                      rows with a known kept, kept, blunders (kept + blunders = kept_known), target_agrees, and
+ *                      contradictions: blunders that change the outcome in the mover's FAVOUR, which best play rules out --
+ *                      a tripwire for the solver, zero unless it is wrong
+ *   per_game_dev       int32 [n_games][4], columns C4_REVIEW_GAME_*: late rows, rows with a known kept, blunders, and the age
+ *                      of the last blunder (-1: none)
+ *   exact_targets_dev  float32 [n], optional (then targets_in_dev float32 [n] is read): 0.5f * outcome[i] for a late row with
+ *                      a known outcome -- Result's value: 1.0 o win, 0.5 draw, 0.0 x win --, targets_in_dev[i] for every other
+ *   exact_priors_dev   float32 [n][7], optional (then keep_dev uint8 [n][7], the moves that keep the outcome, keep_known_dev
+ *                      uint8 [n], 1 where that mask is known, and policy_in_dev float32 [n][7] are read): uniform over the
+ *                      keeping moves of a late row whose mask is known and not empty, policy_in_dev[i] for every other
+ * The chain is checked, not trusted: a row must be an undecided position, its game_index within 0..n_games-1, results[g]
+ * within -1..2, its move a playable column, and the position after the move (c4_board.h make_move) must equal row i + 1
+ * exactly or, behind a game's last row, be finished -- with the result results[g] where that is not -1.  Rows that fail
+ * are counted in chain_errors_dev int32 [1] and take no part in the aggregates; first_error_dev int32 [1] (optional) is the
+ * smallest such row, INT32_MAX if there is none.  A batch with chain errors has no answer: the caller discards the
+ * outputs.  The fold zeroes its aggregates first (one more launch); n and 4 * n_games must fit 32 bits. */
+#define C4_REVIEW_PLIES 42
+#define C4_REVIEW_COLUMNS 7
+#define C4_REVIEW_LATE 0
+#define C4_REVIEW_OUTCOME_KNOWN 1
+#define C4_REVIEW_KEPT_KNOWN 2
+#define C4_REVIEW_KEPT 3
+#define C4_REVIEW_BLUNDERS 4
+#define C4_REVIEW_TARGET_AGREES 5
+#define C4_REVIEW_CONTRADICTIONS 6
+#define C4_REVIEW_GAME_COLUMNS 4
+#define C4_REVIEW_GAME_LATE 0
+#define C4_REVIEW_GAME_KEPT_KNOWN 1
+#define C4_REVIEW_GAME_BLUNDERS 2
+#define C4_REVIEW_GAME_LAST_BLUNDER_AGE 3
+int c4_review_select_dev(int device, void *hip_stream, const int64_t *boards_dev, int64_t n, int max_empties, uint8_t *late_dev);
+int c4_review_outcomes_dev(int device, void *hip_stream, const int64_t *boards_dev, const uint8_t *late_dev, const int64_t *row_of_dev, int64_t n,
+                           const int8_t *searched_status_dev, const int8_t *searched_score_dev, const int64_t *searched_nodes_dev, int64_t m,
+                           int8_t *status_dev, int8_t *outcome_dev, int64_t *nodes_dev);
+int c4_review_fold_dev(int device, void *hip_stream, const int64_t *boards_dev, const uint8_t *moves_dev, const int32_t *game_index_dev,
+                       const int8_t *results_dev, int64_t n, int64_t n_games, const int8_t *outcome_dev, const uint8_t *late_dev,
+                       const float *targets_in_dev, int8_t *kept_dev, int8_t *target_agrees_dev, int64_t *by_ply_dev, int32_t *per_game_dev,
+                       int32_t *chain_errors_dev, int32_t *first_error_dev, float *exact_targets_dev, const uint8_t *keep_dev,
+                       const uint8_t *keep_known_dev, const float *policy_in_dev, float *exact_priors_dev);
+
 int c4_abi_version(void);
 
 #ifdef __cplusplus
