@@ -33,6 +33,7 @@ SOLVE_NODE_INTERIOR, SOLVE_NODE_SELF, SOLVE_NODE_ANSWERED, SOLVE_NODE_OVER_BUDGE
 SOLVE_GRAPH_MAX_PLIES = 8
 SOLVE_DEFAULT_NODES_PER_LAUNCH = 1 << 14
 REVIEW_COLUMNS = ("late", "outcome_known", "kept_known", "kept", "blunders", "target_agrees", "contradictions")     # C4_REVIEW_*
+EXACT_LEAVES_COLUMNS = ("overridden", "over_budget", "nodes", "late")                                               # C4_EXACT_LEAVES_*
 REVIEW_GAME_COLUMNS = ("n_late", "n_kept_known", "n_blunders", "last_blunder_age")                                  # C4_REVIEW_GAME_*
 
 
@@ -238,6 +239,7 @@ SIGNATURES = {
     "c4_review_select_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "c4_review_outcomes_dev": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3),
     "c4_review_fold_dev": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64] + [C.c_void_p] * 14),
+    "c4_exact_leaves_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

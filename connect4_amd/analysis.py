@@ -16,6 +16,7 @@ from .board import Board
 from .config import MCTSConfig
 from .engine import Engine, check_packed_boards
 from .evaluators import DeviceNetEvaluator, evaluate_centre_with_prior, unwrap
+from .fused_net import has_net_handle
 from .tree import Tree
 
 __all__ = ["search_positions", "run_queue", "trees", "pack_boards"]
@@ -107,9 +108,9 @@ def run_queue(config: MCTSConfig, boards, evaluator, n_slots: Optional[int] = No
             ages = packed[2]
         tapes = _draw_tapes(config, ages)
 
-    bits = kind == "device" and bool(getattr(dev_eval.net, "from_bitboards", False))
-    use_fused = bits if fused is None else bool(fused)
-    if use_fused and not bits:
+    handle = kind == "device" and has_net_handle(dev_eval.net)      # the fused kernels take a c4_net handle (an ExactLeafNet has none)
+    use_fused = handle if fused is None else bool(fused)
+    if use_fused and not handle:
         raise ValueError("the fused kernels need a DeviceNetEvaluator over a FusedNet")
     f32 = True
     if kind == "centre":

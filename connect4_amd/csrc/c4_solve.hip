@@ -1,5 +1,6 @@
 // c4_solve.hip -- exact values of positions by alpha-beta on gfx950, behind c4_solve / c4_solve_deep / c4_solve_window, their
-// _dev twins, the c4_solve_table_* calls, c4_solve_children_dev and the c4_review_*_dev calls of include/c4_engine.h.
+// _dev twins, the c4_solve_table_* calls, c4_solve_children_dev, the c4_review_*_dev calls and c4_exact_leaves_dev of
+// include/c4_engine.h.
 //
 // The answer is the one the reference's GridSearch(plies >= empty squares) computes exhaustively
 // (oinkoink/grid_search.py:38-71: no evaluator is reached, the terminal scoring prefers faster wins and
@@ -35,7 +36,8 @@
 //   * the frame depth MAXP.  k_solve_search<MAX_PLY, NoTable> (c4_solve, c4_solve_dev) has 24 plies of frames: 2 x 24 x 64
 //     x 4 B = 12 KiB of LDS a one-wave workgroup, thirteen workgroups a CU, rows with more empty squares are TOO_DEEP.
 //     k_solve_search<DEEP_MAX_PLY, TableRef> (c4_solve_deep*, c4_solve_window*) has 42: 21 KiB, all frames still in LDS,
-//     seven workgroups a CU, every position.  These two are the only instantiations.
+//     seven workgroups a CU, every position.  These two are the only instantiations; k_exact_leaves (c4_exact_leaves_dev) runs
+//     the first one's search, run_lane<MAX_PLY, LdsStack, NoTable>, without parking.
 //   * the table T.  NoTable compiles no table, hit-count or window code.  A TableRef is a transposition table in device
 //     memory that every lane of every launch of every call shares, or none (e == nullptr: the table-free deep search).
 //   * the root window (c4_solve_window*, a Window of per-row arrays): alpha < beta on the mover's score instead of the
@@ -693,6 +695,81 @@ __global__ void __launch_bounds__(BLOCK) k_solve_search(const int64_t *__restric
         if (p < L.d) {
             w.stk_moves[(int64_t)p * w.n + row] = s_moves[p][threadIdx.x];
             w.stk_ab[(int64_t)p * w.n + row] = s_ab[p][threadIdx.x];
+        }
+    }
+}
+
+// -- exact values over a leaf batch (c4_exact_leaves_dev) --------------------------------------------------------------------
+// One launch between the network and the next tree step: the late rows of a leaf batch -- classify says searchable, at most
+// max_empties empty squares -- are searched table-free from the window (-1, +1) by run_lane<MAX_PLY, LdsStack, NoTable>, the
+// search of k_solve_search<MAX_PLY, NoTable>, and an answered row's value becomes who wins.  Nothing is parked: the quota of
+// the one run_lane call is the whole budget less the root, so a lane ends answered or over budget, and the loop bound is
+// run_lane's own 3 * quota + 64.
+//
+// A workgroup is LEAF_WAVES waves over LEAF_WAVES x 64 consecutive rows, each wave with a stack of its own (k_solve_search's
+// 12 KiB).  Late rows are few for most of a game, so they are packed before the search: every lane classifies its row, the
+// waves' ballots give each late row a dense place in s_rows (two barriers, which every lane of the workgroup reaches before
+// any leaves), lanes 0..m-1 search s_rows[lane] and the waves behind m leave.  After the second barrier no lane waits for
+// another.  The counters are reduced over the wave (ballots, one shuffle tree for the nodes) and added once a wave with 64-bit
+// integer atomics: exact sums, whatever the grid.
+constexpr int LEAF_WAVES = 4;
+constexpr int LEAF_BLOCK = LEAF_WAVES * BLOCK;
+
+__global__ void __launch_bounds__(LEAF_BLOCK) k_exact_leaves(const uint64_t *__restrict__ color0, const uint64_t *__restrict__ color1, int32_t n,
+                                                             int max_empties, int64_t node_budget, float *__restrict__ values,
+                                                             unsigned long long *__restrict__ counters)
+{
+    __shared__ uint32_t s_moves[LEAF_WAVES][MAX_PLY][BLOCK];
+    __shared__ uint32_t s_ab[LEAF_WAVES][MAX_PLY][BLOCK];
+    __shared__ int32_t s_rows[LEAF_BLOCK];
+    __shared__ int32_t s_count[LEAF_WAVES];
+    const int tid = (int)threadIdx.x, wave = tid / BLOCK, lane = tid % BLOCK;
+    const int64_t mine = (int64_t)blockIdx.x * LEAF_BLOCK + tid;
+    bool late = false;
+    if (mine < n) {
+        int o, fa;
+        late = classify(color0[mine], color1[mine], o, fa, max_empties) == C4_SOLVE_SOLVED;
+    }
+    const unsigned long long ballot = __ballot(late);
+    if (lane == 0) s_count[wave] = __popcll(ballot);
+    __syncthreads();
+    int base = 0, m = 0;
+#pragma unroll
+    for (int w = 0; w < LEAF_WAVES; ++w) {
+        const int c = s_count[w];
+        base += w < wave ? c : 0;
+        m += c;
+    }
+    if (late) s_rows[base + __popcll(ballot & ((1ULL << lane) - 1))] = (int32_t)mine;     // base + rank < m <= LEAF_BLOCK
+    __syncthreads();
+    if (wave * BLOCK >= m) return;      // the same in every lane of the wave
+    const bool work = tid < m;
+    int64_t nodes = 0;
+    bool answered = false;
+    if (work) {
+        const int32_t row = s_rows[tid];        // a late row of this workgroup: 0 <= row < n
+        const uint64_t c0 = color0[row], c1 = color1[row];
+        LdsStack stk{s_moves[wave], s_ab[wave], lane};
+        Lane L;
+        enter_root(c0, c1, L, -1, 1);
+        nodes = 1;                              // the root is node 1, as in k_solve_init
+        if (!L.done && node_budget > 1) nodes += run_lane<MAX_PLY>(L, stk, NoTable{}, node_budget - 1);
+        if (L.done) {                           // else: it would take a node beyond the budget to go on
+            const int sign = L.ret > 0 ? 1 : L.ret < 0 ? -1 : 0;
+            values[row] = 0.5f * (float)(((popc64(c0 | c1) & 1) ? -sign : sign) + 1);       // o moves at even ages
+            answered = true;
+        }
+    }
+    if (counters) {
+        const unsigned long long n_work = __popcll(__ballot(work)), n_answered = __popcll(__ballot(answered));
+        long long sum = (long long)nodes;
+#pragma unroll
+        for (int off = BLOCK / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, BLOCK);
+        if (lane == 0) {
+            atomicAdd(&counters[C4_EXACT_LEAVES_OVERRIDDEN], n_answered);
+            atomicAdd(&counters[C4_EXACT_LEAVES_OVER_BUDGET], n_work - n_answered);
+            atomicAdd(&counters[C4_EXACT_LEAVES_NODES], (unsigned long long)sum);
+            atomicAdd(&counters[C4_EXACT_LEAVES_LATE], n_work);
         }
     }
 }
@@ -1758,6 +1835,23 @@ int c4_solve_children_dev(int device, void *hip_stream, const int64_t *boards_de
     if (rc) return rc;
     hipLaunchKernelGGL(k_solve_children, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, boards_dev, n,
                        children_dev, legal_dev);
+    SOLVE_CHECK(hipGetLastError());
+    return C4_OK;
+}
+
+int c4_exact_leaves_dev(int device, void *hip_stream, const uint64_t *color0_dev, const uint64_t *color1_dev, int32_t n, int max_empties,
+                        int64_t node_budget, float *values_dev, int64_t *counters_dev)
+{
+    if (n < 0) { set_solve_err("n < 0"); return C4_EINVAL; }
+    if (max_empties < 0 || max_empties > MAX_EMPTIES) { set_solve_err("max_empties %d outside 0..%d", max_empties, MAX_EMPTIES); return C4_EINVAL; }
+    if (node_budget < 1) { set_solve_err("node_budget must be at least 1"); return C4_EINVAL; }
+    if (!color0_dev || !color1_dev || !values_dev) { set_solve_err("null argument"); return C4_EINVAL; }
+    if (n == 0 || max_empties == 0) return C4_OK;       // no row can be late: nothing is launched
+    if (node_budget > ((int64_t)1 << 40)) node_budget = (int64_t)1 << 40;       // run_lane's loop bound is 3 * quota + 64
+    int rc = pick_device(device);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_exact_leaves, dim3((unsigned)(((int64_t)n + LEAF_BLOCK - 1) / LEAF_BLOCK)), dim3(LEAF_BLOCK), 0, (hipStream_t)hip_stream,
+                       color0_dev, color1_dev, n, max_empties, node_budget, values_dev, (unsigned long long *)counters_dev);
     SOLVE_CHECK(hipGetLastError());
     return C4_OK;
 }

@@ -134,6 +134,12 @@ class FusedNet:
             pass
 
 
+def has_net_handle(net) -> bool:
+    """True for a bitboard net the fused kernels can call (a FusedNet: a c4_net handle).  Any other net -- a PyTorch net fed
+    through planes, an ExactLeafNet -- is evaluated between two c4_step launches."""
+    return bool(getattr(net, "from_bitboards", False)) and getattr(net, "_h", None) is not None
+
+
 def make_selfplay_net(state_dict, device: int = 0, precision: Optional[str] = None):
     """The fastest evaluator this build has for a checkpoint at the requested precision: the fused MFMA forwards for 32
     filters (the reference's default, config.py:8-12; reference precision "f32x3" unless "f16" is asked for) and for

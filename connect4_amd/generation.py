@@ -11,7 +11,9 @@ the net of ten generations ago -- inside the fused kernel (connect4_amd.match.De
 evaluate_centre_with_prior on the host lock-step Match, and appends the result to save_dir/match_results.pkl.  Visdom
 stays with the reference's loop.  Not in the reference: with `review_empties` rank 0 reviews the generation's games against
 exact play (connect4_amd/review.py) before the training tensors are built, appends the summary to save_dir/review.pkl and,
-with `exact_targets`, trains on the exact value of every solved late position instead of the game's result (opt-in).
+with `exact_targets`, trains on the exact value of every solved late position instead of the game's result (opt-in).  With `exact_leaves` the self-play net is
+wrapped in an ExactLeafNet (connect4_amd/exact_leaves.py): the search itself scores late leaves with the solver, on the step
+path instead of the fused kernel (opt-in).
 """
 import os
 import pickle
@@ -37,7 +39,8 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
                    seed: int = 0, device: int = 0, n_slots: Optional[int] = None, write_games_pkl: bool = False,
                    timings: Optional[dict] = None, precision: Optional[str] = None, test_sets: Optional[dict] = None,
                    train_stats: bool = False, match_every: Optional[int] = None, match_plies: int = 1,
-                   review_empties: Optional[int] = None, review_table=None, exact_targets: bool = False):
+                   review_empties: Optional[int] = None, review_table=None, exact_targets: bool = False,
+                   exact_leaves: Optional[int] = None, exact_leaf_budget: Optional[int] = None):
     """Returns (PackedGames of all ranks, last_loss).  With torch.distributed initialised every rank plays its shard and
     all ranks receive all games.  There is ONE model, as in the reference (training.py:147-153, model.py:143-147): rank 0
     writes save_dir/<gen>/{data.pth, games.pkl} (storage.py:15-16, data.py:47-64), trains on `trainer.device` over the
@@ -49,14 +52,17 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
     loops over run_generation passes LabelledSets (load_test_sets once); run_generations loads each path once.
     `match_every` / `match_plies`: see generation_match (rank 0, after the checkpoint, when gen % match_every == 0).
     `review_empties` / `review_table` / `exact_targets`: see review_generation (rank 0, after the games are gathered and
-    before the training tensors are built; no collective).  The games returned are the games as played."""
+    before the training tensors are built; no collective).  The games returned are the games as played.
+    `exact_leaves` / `exact_leaf_budget`: see _self_play; timings["exact_leaves"] holds this rank's counters."""
     import torch
     _check_review_args(review_empties, exact_targets)
+    _check_exact_leaf_args(exact_leaves, exact_leaf_budget)
     multi, rank = _ranks()
     test_sets = load_test_sets(test_sets, trainer.device) if rank == 0 else None
     earlier = existing_window(save_dir, gen) if (save_dir is not None and rank == 0) else []
     t0 = time.perf_counter()
-    games = _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision)
+    leaf_counters = {}
+    games = _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision, exact_leaves, exact_leaf_budget, leaf_counters)
     t1 = time.perf_counter()
     loss, rows = None, 0
     t2 = t1
@@ -84,6 +90,8 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
                        positions=int(games.n_positions), training_rows=rows)
         if review is not None:
             timings.update(review)
+        if exact_leaves is not None:
+            timings["exact_leaves"] = leaf_counters
     if rank == 0:
         _report(trainer, test_sets, train_stats, save_dir, gen, timings)
         if match_every and gen % match_every == 0:
@@ -98,12 +106,27 @@ def _ranks():
     return multi, (dist.get_rank() if dist.is_initialized() else 0)
 
 
-def _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision):
-    """Every rank plays its shard with the trainer's current weights; all ranks receive all games (finished on return)."""
+def _check_exact_leaf_args(exact_leaves, exact_leaf_budget):
+    if exact_leaf_budget is not None and exact_leaves is None:
+        raise ValueError("exact_leaf_budget is the budget of exact_leaves: give exact_leaves")
+
+
+def _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision, exact_leaves=None, exact_leaf_budget=None,
+               leaf_counters=None):
+    """Every rank plays its shard with the trainer's current weights; all ranks receive all games (finished on return).
+    exact_leaves=E: the net is wrapped in ExactLeafNet(net, E, exact_leaf_budget or its default), so the shard is played on
+    the step path -- c4_step, forward, overlay, captured in a graph -- instead of the fused kernel, and `leaf_counters`
+    (a dict) receives max_empties, node_budget and this rank's counters().  None: nothing changes."""
     import torch
     net = make_selfplay_net(trainer.net.state_dict(), device=device, precision=precision)   # weights are fixed within a generation
     try:
-        games = generate_games_sharded_packed(config, net, n_games, seed=seed + 1000 * gen, device=device, n_slots=n_slots)
+        player = net
+        if exact_leaves is not None:
+            from .exact_leaves import DEFAULT_NODE_BUDGET, ExactLeafNet
+            player = ExactLeafNet(net, exact_leaves, DEFAULT_NODE_BUDGET if exact_leaf_budget is None else exact_leaf_budget)
+        games = generate_games_sharded_packed(config, player, n_games, seed=seed + 1000 * gen, device=device, n_slots=n_slots)
+        if exact_leaves is not None and leaf_counters is not None:
+            leaf_counters.update(max_empties=player.max_empties, node_budget=player.node_budget, **player.counters())
     finally:
         if hasattr(net, "close"):
             net.close()
@@ -286,7 +309,8 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
                     first_gen: Optional[int] = None, seed: int = 0, device: int = 0, n_slots: Optional[int] = None,
                     precision: Optional[str] = None, write_games_pkl: bool = False, timings: Optional[list] = None,
                     test_sets: Optional[dict] = None, train_stats: bool = False, match_every: Optional[int] = None,
-                    match_plies: int = 1, review_empties: Optional[int] = None, review_table=None, exact_targets: bool = False):
+                    match_plies: int = 1, review_empties: Optional[int] = None, review_table=None, exact_targets: bool = False,
+                    exact_leaves: Optional[int] = None, exact_leaf_budget: Optional[int] = None):
     """n_generations generations of run_generation -- same seeds (seed + 1000 * gen), same files (data.pth, net.pth,
     optional games.pkl), same broadcast of the trained state -- with the sliding window (data.py:66-75) kept on rank 0's GPU
     as packed positions (replay.ReplayWindow): each generation's games are appended to it and trained with
@@ -302,10 +326,11 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
     to save_dir/<name>.pkl) the sets' names and train_stats, and with `match_every` (generation_match on rank 0 after the
     checkpoint of every generation with gen % match_every == 0; save_dir/match_results.pkl) "match", and with `review_empties`
     (review_generation, as run_generation; with `exact_targets` the window's segment carries the exact targets) "review" and
-    "review_s".  Returns (the window -- None on other ranks --, [last loss of each generation])."""
+    "review_s", and with `exact_leaves` (as run_generation) "exact_leaves".  Returns (the window -- None on other ranks --, [last loss of each generation])."""
     import torch
     from .replay import ReplayWindow
     _check_review_args(review_empties, exact_targets)
+    _check_exact_leaf_args(exact_leaves, exact_leaf_budget)
     multi, rank = _ranks()
     os.makedirs(save_dir, exist_ok=True)
     test_sets = load_test_sets(test_sets, trainer.device) if rank == 0 else None
@@ -322,7 +347,8 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
     losses = []
     for gen in range(first_gen, first_gen + n_generations):
         t0 = time.perf_counter()
-        games = _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision)
+        leaf_counters = {}
+        games = _self_play(trainer, config, n_games, seed, gen, device, n_slots, precision, exact_leaves, exact_leaf_budget, leaf_counters)
         t1 = time.perf_counter()
         loss, rows, nbytes = None, 0, 0
         t2 = t1
@@ -345,6 +371,8 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
                       positions=int(games.n_positions), training_rows=rows, window_rows=rows, window_bytes=nbytes)
         if review is not None:
             report.update(review)
+        if exact_leaves is not None:
+            report["exact_leaves"] = leaf_counters
         if rank == 0:
             _report(trainer, test_sets, train_stats, save_dir, gen, report)
             if match_every and gen % match_every == 0:

@@ -17,6 +17,7 @@ import torch
 from . import _lib as L
 from .config import MCTSConfig
 from .engine import Engine
+from .fused_net import has_net_handle
 from .training_game import GameData, game_data_from_record
 
 _PLANES = {torch.float32: L.PLANES_F32, torch.float16: L.PLANES_F16, torch.bfloat16: L.PLANES_BF16}
@@ -50,7 +51,8 @@ class SelfPlay:
         self._pipeline = 2 if (pipeline == 2 and self._bits and n_slots % 16 == 0) else 1
         self._streams = None
         # fused_loop: tree step + network in ONE persistent kernel (c4_selfplay_steps), no graph needed
-        self._fused_loop = bool(fused_loop and self._bits)
+        # (it takes a c4_net handle: a net without one -- an ExactLeafNet -- plays on the step path, graph included)
+        self._fused_loop = bool(fused_loop and self._bits and has_net_handle(net))
         self._steps_per_launch = max(1, steps_per_launch)
         self._leaf_c0, self._leaf_c1, _ = self.engine.leaf_buffers()
         self.steps_done = 0
@@ -164,7 +166,7 @@ class SelfPlay:
 
 def _play_to_completion(config, net, n_games, n_slots, seed, device, planes_dtype, poll_steps, use_graph, timeout_s):
     n_slots = min(n_games, n_slots or 4096)
-    fused = bool(getattr(net, "from_bitboards", False))
+    fused = has_net_handle(net)
     sp = SelfPlay(net, n_slots, config, seed=seed, device=device, games_target=n_games,
                   record_capacity_games=n_games, planes_dtype=planes_dtype, use_graph=use_graph,
                   fused_loop=fused, max_inner_iters=32 if fused else 8)

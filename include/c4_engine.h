@@ -881,6 +881,29 @@ int c4_review_fold_dev(int device, void *hip_stream, const int64_t *boards_dev, 
                        int32_t *chain_errors_dev, int32_t *first_error_dev, float *exact_targets_dev, const uint8_t *keep_dev,
                        const uint8_t *keep_known_dev, const float *policy_in_dev, float *exact_priors_dev);
 
+/* -- exact values over a leaf batch: the solver laid over the net (c4_solve.hip) ------------------------------------------- */
+/* The rows are a leaf batch in the layout of c4_leaf_buffers / c4_net_forward: color0_dev, color1_dev uint64 [n], values_dev
+ * float32 [n] as the network has just written them.  A row is late when it is an undecided position (C4_SOLVE_SOLVED before
+ * any search) with at most max_empties empty squares.  Every late row is searched table-free from the window (-1, +1) for at
+ * most node_budget nodes -- c4_solve_window_dev's rule: the root is node 1, a row that would need a node beyond the budget
+ * has no answer, and the node count is c4_solve_window_dev's table-free count -- and an answered row's values_dev[i] becomes
+ * 1.0f (o wins), 0.5f (draw) or 0.0f (x wins): the evaluator's convention, from o's side whoever moves.  Every other row
+ * keeps its values_dev[i] bit for bit: more empty squares, a finished position, a row that is no position (a zero or stale
+ * leaf row), a late row over budget.  Nothing else is written; priors are not an argument.
+ * counters_dev int64 [4] (optional), columns C4_EXACT_LEAVES_*: the call ADDS rows overridden, late rows over budget, nodes
+ * entered and late rows (overridden + over budget) to what is there -- integer atomics, reduced over a wave first, so the
+ * sums are exact; the caller clears them.
+ * One launch on hip_stream; no allocation, no copy, no wait: the call can be captured in a HIP graph.  max_empties is
+ * 0..C4_SOLVE_MAX_EMPTIES, and 0 launches nothing; node_budget is at least 1 (above 2^40 it is 2^40).  n < 0, a value outside
+ * these ranges or a null color0_dev, color1_dev or values_dev: C4_EINVAL.  Messages: c4_solve_last_error().
+ * (An addition: C4_ABI_VERSION stays.) */
+#define C4_EXACT_LEAVES_OVERRIDDEN 0
+#define C4_EXACT_LEAVES_OVER_BUDGET 1
+#define C4_EXACT_LEAVES_NODES 2
+#define C4_EXACT_LEAVES_LATE 3
+int c4_exact_leaves_dev(int device, void *hip_stream, const uint64_t *color0_dev, const uint64_t *color1_dev, int32_t n, int max_empties,
+                        int64_t node_budget, float *values_dev, int64_t *counters_dev);
+
 int c4_abi_version(void);
 
 #ifdef __cplusplus
