@@ -119,6 +119,14 @@ class ExportBuffers(C.Structure):
 
 
 WINDOW_MAX_SEGMENTS = 64
+WINDOW_MERGE_MAX_POSITIONS = 1 << 23        # C4_WINDOW_MERGE_MAX_POSITIONS
+WINDOW_MERGE_SLOT_BYTES = 80                # C4_WINDOW_MERGE_SLOT_BYTES
+WINDOW_MERGE_BLOCK = 256                    # C4_WINDOW_MERGE_BLOCK
+
+
+def window_merge_work_bytes(n: int) -> int:
+    """C4_WINDOW_MERGE_WORK_BYTES(n)."""
+    return 4 * (n + (n + WINDOW_MERGE_BLOCK - 1) // WINDOW_MERGE_BLOCK)
 
 
 class WindowSegment(C.Structure):
@@ -172,6 +180,8 @@ SIGNATURES = {
     "c4_window_gather_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "c4_planes_to_boards_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "c4_window_merge_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] +
+                            [C.c_void_p] * 8),
     "c4_window_last_error": (C.c_char_p, []),
     "c4_eval_cache_lookup": (C.c_int, [C.c_void_p, _u64p, _u64p, C.c_int32, _f32p, _f32p, _i32p]),
     "c4_debug_root_noise": (C.c_int, [C.c_int, C.c_uint64, C.c_double, _i64p, _i32p, _i32p, C.c_int32, _f64p, _f64p]),

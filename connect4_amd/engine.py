@@ -469,6 +469,37 @@ def planes_to_boards(planes, stream=0):
     return boards, n_bad
 
 
+def window_merge(segments_ptr, n_segments, n_positions, device, mirror=True, log2_capacity=None, wave_combine=True, stream=0):
+    """c4_window_merge_dev over the window whose segment table is at `segments_ptr`: (boards int64 [n,2], targets
+    float32 [n], policy float32 [n,7], counts int32 [n], heads int32 [2] = (n_distinct, n_bad)), device tensors with
+    room for every position; the first n_distinct rows are the merged window (include/c4_engine.h states the rule).
+    log2_capacity=None: the next power of two at or above 2 n_positions.  wave_combine=False: the plain insert, one
+    lane one set of atomics (the same results; the measured A/B is in profiles/window_merge.json).  The table and
+    work buffers are allocated here; the launches go on `stream` (default: torch's current stream) and nothing is
+    waited for."""
+    import torch
+    dev = torch.device(device)
+    _need_gpu(dev, "window_merge (c4_window_merge_dev)")
+    n = int(n_positions)
+    if log2_capacity is None:
+        log2_capacity = max(2 * n - 1, 0).bit_length()
+    log2_capacity = int(log2_capacity)
+    slots = (1 << log2_capacity) if 0 <= log2_capacity <= 30 and (1 << log2_capacity) >= n else 0      # (refused below: nothing to allocate)
+    table = torch.empty(max(slots, 1) * L.WINDOW_MERGE_SLOT_BYTES, dtype=torch.uint8, device=dev)
+    work = torch.empty(max(L.window_merge_work_bytes(n) // 4, 1), dtype=torch.int32, device=dev)
+    out = (torch.empty((n, 2), dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+           torch.empty((n, 7), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+    heads = torch.empty(2, dtype=torch.int32, device=dev)
+    if not stream:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    _check_window(L.load().c4_window_merge_dev(dev.index or 0, C.c_void_p(stream), C.c_void_p(segments_ptr), int(n_segments), n,
+                                               1 if mirror else 0, 1 if wave_combine else 0, log2_capacity,
+                                               C.c_void_p(table.data_ptr()), C.c_void_p(work.data_ptr()),
+                                               *[C.c_void_p(t.data_ptr()) for t in out], C.c_void_p(heads.data_ptr()),
+                                               C.c_void_p(heads.data_ptr() + 4)))
+    return out + (heads,)
+
+
 def debug_root_noise(seed, alpha, game_id, ply, legal_mask, device=0):
     gid = np.ascontiguousarray(game_id, dtype=np.int64)
     pl = np.ascontiguousarray(ply, dtype=np.int32)

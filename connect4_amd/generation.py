@@ -310,7 +310,8 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
                     precision: Optional[str] = None, write_games_pkl: bool = False, timings: Optional[list] = None,
                     test_sets: Optional[dict] = None, train_stats: bool = False, match_every: Optional[int] = None,
                     match_plies: int = 1, review_empties: Optional[int] = None, review_table=None, exact_targets: bool = False,
-                    exact_leaves: Optional[int] = None, exact_leaf_budget: Optional[int] = None):
+                    exact_leaves: Optional[int] = None, exact_leaf_budget: Optional[int] = None, merge_duplicates: bool = False,
+                    merge_mirror: bool = True):
     """n_generations generations of run_generation -- same seeds (seed + 1000 * gen), same files (data.pth, net.pth,
     optional games.pkl), same broadcast of the trained state -- with the sliding window (data.py:66-75) kept on rank 0's GPU
     as packed positions (replay.ReplayWindow): each generation's games are appended to it and trained with
@@ -326,7 +327,11 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
     to save_dir/<name>.pkl) the sets' names and train_stats, and with `match_every` (generation_match on rank 0 after the
     checkpoint of every generation with gen % match_every == 0; save_dir/match_results.pkl) "match", and with `review_empties`
     (review_generation, as run_generation; with `exact_targets` the window's segment carries the exact targets) "review" and
-    "review_s", and with `exact_leaves` (as run_generation) "exact_leaves".  Returns (the window -- None on other ranks --, [last loss of each generation])."""
+    "review_s", and with `exact_leaves` (as run_generation) "exact_leaves".  With `merge_duplicates` each generation trains on
+    window.merged(mirror=merge_mirror) -- identical positions (and, with merge_mirror, mirror images) as one row with the mean
+    of their targets and priors -- while the unmerged window is the one kept and appended to and data.pth is what it is
+    without the option; `timings` then has "window_distinct" (the merged window's positions; training_rows is twice that) and
+    "merge_s".  Returns (the window -- None on other ranks --, [last loss of each generation])."""
     import torch
     from .replay import ReplayWindow
     _check_review_args(review_empties, exact_targets)
@@ -361,7 +366,12 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
             torch.cuda.synchronize(device)
             t2 = time.perf_counter()
             rows, nbytes = window.rows, window.nbytes
-            loss = trainer.train_window(window, stats=True) if train_stats else trainer.train_window(window)
+            trained_on = window
+            if merge_duplicates:
+                trained_on = window.merged(mirror=merge_mirror)
+                torch.cuda.synchronize(device)
+                merge_report = dict(window_distinct=trained_on.n_positions, training_rows=trained_on.rows, merge_s=time.perf_counter() - t2)
+            loss = trainer.train_window(trained_on, stats=True) if train_stats else trainer.train_window(trained_on)
             _checkpoint(trainer, save_dir, gen)
         if multi:
             loss = trainer.broadcast_state(src=0, extra=loss)
@@ -373,6 +383,8 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
             report.update(review)
         if exact_leaves is not None:
             report["exact_leaves"] = leaf_counters
+        if merge_duplicates and rank == 0:
+            report.update(merge_report)
         if rank == 0:
             _report(trainer, test_sets, train_stats, save_dir, gen, report)
             if match_every and gen % match_every == 0:

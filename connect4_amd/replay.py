@@ -30,6 +30,82 @@ def _same_bits(a, b):
     return a.shape == b.shape and bool(torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)))
 
 
+_BAD_ROWS = ("%d of %d rows cannot be merged: overlapping or floating stones, stones outside the board, or a target or "
+             "prior that is not a finite number in [0, 1]")
+_BOTTOM = 0x40810204081                 # bit 7 c of every column (c4_board.h)
+_BOARD = _BOTTOM * 0x3f                 # the 42 cells
+_FIXED_ONE = 2.0 ** 40
+
+
+def _flip_color(p: int) -> int:
+    return sum(((p >> (7 * c)) & 0x7f) << (7 * (6 - c)) for c in range(7))
+
+
+def _position_key(c0: int, c1: int) -> int:
+    occ = c0 | c1
+    return (c1 if bin(occ).count("1") & 1 else c0) + occ + _BOTTOM
+
+
+def merge_host(boards, targets, policy, mirror: bool = True):
+    """Identical positions merged into one row each -- the rule c4_window_merge_dev computes (include/c4_engine.h), in
+    NumPy with Python integers; no GPU.  boards int64 [n,2], targets float32 [n], policy float32 [n,7] (arrays or
+    tensors).  A position's key is mover's stones + occupied + BOTTOM; with `mirror` a group is keyed by the smaller
+    of that and its mirror image's key, and a member whose own key is the larger one is *reversed*: its priors count
+    for the mirrored columns.  Per group the targets and priors are summed as integers rne(x 2^40) and divided in
+    float64 by count 2^40, rounded to float32; a group of one keeps its row bit for bit.  Groups come in the order of
+    their first members, with that member's board as stored and, if it is reversed, its column order.
+    Returns (boards int64 [g,2], targets float32 [g], policy float32 [g,7], counts int32 [g]); ValueError on bad rows
+    (overlapping stones, stones outside the 42 cells or floating, a target or prior not finite or outside [0, 1])."""
+    import numpy as np
+
+    def host(x, dtype):
+        return np.ascontiguousarray((x.detach().cpu() if hasattr(x, "detach") else x), dtype=dtype)
+    b, t, p = host(boards, np.int64), host(targets, np.float32), host(policy, np.float32)
+    n = int(b.shape[0])
+    if b.shape != (n, 2) or t.shape != (n,) or p.shape != (n, 7):
+        raise ValueError("merge_host takes (boards int64 [n,2], targets float32 [n], policy float32 [n,7])")
+    if n >= L.WINDOW_MERGE_MAX_POSITIONS:
+        raise ValueError("%d positions: the merge's int64 sums hold fewer than %d" % (n, L.WINDOW_MERGE_MAX_POSITIONS))
+    tp = np.concatenate([t[:, None], p], axis=1)
+    with np.errstate(invalid="ignore"):
+        in_range = np.all((tp >= 0) & (tp <= 1), axis=1)                    # (False for NaN and inf)
+        fixed = np.rint(tp.astype(np.float64) * _FIXED_ONE)                 # rne(x 2^40), exact in float64
+    groups, order, n_bad = {}, [], 0        # group key -> [count, sums[8], first index, first is reversed]
+    for i, (c0, c1) in enumerate(b.view(np.uint64).tolist()):
+        occ = c0 | c1
+        if (c0 & c1) or (occ & ~_BOARD) or (occ & (occ + _BOTTOM)) or not in_range[i]:
+            n_bad += 1
+            continue
+        key = _position_key(c0, c1)
+        mkey = _position_key(_flip_color(c0), _flip_color(c1))
+        reversed_ = bool(mirror) and key > mkey
+        v = [int(x) for x in fixed[i]]
+        if reversed_:
+            key, v = mkey, v[:1] + v[:0:-1]
+        g = groups.get(key)
+        if g is None:
+            groups[key] = [1, v, i, reversed_]
+            order.append(key)
+        else:
+            g[0] += 1
+            g[1] = [x + y for x, y in zip(g[1], v)]
+    if n_bad:
+        raise ValueError(_BAD_ROWS % (n_bad, n))
+    m = len(order)
+    ob, ot, op, oc = np.empty((m, 2), np.int64), np.empty(m, np.float32), np.empty((m, 7), np.float32), np.empty(m, np.int32)
+    for r, key in enumerate(order):
+        count, sums, first, reversed_ = groups[key]
+        ob[r], oc[r] = b[first], count
+        if count == 1:
+            ot[r], op[r] = t[first], p[first]
+            continue
+        if reversed_:
+            sums = sums[:1] + sums[:0:-1]
+        mean = [np.float32(np.float64(s) / (np.float64(count) * _FIXED_ONE)) for s in sums]
+        ot[r], op[r] = mean[0], mean[1:]
+    return ob, ot, op, oc
+
+
 class ReplayWindow:
     def __init__(self, device=None):
         import torch
@@ -42,6 +118,8 @@ class ReplayWindow:
         self._active: List[int] = []    # the selected generations, newest first
         self._table = None          # device bytes of c4_window_segment[WINDOW_MAX_SEGMENTS]: ONE allocation for the window's life,
         self._counter = None        # so a captured graph that gathers from the window sees a fixed pointer
+        self.merge_counts = None    # of a window that merged() made: int32 [n_positions], the members of every row,
+        self.merged_from = None     # and the number of positions that went in
 
     # -- contents --------------------------------------------------------------------------------
     def append(self, gen: int, games_or_tensors):
@@ -176,6 +254,38 @@ class ReplayWindow:
                 if bad:
                     raise IndexError("%d of %d indices are outside the window's %d rows" % (bad, m, self.rows))
         return out
+
+    # -- duplicates ------------------------------------------------------------------------------
+    def merged(self, mirror: bool = True, log2_capacity: Optional[int] = None):
+        """A new one-segment ReplayWindow on the same device, labelled with the newest active generation, in which
+        identical positions of this window (with `mirror`: and their left-right mirror images) are one row carrying the
+        mean of their targets and priors -- merge_host's rule, computed by c4_window_merge_dev.  The result also has
+        ``merge_counts`` (int32 [rows/2]: members per row) and ``merged_from`` (the positions that went in); gather and
+        Trainer.train_window take it as any window.  `log2_capacity`: log2 of the hash table's slots (default: the next
+        power of two at or above 2 n_positions; below n_positions is refused).  This window is left untouched.  One
+        host synchronisation (the number of distinct positions); ValueError when the window holds bad rows."""
+        import torch
+        from . import engine as _engine
+        if self.device.type != "cuda":
+            raise RuntimeError(_NO_CPU % ("merged", "c4_window_merge_dev"))
+        if not self._active:
+            raise RuntimeError("the window is empty: append() generations and select() one first")
+        n = self.n_positions
+        if n >= L.WINDOW_MERGE_MAX_POSITIONS:
+            raise ValueError("%d positions: the merge's int64 sums hold fewer than %d" % (n, L.WINDOW_MERGE_MAX_POSITIONS))
+        with torch.cuda.device(self.device):
+            boards, targets, policy, counts, heads = _engine.window_merge(self._table.data_ptr(), len(self._active), n, self.device,
+                                                                          mirror, log2_capacity)
+            n_distinct, n_bad = heads.tolist()
+        if n_bad:
+            raise ValueError(_BAD_ROWS % (n_bad, n))
+        w = ReplayWindow(self.device)
+        gen = self._active[0]
+        w.append(gen, (boards[:n_distinct].clone(), targets[:n_distinct].clone(), policy[:n_distinct].clone()))
+        w._activate([gen])
+        w.merge_counts = counts[:n_distinct].clone()
+        w.merged_from = n
+        return w
 
     # -- from disk -------------------------------------------------------------------------------
     @classmethod

@@ -350,6 +350,34 @@ int c4_window_gather_dev(int device, void *hip_stream, const c4_window_segment *
  * parity of the stone count.  For data.pth files the library did not write.  One launch on hip_stream. */
 int c4_planes_to_boards_dev(int device, void *hip_stream, const float *planes_dev, int64_t n, int64_t *boards_out,
                             int32_t *n_bad_dev);
+/* Identical positions of the window merged into one row each, carrying the mean of their targets and priors.
+ * Input: the n_positions positions of the n_segments segments in table order, as stored (mirror rows are no inputs);
+ * n_positions must be the table's total -- a position the table does not hold counts as a bad row.
+ *   key       occ = c0 | c1, mover = c1 when popcount(occ) is odd, else c0; key = mover + occ + BOTTOM (c4_solve.hip's
+ *             tt_key), mkey = the key of the left-right mirror image.  With `mirror` the group key is min(key, mkey) and
+ *             a member with key > mkey is REVERSED; without, the group key is key and nobody is reversed.
+ *   bad rows  c0 & c1 != 0, a stone outside the 42 cells, a stone with no stone under it, a target or prior that is not
+ *             finite or outside [0, 1].  They join no group and are counted in *n_bad_dev; the outputs then mean nothing.
+ *   sums      per group a count and eight int64 sums: T = sum rne(target 2^40), P[c] = sum rne(prior[c'] 2^40) with
+ *             c' = 6 - c for a reversed member, else c.  Integer sums: the order of addition does not matter.
+ *             n_positions < C4_WINDOW_MERGE_MAX_POSITIONS keeps every sum below 2^63; else C4_EINVAL.
+ *   output    one row per group, groups in the order of their first members; the board is the first member's as stored;
+ *             target = float32(float64(T) / (float64(count) 2^40)), prior[c] likewise from P[c], or from P[6 - c] when the
+ *             first member is reversed; counts int32.  A group of one copies its target and priors bit for bit.
+ * table_dev: C4_WINDOW_MERGE_SLOT_BYTES << log2_capacity bytes, cleared by the call; 2^log2_capacity < n_positions is
+ * C4_EINVAL (log2_capacity 0..30).  work_dev: C4_WINDOW_MERGE_WORK_BYTES(n_positions) bytes.  The four outputs have room
+ * for n_positions rows; *n_distinct_dev (device int32) says how many were written.  wave_combine != 0 sums equal keys
+ * inside a wave before going to memory: the same results, sooner when many positions repeat (self-play windows).
+ * A few launches and memsets on hip_stream; allocates nothing, waits for nothing.  Messages: c4_window_last_error().
+ * (An addition: C4_ABI_VERSION stays.) */
+#define C4_WINDOW_MERGE_MAX_POSITIONS (1 << 23)
+#define C4_WINDOW_MERGE_SLOT_BYTES 80
+#define C4_WINDOW_MERGE_BLOCK 256
+#define C4_WINDOW_MERGE_WORK_BYTES(n) (4 * ((int64_t)(n) + ((int64_t)(n) + C4_WINDOW_MERGE_BLOCK - 1) / C4_WINDOW_MERGE_BLOCK))
+int c4_window_merge_dev(int device, void *hip_stream, const c4_window_segment *segments_dev, int32_t n_segments,
+                        int64_t n_positions, int32_t mirror, int32_t wave_combine, int32_t log2_capacity, void *table_dev,
+                        void *work_dev, int64_t *boards_out, float *targets_out, float *policy_out, int32_t *counts_out,
+                        int32_t *n_distinct_dev, int32_t *n_bad_dev);
 const char *c4_window_last_error(void);
 
 /* Read-out of the evaluation cache (the memo table of evaluators.py:9-25): what it answers for the given
