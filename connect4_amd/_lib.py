@@ -23,6 +23,7 @@ PRIOR_NONE, PRIOR_F32, PRIOR_F64 = 0, 1, 2
 PV_VALUE, PV_VISITS = 0, 1
 NET_F16, NET_F32X3, NET_F32X3_WIDE = 0, 1, 2   # c4_net_desc.precision
 MATCH_MAX_NETS = 16
+MATCH_KERNEL_WAVE, MATCH_KERNEL_SPLIT = 0, 1   # c4_match_player.kernel
 SOLVE_MAX_EMPTIES = 24
 SOLVE_DEEP_MAX_EMPTIES = 42
 SOLVE_TABLE_MIN_LOG2, SOLVE_TABLE_MAX_LOG2 = 10, 30
@@ -51,6 +52,12 @@ class Config(C.Structure):
                 ("seed", C.c_uint64), ("stop_after_move", C.c_int32), ("games_target", C.c_int64),
                 ("record_capacity_games", C.c_int32), ("max_inner_iters", C.c_int32),
                 ("planes_dtype", C.c_int32), ("eval_cache_log2_entries", C.c_int32), ("level_budget", C.c_int32), ("time_budget_cycles", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class MatchPlayer(C.Structure):
+    """c4_match_player: the player behind one net index of a match engine (c4_match_configure)."""
+    _fields_ = [("simulations", C.c_int32), ("pb_c_base", C.c_int32), ("pb_c_init", C.c_double), ("kernel", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
 
 
 class Stats(C.Structure):
@@ -209,6 +216,7 @@ SIGNATURES = {
     "c4_selfplay_steps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "c4_match_assign": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int32]),
     "c4_match_steps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "c4_match_configure": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MatchPlayer)]),
     "c4_queue_positions": (C.c_int, [C.c_void_p, _u64p, _u64p, C.c_int64]),
     "c4_queue_positions_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "c4_queue_progress": (C.c_int, [C.c_void_p, _i64p, _i64p]),

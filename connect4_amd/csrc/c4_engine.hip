@@ -14,12 +14,13 @@
 //   * score arithmetic reproduces the reference bit-for-bit: float64 everywhere, or NumPy>=2's
 //     float32 path when the prior is a float32 net output (see ucb_score below); log() comes from a
 //     host-built table so device libm never enters the comparison.  Build with -ffp-contract=off;
-//   * five kernels share tree_step(): c4_step_kernel (one rollout step per launch, evaluator outside),
+//   * six kernels share tree_step(): c4_step_kernel (one rollout step per launch, evaluator outside),
 //     c4_selfplay_kernel (workgroup-synchronous tree / network phases in one persistent kernel),
 //     c4_selfplay_wave_kernel (every wave alternates the tree walk of its own slots with the network on
 //     their leaves, no barrier; slot state lives in LDS for the whole launch), c4_match_wave_kernel (the
-//     same with one net per launch: net-vs-net matches) and c4_selfplay_split_kernel (the default: tree
-//     waves and network waves of one workgroup hand leaves and answers over through LDS).
+//     same with one net per launch: net-vs-net matches), c4_selfplay_split_kernel (the default: tree
+//     waves and network waves of one workgroup hand leaves and answers over through LDS) and
+//     c4_match_split_kernel (that one with one net per launch: matches of every net mode).
 //
 // No CUDA-compat headers, no CPU fallback: every entry point needs a HIP device.  One code path: the only
 // build switches are the diagnostic ones below, both off in the library anyone ships.
@@ -2170,6 +2171,269 @@ __global__ __launch_bounds__(c4net::NTHREADS) void c4_selfplay_split_kernel(cons
 }
 
 // ------------------------------------------------------------------------------------------
+// c4_match_split_kernel<TS, MODE, TW>: the split kernel above under the match rule of c4_match_wave_kernel.
+// A launch serves ONE net (nd, d.cache, net_index) and only the slots where that net is to move; `d` has
+// stop_after_move set, and the tree wave that walked a slot to SLOT_MOVE_DONE stages the move, makes it, publishes a
+// finished game and hands the slot over with need_root (the text of c4_match_wave_kernel).  It holds every net mode,
+// the 64-filter reference-precision net included: four network waves' planes fit where eight forwards do not.
+// What differs from c4_selfplay_split_kernel:
+//   - s_perm deals out this launch's slots only (active AND this net to move), so no foreign slot occupies a tree lane;
+//   - a foreign slot -- it may be in the middle of the other net's search, with an answered leaf -- passes through: its
+//     SlotMem, its answer row (the "make carried-over answers finite" step included) and its path row leave as they
+//     came, and its request word stays idle, so no network wave ever claims it;
+//   - a slot that has moved is foreign for the rest of the launch (a move is chosen with no leaf pending: nothing is
+//     outstanding), and a tree wave with no slot left leaves its loop at once.  The network waves drain what was posted
+//     and leave when all tree waves are done, as above: between launches "has a leaf" still means "answered";
+//   - speculative passes follow real answers, which only this net's slots ask for, and fill d.cache, this net's table.
+// The two match kernels are interchangeable launch by launch and net by net: between two nets' turns a slot holds a
+// root and need_root, nothing a kernel keeps to itself.  Dense packing only (grid = ceil(G / TS)).
+// ------------------------------------------------------------------------------------------
+template <int TS, int MODE, int TW>
+__global__ __launch_bounds__(c4net::NTHREADS) void c4_match_split_kernel(const Dev *d_dev, c4net::NetDev nd, float *__restrict__ values,
+                                                                         float *__restrict__ priors, int n_steps,
+                                                                         const uint8_t *__restrict__ side_o, const uint8_t *__restrict__ side_x,
+                                                                         int net_index)
+{
+    using namespace c4net;
+    const_dev &d = *(const_dev *)d_dev;
+    constexpr int NW = NWAVES - TW;           // tree waves, network waves
+    constexpr int SPW = (TS + TW - 1) / TW;   // slots per tree wave (at most)
+    static_assert(TW >= 1 && NW >= 1 && SPW >= 1 && SPW <= 8 && TS <= 64, "slots per workgroup");
+    constexpr int WBUF = WaveBuf<MODE>::HALVES;
+    constexpr bool SPECULATE = MODE == NETMODE_F32_F16;   // as c4_selfplay_split_kernel
+    __shared__ __attribute__((aligned(16))) _Float16 act[NW][WBUF];   // planes of the network waves
+    __shared__ __attribute__((aligned(16))) float4 mlp[MLP_F4];
+    __shared__ SlotMem smem[TS];
+    __shared__ float s_val[TS + NW];        // rows TS..: scratch of the network waves' speculative passes
+    __shared__ float s_pri[(TS + NW) * 7];
+    __shared__ uint32_t s_stats[N_STATS];
+    __shared__ __attribute__((aligned(16))) float s_bias[BIAS_LDS_FLOATS];
+    __shared__ __attribute__((aligned(16))) uint16_t s_tab16[64 * TAB16];
+    __shared__ __attribute__((aligned(16))) half8 s_w0[W0Lds<MODE>::FRAGS];
+    __shared__ __attribute__((aligned(16))) PathEntry s_path[TS][MAX_DEPTH];
+    __shared__ __attribute__((aligned(16))) Rec s_l1[TS][GROUP];
+    __shared__ uint32_t s_req[C4_SPLIT_PHASES ? 3 * TS + 4 : TS];     // REQ_* of the slot's leaf (tree_step's diagnostic build: + times, sums)
+    __shared__ uint32_t s_simd[4];
+    __shared__ uint8_t s_perm[TW * SPW];   // the slot a (tree wave, group) pair walks (0xff: none)
+    __shared__ uint32_t s_tree_done;
+    __shared__ uint8_t s_side[2][TS];      // net that moves o / x in each slot (0xff: no game)
+    static_assert(sizeof(act) + sizeof(mlp) + sizeof(smem) + sizeof(s_val) + sizeof(s_pri) + sizeof(s_stats) + sizeof(s_bias) + sizeof(s_tab16) +
+                  sizeof(s_w0) + sizeof(s_path) + sizeof(s_l1) + sizeof(s_req) + sizeof(s_simd) + sizeof(s_perm) + sizeof(s_side) + 64 <= 160 * 1024,
+                  "the split match kernel's LDS must fit a CU's 160 KiB");
+    const SlotMap slots{(int)blockIdx.x * TS, 1};
+    // ---- launch prologue: as c4_selfplay_split_kernel, plus the slots' player assignment
+    if (threadIdx.x < TS) {
+        const int p = threadIdx.x, g = slots(p);
+        smem[p] = load_slot(&d, g);
+        const bool ok = g < d.G;
+        s_side[0][p] = ok ? side_o[g] : (uint8_t)0xff;
+        s_side[1][p] = ok ? side_x[g] : (uint8_t)0xff;
+    }
+    if (threadIdx.x < N_STATS) s_stats[threadIdx.x] = 0;
+    if (threadIdx.x < 4) s_simd[threadIdx.x] = 0;
+#if C4_SPLIT_PHASES
+    if (threadIdx.x < 4) s_req[3 * TS + threadIdx.x] = 0;
+#endif
+    if (threadIdx.x == 0) s_tree_done = 0;
+    load_answers<TS>(&d, slots, values, priors, s_val, s_pri);   // answers of earlier launches (every net's rows)
+    for (int i = threadIdx.x; i < MLP_F4; i += NTHREADS) mlp[i] = nd.mlp[i];
+    stage_bias_lds(nd, s_bias);
+    if (W0Lds<MODE>::FRAGS > 1) stage_w0_lds(nd, s_w0);
+    if (threadIdx.x < 64) build_tab16<WaveRow<MODE>::CS>(s_tab16, threadIdx.x);
+    for (int i = threadIdx.x; i < TS * MAX_DEPTH; i += NTHREADS) {   // paths of leaves pending from earlier launches
+        const int p = i / MAX_DEPTH, k = i - p * MAX_DEPTH;
+        if (slots(p) < d.G) s_path[p][k] = d.path[(size_t)slots(p) * MAX_DEPTH + k];
+    }
+    __syncthreads();
+    // a slot belongs to this launch iff it has a game and this launch's net is to move in it
+    auto mine = [&](int p) {
+        const SlotMem &m = smem[p];
+        return m.state() == SLOT_ACTIVE && (int)s_side[popc64(m.root0 | m.root1) & 1][p] == net_index;
+    };
+    // This launch's slots, sorted by ply, dealt out to the tree waves in TW contiguous chunks of equal size (+-1), and their
+    // request words: a leaf carried over from this net's previous launch has its answer, every other word is idle.
+    if (threadIdx.x < 64) {
+        const int p = threadIdx.x;
+        if (p < TW * SPW) s_perm[p] = 0xff;
+        const bool own = p < TS && mine(p < TS ? p : 0);
+        const int n_own = __popcll(__builtin_amdgcn_ballot_w64(own));
+        if (own) {
+            const uint32_t kp = smem[p].ply;
+            int rank = 0;
+            for (int q = 0; q < TS; ++q)
+                if (mine(q)) { const uint32_t kq = smem[q].ply; rank += (kq < kp) || (kq == kp && q < p); }
+            const int t = (rank * TW) / n_own;
+            const int first = (t * n_own + TW - 1) / TW;
+            s_perm[t * SPW + (rank - first)] = (uint8_t)p;
+        }
+        if (p < TS) s_req[p] = (own && smem[p].has_leaf()) ? REQ_ANSWERED : REQ_IDLE;
+        // carried-over answers of this launch's slots are made finite (see c4_selfplay_split_kernel); foreign rows are not touched
+        if (own && smem[p].has_leaf()) {
+            bool bad = false;
+            const float v = s_val[p];
+            if (!(v >= 0.0f && v <= 1.0f)) { s_val[p] = 0.5f; bad = true; }
+            for (int k = 0; k < 7; ++k) {
+                const float q = s_pri[p * 7 + k];
+                if (!(q >= 0.0f && q <= 3.0e38f)) { s_pri[p * 7 + k] = 0.0f; bad = true; }
+            }
+            if (bad) atomicAdd(&s_stats[offsetof(SlotStats, bad_evals) / sizeof(uint64_t)], 1u);
+        }
+    }
+    // ---- roles, as c4_selfplay_split_kernel: the first wave to register on a SIMD walks trees
+    const int simd = (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4) & 3;   // HW_REG_HW_ID bits [5:4]
+    int rank = 0;
+    if ((threadIdx.x & 63) == 0) rank = (int)atomicAdd(&s_simd[simd], 1u);
+    rank = __builtin_amdgcn_readfirstlane(rank);
+    __syncthreads();
+    const bool even = (TW == 4 || TW == 3) && s_simd[0] == 2 && s_simd[1] == 2 && s_simd[2] == 2 && s_simd[3] == 2;
+    const int wv = threadIdx.x >> 6;
+    const bool is_tree = even ? (rank == 0 && simd < TW) : wv < TW;
+    const int role_idx = even ? (is_tree ? simd : (TW == 4 ? simd : (rank == 0 ? 4 : simd))) : (wv < TW ? wv : wv - TW);
+    const unsigned long long t_launch = __builtin_amdgcn_s_memtime();
+    const unsigned long long quantum = (unsigned long long)n_steps * (unsigned long long)(d.time_budget > 0 ? d.time_budget : 80000);
+    if (is_tree) {
+        const int tw = role_idx;   // tree wave index
+        while (__builtin_amdgcn_s_memtime() - t_launch < quantum) {
+            int tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));   // keep lane-derived addresses of the call out of the loop's live ranges
+            const int lane = tid & (GROUP - 1);
+            const int grp = (tid & 63) / GROUP;
+            const int sl = grp < SPW ? (int)s_perm[tw * SPW + grp] : 0xff;   // (0xff = no slot: >= TS)
+            const bool own = sl < TS && mine(sl);
+            if (__builtin_amdgcn_ballot_w64(own) == 0) break;   // only this wave's own moves change who is to move in its slots
+            if (own) {
+                // (returns when every slot of the wave has chosen its move, or at the deadline: a slot that waits for the
+                // network does so inside the call)
+                tree_step<C4_EVAL_EXTERNAL_F32, false, true, true, true, const_dev, true, false>(d, slots(sl), lane, sl, s_path, s_l1, s_val, s_pri, nullptr,
+                                                                                          nullptr, &smem[sl], sl, s_stats, t_launch + quantum,
+                                                                                          &s_req[sl], TS);
+                lds_fence();   // the slot state written by the group's first lane
+                SlotMem *m = &smem[sl];
+                if (m->state() == SLOT_MOVE_DONE) {   // mcts.py:78-88 returned a move: match.py:44-50 plays it, the opponent is next
+                    const int g = slots(sl);
+                    uint64_t r0 = m->root0, r1 = m->root1;
+                    const uint32_t ply = m->ply;
+                    const long long gid = m->gid;
+                    // what tree_step's move choice left in the result rows (each lane reads back its own stores)
+                    int mv = 0;
+                    double absv = 0.0, pol = 0.0;
+                    if (lane == 0) { mv = d.cold->res_move[g]; absv = d.cold->res_value[g]; }
+                    if (lane < 7) pol = d.cold->res_policy[(size_t)g * 7 + lane];
+                    mv = gshfl(mv, 0);
+                    if (d.rec_cap > 0) {   // training_game.py:12-15 record (board before the move), staged until the game ends
+                        const size_t r = (size_t)g * 42 + ply;
+                        if (lane == 0) {
+                            d.cold->stg_c0[r] = r0;
+                            d.cold->stg_c1[r] = r1;
+                            d.cold->stg_move[r] = mv;
+                            d.cold->stg_value[r] = absv;
+                        }
+                        if (lane < 7) d.cold->stg_policy[r * 7 + lane] = pol;
+                    }
+                    const uint32_t cst = make_move(r0, r1, mv);   // board.make_move(move)
+                    int state = SLOT_ACTIVE, need_root = 1;
+                    if (cst >= ST_XWIN) {   // game over: the slot's one game is recorded and the slot parks
+                        if (d.rec_cap > 0) publish_game(d, g, gid, (int)ply + 1, (int32_t)(cst - ST_XWIN), lane);
+                        if (lane == 0) atomicAdd(&s_stats[offsetof(SlotStats, games_finished) / sizeof(uint64_t)], 1u);
+                        state = SLOT_PARKED;
+                        need_root = 0;
+                    }
+                    if (lane == 0) {
+                        m->root0 = r0;
+                        m->root1 = r1;
+                        m->ply = ply + 1;
+                        m->flags = SlotMem::pack(state, 0, need_root);
+                    }
+                }
+            }
+            lds_fence();   // the slot states written by the groups' first lanes are read by the whole wave
+        }
+        if ((threadIdx.x & 63) == 0) atomicAdd(&s_tree_done, 1u);
+    } else {
+        const int lw = threadIdx.x & 63;
+        const int nw = role_idx;   // network wave index: its planes, its scratch row
+        // real requests first, then one speculative pass (see c4_selfplay_split_kernel); every request is one of this net's slots
+        bool have_spec = false;
+        uint64_t sc0 = 0, sc1 = 0;
+        for (;;) {
+            const uint32_t done = lds_ld(&s_tree_done);   // read BEFORE the requests: no post can follow a full count
+            const uint32_t r = lw < TS ? lds_ld(&s_req[lw]) : REQ_IDLE;
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(r == REQ_POSTED);
+            int c = -1, row;
+            uint64_t b0, b1;
+            if (m != 0) {
+                // start looking at a different slot on every network wave, so that they do not race for the same request
+                const int rot = (nw * TS) / NW;
+                constexpr unsigned long long ALL = (TS == 64) ? ~0ull : ((1ull << TS) - 1);
+                const unsigned long long mr = ((m >> rot) | (m << (TS - rot))) & ALL;
+                c = __builtin_amdgcn_readfirstlane((__builtin_ctzll(mr) + rot) % TS);
+                int ok = 0;
+                if (lw == 0) ok = atomicCAS(&s_req[c], REQ_POSTED, REQ_TAKEN) == REQ_POSTED;
+                if (!__builtin_amdgcn_readfirstlane(ok)) continue;
+                b0 = smem[c].leaf0;
+                b1 = smem[c].leaf1;
+                row = c;
+            } else if (SPECULATE && have_spec) {
+                have_spec = false;
+                b0 = sc0;
+                b1 = sc1;
+                row = TS + nw;
+            } else {
+                if (done == (uint32_t)TW) break;
+                __builtin_amdgcn_s_sleep(4);
+                continue;
+            }
+            const bool is_spec = c < 0;
+            net_forward_wave1_mode<MODE>(nd, &act[nw][0], mlp, s_bias, s_tab16, b0, b1, s_val, s_pri, row, s_w0, nullptr);
+            lds_fence();   // the answer is in LDS before the request word says so
+            sanitise_answer(s_val, s_pri, row, lw, s_stats);
+            lds_fence();
+            if (is_spec) {
+                if (lw < GROUP) cache_insert(d, b0, b1, lw, s_val[row], lw < 7 ? s_pri[row * 7 + lw] : 0.0f);
+                if (lw == 0) atomicAdd(&s_stats[offsetof(SlotStats, spec_evals) / sizeof(uint64_t)], 1u);
+                continue;
+            }
+            // the answered position's priors, read before the slot may reuse its rows
+            const float ppr = (SPECULATE && lw < 7) ? s_pri[c * 7 + lw] : -1.0f;
+            if (lw == 0) {
+#if C4_SPLIT_PHASES
+                lds_st(&s_req[2 * TS + c], (uint32_t)__builtin_amdgcn_s_memtime());
+#endif
+                lds_st(&s_req[c], REQ_ANSWERED);
+            }
+            if (SPECULATE && d.cache != nullptr) {
+                const uint32_t r2 = lw < TS ? lds_ld(&s_req[lw]) : REQ_IDLE;
+                if (__builtin_amdgcn_ballot_w64(r2 == REQ_POSTED) != 0) continue;   // real work first
+                uint64_t c0 = b0, c1 = b1;
+                int go_spec = 0;
+                if (lw < GROUP) {
+                    const int mask = legal_mask(b0 | b1);
+                    const bool legal = lw < 7 && ((mask >> lw) & 1);
+                    const int kb = group_argmax(legal ? (double)ppr : -1.0, legal ? lw : -1);   // ties: the higher column (tree.py:11-15)
+                    const uint32_t cst = make_move(c0, c1, kb);
+                    float cv, cp;
+                    go_spec = (cst < ST_XWIN && !cache_probe(d, c0, c1, lw, cv, cp)) ? 1 : 0;
+                }
+                go_spec = __builtin_amdgcn_readfirstlane(go_spec);
+                if (!go_spec) continue;
+                sc0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(c0 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)c0);
+                sc1 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(c1 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)c1);
+                have_spec = true;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- launch epilogue: LDS -> global
+    for (int i = threadIdx.x; i < TS * MAX_DEPTH; i += NTHREADS) {   // paths of the leaves of THIS launch whose answers wait for its next one
+        const int p = i / MAX_DEPTH, k = i - p * MAX_DEPTH;
+        if (slots(p) < d.G && smem[p].has_leaf() && mine(p)) d.path[(size_t)slots(p) * MAX_DEPTH + k] = s_path[p][k];
+    }
+    store_slots<TS>(&d, slots, smem);
+    flush_stats(&d, slots, s_stats);
+    store_answers<TS>(&d, slots, values, priors, s_val, s_pri);
+}
+
+// ------------------------------------------------------------------------------------------
 // small kernels
 // ------------------------------------------------------------------------------------------
 __global__ void c4_reset_kernel(Dev d, const uint64_t *c0, const uint64_t *c1, int n_active)
@@ -2524,7 +2788,7 @@ void set_err(char *dst, const char *fmt, ...)
     if (dst != g_err) { strncpy(g_err, dst, 511); g_err[511] = 0; }
 }
 
-enum { FUSED_NONE, FUSED_SPLIT, FUSED_WAVE, FUSED_BLOCK, FUSED_MATCH };   // the four fused kernel families
+enum { FUSED_NONE, FUSED_SPLIT, FUSED_WAVE, FUSED_BLOCK, FUSED_MATCH, FUSED_MATCH_SPLIT };   // the fused kernel families
 // one fused launch as c4_debug_last_fused_kernel reports it; tw < 0 / queue < 0 where the family has no such template argument
 struct FusedLaunch { int family, ts, mode, tw, queue, spread, grid; };
 
@@ -2560,6 +2824,12 @@ struct c4_engine {
     Dev d_match_uploaded;
     uint8_t *match_side_o, *match_side_x;         // [G] net that moves o / x in each slot, 0xff = none
     int match_assigned;
+    // per-net player descriptions (c4_match_configure); an index that was never configured has the engine's config and the wave kernel
+    int match_configured[C4_MATCH_MAX_NETS];
+    c4_match_player match_player[C4_MATCH_MAX_NETS];   // as resolved: no zeros left in simulations / pb_c_base
+    double2 *match_tab[C4_MATCH_MAX_NETS];        // the index's score table (cfg.simulations + 4 rows), allocated at its first configuration
+    int match_idle;                               // no game in progress: after c4_reset, before c4_match_assign
+    int match_dirty;                              // a configuration changed since d_match_dev was uploaded
     // position queue (c4_queue_positions); is_queue = c4_config.reserved[1]
     int is_queue;
     uint64_t *queue_dev;                          // [queue_n][2], the engine's own copy of the queued positions
@@ -2796,6 +3066,7 @@ int c4_debug_last_fused_kernel(c4_engine *e, char *buf, int cap)
     case FUSED_WAVE: snprintf(name, sizeof(name), "c4_selfplay_wave_kernel<%d,%d,%s>", f.ts, f.mode, q); break;
     case FUSED_BLOCK: snprintf(name, sizeof(name), "c4_selfplay_kernel<%d,%s>", f.ts, q); break;
     case FUSED_MATCH: snprintf(name, sizeof(name), "c4_match_wave_kernel<%d,%d>", f.ts, f.mode); break;
+    case FUSED_MATCH_SPLIT: snprintf(name, sizeof(name), "c4_match_split_kernel<%d,%d,%d>", f.ts, f.mode, f.tw); break;
     default: break;
     }
     if (f.family != FUSED_NONE) snprintf(tail, sizeof(tail), " spread=%d grid=%d", f.spread, f.grid);
@@ -2841,6 +3112,11 @@ int c4_engine_create(const c4_config *cfg, int device, c4_engine **out)
     memset(&e->d_match_uploaded, 0xff, sizeof(Dev));
     e->match_side_o = e->match_side_x = nullptr;
     e->match_assigned = 0;
+    memset(e->match_configured, 0, sizeof(e->match_configured));
+    memset(e->match_player, 0, sizeof(e->match_player));
+    memset(e->match_tab, 0, sizeof(e->match_tab));
+    e->match_idle = 0;
+    e->match_dirty = 0;
     e->is_queue = is_queue;
     e->queue_dev = nullptr;
     e->results_dev = nullptr;
@@ -3060,6 +3336,7 @@ int c4_reset(c4_engine *e, const uint64_t *color0, const uint64_t *color1, int32
     if (d0) (void)hipFree(d0);
     if (d1) (void)hipFree(d1);
     e->launches = 0;
+    e->match_idle = 1;
     return C4_OK;
 }
 
@@ -3173,6 +3450,7 @@ int c4_match_assign(c4_engine *e, const int32_t *net_o, const int32_t *net_x, in
     HIPCHK(e, hipMemcpy(e->match_side_o, so.data(), so.size(), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(e->match_side_x, sx.data(), sx.size(), hipMemcpyHostToDevice));
     e->match_assigned = 1;
+    e->match_idle = 0;
     return C4_OK;
 }
 
@@ -3186,30 +3464,87 @@ int c4_match_steps(c4_engine *e, c4_net *net, int32_t net_index, float *values_d
     if (e->d.use_noise || e->d.nsm > 0) { set_err(e->err, "c4_match_steps plays without root noise and without sampled moves"); return C4_ESTATE; }
     c4net::NetDev nd = net->d;
     nd.stamps = nullptr;
-    if (nd.mode == c4net::NETMODE_F64_PRECISE) {
+    // the kernel of this net index: the one it was configured with, else the wave kernel
+    const bool split = e->match_configured[net_index] && e->match_player[net_index].kernel == C4_MATCH_KERNEL_SPLIT;
+    if (nd.mode == c4net::NETMODE_F64_PRECISE && !split) {
         set_err(e->err, "c4_match_steps cannot hold the 64-filter reference-precision net (eight waves' planes exceed a CU's LDS)");
         return C4_ESTATE;
     }
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : e->stream;
-    if (memcmp(&e->d_match_uploaded, &e->d, sizeof(Dev)) != 0) {   // one description per net: its table, and tree_step stops at the move
+    if (e->match_dirty || memcmp(&e->d_match_uploaded, &e->d, sizeof(Dev)) != 0) {   // one description per net: its table, and tree_step stops at the move
         std::vector<Dev> copies((size_t)e->n_match_nets, e->d);
         for (int k = 0; k < e->n_match_nets; ++k) {
             copies[(size_t)k].cache = e->match_cache[k];
             copies[(size_t)k].stop_after_move = 1;
+            if (e->match_configured[k]) {   // its own search: simulations per move and score table
+                copies[(size_t)k].S = e->match_player[k].simulations;
+                copies[(size_t)k].tabAB = e->match_tab[k];
+            }
         }
         HIPCHK(e, hipMemcpyAsync(e->d_match_dev, copies.data(), sizeof(Dev) * copies.size(), hipMemcpyHostToDevice, st));
         HIPCHK(e, hipStreamSynchronize(st));   // the source dies with this scope
         e->d_match_uploaded = e->d;
+        e->match_dirty = 0;
     }
     const Dev *dk = e->d_match_dev + net_index;
     const dim3 grid((e->d.G + 15) / 16), blk(c4net::NTHREADS);
     const FusedLaunch before = e->last_fused;
-    with_constant<c4net::NETMODE_F64, c4net::NETMODE_F32_PRECISE, c4net::NETMODE_F32_F16>(nd.mode, [&](auto mode) {
-        e->last_fused = {FUSED_MATCH, 16, decltype(mode)::value, -1, -1, 0, (int)grid.x};
-        hipLaunchKernelGGL((c4_match_wave_kernel<16, decltype(mode)::value>), grid, blk, 0, st, dk, nd, values_dev, priors_dev, (int)n_steps, (const uint8_t *)e->match_side_o, (const uint8_t *)e->match_side_x, (int)net_index);
-    });
+    if (split) {
+        // tree waves as launch_split picks them at 16 slots per workgroup; dense packing (spreading a small match over all CUs would
+        // change the launch shape of both kernels)
+        with_constant<c4net::NETMODE_F64_PRECISE, c4net::NETMODE_F64, c4net::NETMODE_F32_PRECISE, c4net::NETMODE_F32_F16>(nd.mode, [&](auto mode) {
+            constexpr int MODE = decltype(mode)::value;
+            constexpr int TW = MODE == c4net::NETMODE_F64 ? 2 : 4;
+            e->last_fused = {FUSED_MATCH_SPLIT, 16, MODE, TW, -1, 0, (int)grid.x};
+            hipLaunchKernelGGL((c4_match_split_kernel<16, MODE, TW>), grid, blk, 0, st, dk, nd, values_dev, priors_dev, (int)n_steps, (const uint8_t *)e->match_side_o, (const uint8_t *)e->match_side_x, (int)net_index);
+        });
+    } else {
+        with_constant<c4net::NETMODE_F64, c4net::NETMODE_F32_PRECISE, c4net::NETMODE_F32_F16>(nd.mode, [&](auto mode) {
+            e->last_fused = {FUSED_MATCH, 16, decltype(mode)::value, -1, -1, 0, (int)grid.x};
+            hipLaunchKernelGGL((c4_match_wave_kernel<16, decltype(mode)::value>), grid, blk, 0, st, dk, nd, values_dev, priors_dev, (int)n_steps, (const uint8_t *)e->match_side_o, (const uint8_t *)e->match_side_x, (int)net_index);
+        });
+    }
     if (int rc = fused_launch_status(e, before, "c4_match_steps")) return rc;
     e->launches += n_steps;
+    return C4_OK;
+}
+
+int c4_match_configure(c4_engine *e, int32_t net_index, const c4_match_player *p)
+{
+    if (!e) { set_err(g_err, "c4_match_configure: null engine"); return C4_EINVAL; }
+    if (e->n_match_nets <= 0) { set_err(e->err, "c4_match_configure: the engine was not created for matches (c4_config.reserved[0] = n_match_nets)"); return C4_ESTATE; }
+    if (!e->match_idle) { set_err(e->err, "c4_match_configure: a match is in progress; configure after c4_reset and before c4_match_assign"); return C4_ESTATE; }
+    if (!p) { set_err(e->err, "c4_match_configure: null player"); return C4_EINVAL; }
+    if (net_index < 0 || net_index >= e->n_match_nets) { set_err(e->err, "c4_match_configure: net_index %d out of range [0,%d)", net_index, e->n_match_nets); return C4_EINVAL; }
+    if (p->simulations < 0 || p->simulations > e->cfg.simulations) {
+        set_err(e->err, "c4_match_configure: simulations = %d out of range [1,%d] (the engine's node pools are sized by c4_config.simulations; 0 = that value)", p->simulations, e->cfg.simulations);
+        return C4_EINVAL;
+    }
+    if (p->pb_c_base < 0) { set_err(e->err, "c4_match_configure: pb_c_base = %d must be >= 1 (0 = the engine's)", p->pb_c_base); return C4_EINVAL; }
+    if (!std::isfinite(p->pb_c_init)) { set_err(e->err, "c4_match_configure: pb_c_init = %g is not finite", p->pb_c_init); return C4_EINVAL; }
+    if (p->kernel != C4_MATCH_KERNEL_WAVE && p->kernel != C4_MATCH_KERNEL_SPLIT) { set_err(e->err, "c4_match_configure: kernel = %d is neither C4_MATCH_KERNEL_WAVE nor C4_MATCH_KERNEL_SPLIT", p->kernel); return C4_EINVAL; }
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2]) { set_err(e->err, "c4_match_configure: reserved fields must be 0"); return C4_EINVAL; }
+    c4_match_player q = *p;
+    if (q.simulations == 0) q.simulations = e->cfg.simulations;
+    if (q.pb_c_base == 0) q.pb_c_base = e->cfg.pb_c_base;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipDeviceSynchronize());
+    // the index's score table: c4_engine_create's rows (host libm) with this player's constants, as long as the engine's so
+    // that every parent visit count the pools can hold has its row
+    const size_t nt = (size_t)e->cfg.simulations + 4;
+    std::vector<double2> AB(nt);
+    for (size_t n = 0; n < nt; ++n) {
+        AB[n].x = std::log((double)((long long)n + q.pb_c_base + 1) / (double)q.pb_c_base) + q.pb_c_init;
+        AB[n].y = std::sqrt((double)n);
+    }
+    if (!e->match_tab[net_index]) {
+        int rc = dev_alloc(e, &e->match_tab[net_index], nt);   // freed with the engine's other allocations
+        if (rc) return rc;
+    }
+    HIPCHK(e, hipMemcpy(e->match_tab[net_index], AB.data(), nt * sizeof(double2), hipMemcpyHostToDevice));
+    e->match_player[net_index] = q;
+    e->match_configured[net_index] = 1;
+    e->match_dirty = 1;
     return C4_OK;
 }
 

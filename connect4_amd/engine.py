@@ -143,6 +143,22 @@ class Engine:
         self._check(self._lib.c4_match_steps(self._h, net._h, int(net_index), C.c_void_p(values.data_ptr()),
                                              C.c_void_p(priors.data_ptr()), int(n_steps), C.c_void_p(stream or 0)))
 
+    def match_configure(self, net_index, simulations=None, pb_c_base=None, pb_c_init=None, kernel="wave"):
+        """The player behind net `net_index` of a match engine (c4_match_configure): its simulations per move (at most the
+        engine's), pb_c_base, pb_c_init -- None: the engine's -- and its match kernel, "wave" (c4_match_wave_kernel) or
+        "split" (c4_match_split_kernel, which also holds the 64-filter "f32x3w" net).  After reset(), before match_assign()."""
+        kernels = {"wave": L.MATCH_KERNEL_WAVE, "split": L.MATCH_KERNEL_SPLIT}
+        if kernel not in kernels:
+            raise ValueError("kernel must be 'wave' or 'split', not %r" % (kernel,))
+        p = L.MatchPlayer()
+        p.simulations = 0 if simulations is None else int(simulations)
+        p.pb_c_base = 0 if pb_c_base is None else int(pb_c_base)
+        p.pb_c_init = float(self.cfg.pb_c_init if pb_c_init is None else pb_c_init)
+        p.kernel = kernels[kernel]
+        if (simulations is not None and p.simulations == 0) or (pb_c_base is not None and p.pb_c_base == 0):
+            raise ValueError("simulations and pb_c_base must be positive (None: the engine's)")
+        self._check(self._lib.c4_match_configure(self._h, int(net_index), C.byref(p)))
+
     def last_fused_kernel(self):
         """The fused kernel the last selfplay_steps / match_steps call launched, e.g.
         "c4_selfplay_split_kernel<16,1,3,false> spread=0 grid=3" (c4_debug_last_fused_kernel); "" before the first one.

@@ -40,7 +40,7 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
                    timings: Optional[dict] = None, precision: Optional[str] = None, test_sets: Optional[dict] = None,
                    train_stats: bool = False, match_every: Optional[int] = None, match_plies: int = 1,
                    review_empties: Optional[int] = None, review_table=None, exact_targets: bool = False,
-                   exact_leaves: Optional[int] = None, exact_leaf_budget: Optional[int] = None):
+                   exact_leaves: Optional[int] = None, exact_leaf_budget: Optional[int] = None, match_unlike: bool = False):
     """Returns (PackedGames of all ranks, last_loss).  With torch.distributed initialised every rank plays its shard and
     all ranks receive all games.  There is ONE model, as in the reference (training.py:147-153, model.py:143-147): rank 0
     writes save_dir/<gen>/{data.pth, games.pkl} (storage.py:15-16, data.py:47-64), trains on `trainer.device` over the
@@ -50,7 +50,7 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
     `test_sets` (name -> stats.LabelledSet or the path of a Connect4Dataset file) and `train_stats`: see score_test_sets and
     Trainer.train(stats=True); both are rank 0's work and add no collective.  A path is loaded on every call: a caller that
     loops over run_generation passes LabelledSets (load_test_sets once); run_generations loads each path once.
-    `match_every` / `match_plies`: see generation_match (rank 0, after the checkpoint, when gen % match_every == 0).
+    `match_every` / `match_plies` / `match_unlike`: see generation_match (rank 0, after the checkpoint, when gen % match_every == 0).
     `review_empties` / `review_table` / `exact_targets`: see review_generation (rank 0, after the games are gathered and
     before the training tensors are built; no collective).  The games returned are the games as played.
     `exact_leaves` / `exact_leaf_budget`: see _self_play; timings["exact_leaves"] holds this rank's counters."""
@@ -95,7 +95,7 @@ def run_generation(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir:
     if rank == 0:
         _report(trainer, test_sets, train_stats, save_dir, gen, timings)
         if match_every and gen % match_every == 0:
-            generation_match(trainer, config, save_dir, gen, device, precision, match_plies, timings)
+            generation_match(trainer, config, save_dir, gen, device, precision, match_plies, timings, unlike=match_unlike)
     return games, loss
 
 
@@ -223,12 +223,14 @@ def append_history(path, gen, row):
 
 
 # -- strength after a generation (training.py:176-207) ----------------------------------------------------------------
-def generation_match(trainer, config, save_dir, gen, device=0, precision=None, plies=1, timings=None):
+def generation_match(trainer, config, save_dir, gen, device=0, precision=None, plies=1, timings=None, unlike=False):
     """TrainingLoop._match: the trainer's net ("AlphaZero", the run's simulations / pb_c_base / pb_c_init, no noise, no
     sampled moves) against "Evaluate_centre_with_prior" while gen <= 10 and against "Older net" -- save_dir/<gen-10>/net.pth,
     MCTSConfig(simulations) -- afterwards, as Match(plies, switch=True).  Two nets meet inside the fused kernel
     (match.DeviceMatch); the centre opponent, and any pairing the device path refuses (match.device_match_reason), go
-    through the host lock-step Match.  The result -- wins / draws / losses / return from the new net's side -- is appended
+    through the host lock-step Match.  `unlike` is handed on to play_match: the players are then described to the engine one
+    by one, so the two searches need not agree and a 64-filter reference-precision run ("f32x3w") plays on the device too, in
+    the split match kernel.  The result -- wins / draws / losses / return from the new net's side -- is appended
     to save_dir/match_results.pkl (append_history) and, with "opponent" and the "path" taken ("device" / "host"), put into
     timings["match"].  Rank 0's work; no collective."""
     import torch
@@ -249,7 +251,7 @@ def generation_match(trainer, config, save_dir, gen, device=0, precision=None, p
             nets.append(make_selfplay_net(old["net_state_dict"], device=device, precision=precision))
             players.append(MCTS("Older net", MCTSConfig(config.simulations), DeviceNetEvaluator(nets[1], device), device=device))
         t0 = time.perf_counter()
-        result, path = play_match(False, players[0], players[1], plies=plies, switch=True)
+        result, path = play_match(False, players[0], players[1], plies=plies, switch=True, **({"unlike": True} if unlike else {}))
         seconds = time.perf_counter() - t0
     finally:
         for p in players:
@@ -311,7 +313,7 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
                     test_sets: Optional[dict] = None, train_stats: bool = False, match_every: Optional[int] = None,
                     match_plies: int = 1, review_empties: Optional[int] = None, review_table=None, exact_targets: bool = False,
                     exact_leaves: Optional[int] = None, exact_leaf_budget: Optional[int] = None, merge_duplicates: bool = False,
-                    merge_mirror: bool = True):
+                    merge_mirror: bool = True, match_unlike: bool = False):
     """n_generations generations of run_generation -- same seeds (seed + 1000 * gen), same files (data.pth, net.pth,
     optional games.pkl), same broadcast of the trained state -- with the sliding window (data.py:66-75) kept on rank 0's GPU
     as packed positions (replay.ReplayWindow): each generation's games are appended to it and trained with
@@ -325,7 +327,7 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
     holds.  `timings`: a list that receives one dict per generation -- run_generation's keys, plus window_rows and
     window_bytes, and with `test_sets` / `train_stats` (as run_generation: scored on rank 0 after each checkpoint, appended
     to save_dir/<name>.pkl) the sets' names and train_stats, and with `match_every` (generation_match on rank 0 after the
-    checkpoint of every generation with gen % match_every == 0; save_dir/match_results.pkl) "match", and with `review_empties`
+    checkpoint of every generation with gen % match_every == 0, `match_unlike` as there; save_dir/match_results.pkl) "match", and with `review_empties`
     (review_generation, as run_generation; with `exact_targets` the window's segment carries the exact targets) "review" and
     "review_s", and with `exact_leaves` (as run_generation) "exact_leaves".  With `merge_duplicates` each generation trains on
     window.merged(mirror=merge_mirror) -- identical positions (and, with merge_mirror, mirror images) as one row with the mean
@@ -388,7 +390,7 @@ def run_generations(trainer: Trainer, config: MCTSConfig, n_games: int, save_dir
         if rank == 0:
             _report(trainer, test_sets, train_stats, save_dir, gen, report)
             if match_every and gen % match_every == 0:
-                generation_match(trainer, config, save_dir, gen, device, precision, match_plies, report)
+                generation_match(trainer, config, save_dir, gen, device, precision, match_plies, report, unlike=match_unlike)
         if timings is not None:
             timings.append(report)
     return window, losses

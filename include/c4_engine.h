@@ -515,11 +515,37 @@ int c4_selfplay_steps(c4_engine *e, c4_net *net, float *values_dev, float *prior
  * Which launch runs a simulation, and in which order the nets are served, never changes a game: the games are those
  * that alternating c4_step / c4_net_forward searches of the two nets play, position by position.
  * values_dev / priors_dev as c4_selfplay_steps (one pair of buffers for all nets, persisting between the calls).
- * The 64-filter C4_NET_F32X3_WIDE net cannot be held (C4_ESTATE), as with C4_FUSED_MODE=wave. */
+ * The kernel is the one the net index was configured with (c4_match_configure below); an index that was never
+ * configured runs c4_match_wave_kernel with the engine's search config.  c4_match_wave_kernel cannot hold the 64-filter
+ * C4_NET_F32X3_WIDE net (C4_ESTATE, as with C4_FUSED_MODE=wave): configure its index with C4_MATCH_KERNEL_SPLIT.
+ * c4_match_configure: the player behind net index `net_index` (an addition: C4_ABI_VERSION stays).  The nets of a match
+ * need not be alike: a slot's whole search is run by the launches of the net that is to move in it, and between two
+ * nets' turns the slot holds a root and nothing else, so every net index may have its own
+ *   simulations   1 .. c4_config.simulations (the node pools are sized by the engine's value: create the engine with the
+ *                 largest); 0 = the engine's
+ *   pb_c_base     >= 1; 0 = the engine's
+ *   pb_c_init     finite (the rule of c4_engine_create)
+ *   kernel        C4_MATCH_KERNEL_WAVE  c4_match_wave_kernel
+ *                 C4_MATCH_KERNEL_SPLIT c4_match_split_kernel: c4_selfplay_steps' split kernel (tree waves + network
+ *                                       waves) under the same one-net-per-launch rule; holds every net mode
+ * and nets on different kernels meet in one match.  The engine builds the index's score table with the host libm code
+ * of c4_engine_create and owns it.  Valid on a match engine while no game is in progress -- after c4_reset, before
+ * c4_match_assign -- else C4_ESTATE; a bad value is C4_EINVAL and leaves the engine as it was (reserved must be 0).  The
+ * configuration holds until the next c4_match_configure of that index or c4_engine_destroy.  Synchronous. */
 #define C4_MATCH_MAX_NETS 16
+#define C4_MATCH_KERNEL_WAVE  0
+#define C4_MATCH_KERNEL_SPLIT 1
+typedef struct {
+    int32_t simulations;
+    int32_t pb_c_base;
+    double pb_c_init;
+    int32_t kernel;
+    int32_t reserved[3];
+} c4_match_player;
 int c4_match_assign(c4_engine *e, const int32_t *net_o, const int32_t *net_x, int32_t n);
 int c4_match_steps(c4_engine *e, c4_net *net, int32_t net_index, float *values_dev, float *priors_dev, int32_t n_steps,
                    void *hip_stream);
+int c4_match_configure(c4_engine *e, int32_t net_index, const c4_match_player *p);
 /* -- position queue: search a list of positions of any length on the engine's slots -------------------------------
  * (stands in for a loop of mcts.search(config, board, evaluator), mcts.py:94-121, over a test set or a generation's
  * positions.)  An engine created with c4_config.reserved[1] = 1 (and stop_after_move = 1; any eval_mode) searches N
@@ -604,6 +630,7 @@ int c4_debug_latency_stamps(c4_engine *e, unsigned long long *out);
  * 2 fp16 64 filters, 3 f32x3w), the run-time slot packing and the grid, e.g.
  *     "c4_selfplay_split_kernel<16,1,3,false> spread=0 grid=3"    "c4_selfplay_wave_kernel<32,2,true> spread=0 grid=2"
  *     "c4_selfplay_kernel<16,false> spread=0 grid=3"              "c4_match_wave_kernel<16,2> spread=0 grid=1"
+ *     "c4_match_split_kernel<16,3,4> spread=0 grid=7"             (TS, MODE, TW; a net index configured with C4_MATCH_KERNEL_SPLIT)
  * and "" before the first such launch.  A launch that the runtime refused (the call returned C4_EDEVICE) is not recorded: the
  * name stays that of the last launch that started.  Host bookkeeping only: no device work, no synchronisation.  Returns the length written
  * (without the terminator), or C4_EINVAL for a null argument or a `cap` that cannot hold the name and its terminator (128
